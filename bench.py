@@ -10,11 +10,13 @@ data-path collective; rank 0 broadcasts the per-stream parameter block once (RCC
 `python bench.py --gpus N` starts the N ranks itself (re-exec under torch.distributed.run) when it was not
 launched by a distributed launcher; it never prints a line whose n_gpus differs from --gpus.
 
-Prints ONE JSON line on rank 0.  Besides the driver's contract it carries
+A plain run renders the frames, warms up, times --steps steps and prints ONE JSON line on rank 0 (metric, value, unit,
+ms_per_step, ...).  `--dump-outputs DIR` writes the detections of the last timed step as DIR/<name>.npy.  `--full` adds
   roofline        -- the threshold pass (the kernel BASELINE.json's metric names), HIP-event timed
-  cpu_baseline    -- the CPU restatement (oracle/) timed on this box's host cores on a bounded sample
+  cpu_baseline    -- the CPU restatement (oracle/) timed on the host's cores on a bounded sample
   stage_roofline  -- achieved HBM fraction of the other streaming stages (algorithmic bytes of DESIGN.md section 4)
-  extra           -- median / min step time, batch-size sweep, H2D-included rate, single-frame latency
+  extra           -- batch-size sweep, bgr8 input, H2D-included rate, single-frame latency, sigma 0, decimate 2
+  parity_gate     -- every frame of the batch (and the stages of 16) against the CPU restatement
 """
 import argparse
 import json
@@ -47,10 +49,15 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; gloo is for the shared-GPU smoke only")
     ap.add_argument("--shared-gpu", action="store_true",
                     help="smoke only: ranks may share a device (local_rank %% device_count) when the box has fewer GPUs than ranks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure stage times, rooflines, the CPU baseline and the informational rows, "
+                         "and run the parity gate against the CPU restatement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no parity gate")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no threshold-only roofline")
     ap.add_argument("--small-row", type=int, default=0, help=argparse.SUPPRESS)   # (internal: one row of the batch sweep, own process)
-    ap.add_argument("--no-extra", action="store_true", help="skip the informational measurements (sweep, H2D, latency, sigma 0, decimate 2)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the informational measurements (sweep, H2D, latency, sigma 0, decimate 2)")
     return ap.parse_args(argv)
 
 
@@ -80,6 +87,29 @@ def render_frames(seed, n, sigma):
     with ThreadPoolExecutor(max_workers=min(32, os.cpu_count() or 1)) as ex:
         imgs = list(ex.map(lambda i: synth.scene_c2(seed=seed + i, sigma=sigma)[0], range(n)))
     return np.stack(imgs)
+
+
+DUMP_LIMIT_BYTES = 60 << 20      # under the 64 MB the outputs may take, .npy headers included
+
+
+def dump_outputs(outdir, prep, prefix=""):
+    """The records the timed amdAprilTagsDetectBatchEx call handed back (prep['out'] / prep['cnt'], before anything else runs
+    on the handle): per-frame counts, and every detection in frame order with the library's order inside a frame, all in
+    float64 (the integer fields are exact in it).  A batch that could exceed 64 MB at max_dets records per frame is cut to
+    evenly spaced frames; `frame` keeps each record's index in the batch."""
+    n, max_dets = prep["n"], prep["max_dets"]
+    rec = np.ctypeslib.as_array(prep["out"]).reshape(n, max_dets)
+    cnt = np.ctypeslib.as_array(prep["cnt"]).astype(np.int64)
+    frame_bytes = 8 * (1 + max_dets * (5 + 9 + 2 + 8 + 9 + 3))     # count + float64 values of max_dets records, as written below
+    frames = np.linspace(0, n - 1, min(n, DUMP_LIMIT_BYTES // frame_bytes)).astype(np.int64)
+    keep = np.arange(max_dets)[None, :] < cnt[frames, None]
+    r = rec[frames][keep]
+    arrays = {"count": cnt[frames], "frame": frames[np.nonzero(keep)[0]], "family": r["family"], "id": r["id"],
+              "hamming": r["hamming"], "decision_margin": r["decision_margin"], "H": r["H"].reshape(-1, 3, 3),
+              "center": r["c"], "corners": r["p"], "R": r["R"].reshape(-1, 3, 3), "t": r["t"]}
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, prefix + k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def build_native_oracle():
@@ -331,6 +361,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     out = det.unpack(prep)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prep, "rank%d_" % rank if rank else "")
     rank_fps = [B * args.steps / dt_own]
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
@@ -341,11 +373,12 @@ def main():
         dist.all_gather(all_t, mine_t)
         rank_fps = [float(t.item()) for t in all_t]
     flags = det.frame_flags(B)
-    det.set_profiling(True)
-    det.run_prepared(prep)
-    stage_ms = det.stage_ms()
-    counts = det.mean_counts(B)
-    det.set_profiling(False)
+    if args.full:
+        det.set_profiling(True)
+        det.run_prepared(prep)
+        stage_ms = det.stage_ms()
+        counts = det.mean_counts(B)
+        det.set_profiling(False)
     mem = det.device_bytes()
 
     # Parity gate in the same run: EVERY rank compares ALL frames of its batch with the CPU restatement (ids exact; corners,
@@ -358,7 +391,7 @@ def main():
     byframe = None
     cpu_rec = None
     gated = 0
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if rank == 0:
             cpu_rec, byframe = cpu_baseline(frames_np, intr, args.decimate, tag_size)
         if world > 1:
@@ -419,7 +452,7 @@ def main():
         gate_all = gate_ok
 
     extra = {}
-    if rank == 0 and not args.no_extra:
+    if rank == 0 and args.full and not args.no_extra:
         extra = extra_measurements(det, batch, frames_np, intr, args, torch, dev, tag_size, dev_index)
     det.close()
 
@@ -443,15 +476,16 @@ def main():
             "detections_per_frame": float(np.mean(ndet)), "frame_flags_nonzero": int(sum(1 for f in flags if f)),
             "step_ms_median": round(float(np.median(step_ms)), 3), "step_ms_min": round(float(np.min(step_ms)), 3),
             "fps_median_step": round(B / (float(np.median(step_ms)) * 1e-3), 1), "fps_best_step": round(B / (float(np.min(step_ms)) * 1e-3), 1),
-            "stage_ms_per_step": {k: round(v, 3) for k, v in stage_ms.items()},
-            "stage_roofline": stage_rooflines(stage_ms, B, counts, args.decimate),
-            "frame_content_mean": counts, "device_bytes_handle": mem,
+            **({"stage_ms_per_step": {k: round(v, 3) for k, v in stage_ms.items()},
+                "stage_roofline": stage_rooflines(stage_ms, B, counts, args.decimate),
+                "frame_content_mean": counts} if args.full else {}),
+            "device_bytes_handle": mem,
         }
         if extra:
             rec["extra"] = extra
         if cpu_rec is not None:
             rec["cpu_baseline"] = cpu_rec
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             rec["roofline"] = threshold_roofline(batch[:min(B, 160)], args.decimate)
             thr = rec["stage_roofline"].get("threshold")
             if thr:   # the same kernel inside the timed pipeline (B frames, HIP-event stage time of this run)

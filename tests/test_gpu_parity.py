@@ -1134,7 +1134,7 @@ def test_bench_two_ranks_on_one_gpu(built):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--shared-gpu", "--steps", "2",
-           "--warmup", "1", "--batch", "32", "--distinct", "32", "--no-extra", "--no-roofline"]
+           "--warmup", "1", "--batch", "32", "--distinct", "32", "--full", "--no-extra", "--no-roofline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-2500:])
@@ -1163,7 +1163,7 @@ def test_bench_eight_ranks_on_one_gpu(built):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--shared-gpu", "--steps", "2",
-           "--warmup", "1", "--batch", "16", "--distinct", "16", "--no-extra", "--no-roofline"]
+           "--warmup", "1", "--batch", "16", "--distinct", "16", "--full", "--no-extra", "--no-roofline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=root, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-2500:])

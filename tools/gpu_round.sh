@@ -16,7 +16,7 @@ timeout 1200 python -m pytest tests -m gpu -q --maxfail=8 -x -p no:cacheprovider
 echo "pytest exit $?" | tee -a $OUT/summary.txt
 tail -3 $OUT/pytest.log | tee -a $OUT/summary.txt
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 900 python bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench exit $?" | tee -a $OUT/summary.txt
 tail -c 7000 $OUT/bench.json | tee -a $OUT/summary.txt
 if [ "$2" != "noprof" ]; then
