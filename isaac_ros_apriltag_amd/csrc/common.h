@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "growth.h"   // FrameCounters, AT_FLAG_CANDS
 #include "tools_hooks.h"
 
 #define AT_NO_LABEL 0xFFFFFFFFu
@@ -13,7 +14,6 @@
 #define AT_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
 #define AT_INVALID_SLOT 0xFFFFFFFFu
 #define AT_MAX_FAMILIES 4
-#define AT_FLAG_CANDS 0x20u   // internal frame flag: quad-candidate list full (never reported; see run_batch)
 
 // Per-frame descriptor (device copy of amdAprilTagsImageInput_t + intrinsics), one per batch slot.
 struct FrameDesc {
@@ -26,22 +26,6 @@ struct FrameDesc {
   const uint8_t* src;  // colour submissions (amdAprilTagsEncoding != mono8): the caller's interleaved frame; null otherwise
   uint32_t src_pitch;
   uint32_t fmt;        // amdAprilTagsEncoding of `src`
-};
-
-// Per-frame counters (one struct per batch slot), zeroed at the start of every submission.
-struct FrameCounters {
-  uint32_t npoints_raw;   // staged boundary points
-  uint32_t nclusters;     // kept clusters
-  uint32_t npoints_kept;  // points in kept clusters (allocation cursor)
-  uint32_t nquads;
-  uint32_t ndets;         // raw detections before reconcile
-  uint32_t flags;         // AMDAT_FLAG_*
-  uint32_t nout;          // detections after reconcile
-  uint32_t nroots;        // tile-local component roots (CC root list)
-  uint32_t ncand;         // quad candidates (four fitted lines) awaiting k_quad_finish
-  uint32_t nlong;         // long staging records (k_points -> k_scatter)
-  uint32_t seq;           // FrameDesc::seq of the launch that produced these counters, written last (k_reconcile): the host checks it
-                          // after its stream wait, so results of an EARLIER launch can never be taken for this one's
 };
 
 struct ClusterRec {

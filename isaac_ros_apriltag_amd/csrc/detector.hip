@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -138,6 +139,15 @@ uint32_t next_pow2(uint32_t v) {
   while (p < v) p <<= 1;
   return p;
 }
+
+// A device allocation the handle owns: its pointer and the bytes device_bytes counts for it (dev_alloc / dev_free).
+struct DevAlloc {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+template <class T> struct DevBuf : DevAlloc {
+  operator T*() const { return static_cast<T*>(p); }
+};
 }  // namespace
 
 // One size class of the quad fit: workgroup size, LDS key capacity, cluster sizes (lo, hi], persistent grid,
@@ -152,8 +162,8 @@ struct FqClass {
   int slot_cap;
   int pop;                                // clusters taken from the work list per atomic
   int small_k = 0;                        // > 0: k_fit_small<small_k> (keys and sweep state in registers, moments in LDS), no scratch
-  double* d_lf = nullptr;                 // grid x slot_cap x 6 doubles
-  double* d_errs = nullptr;               // grid x slot_cap x 2 doubles: error arrays of clusters that exceed what the
+  DevBuf<double> d_lf;                    // grid x slot_cap x 6 doubles
+  DevBuf<double> d_errs;                  // grid x slot_cap x 2 doubles: error arrays of clusters that exceed what the
                                           // kernel keeps in LDS / registers (slot_cap > 16 x nt, or > sort_cap)
 };
 
@@ -169,59 +179,48 @@ struct amdAprilTagsDetector_st {
   bool aux_prioritised = false;      // the side streams carry priorities (handles above eight frames per submission; see creation)
   hipEvent_t ev_fork = nullptr, ev_join[FQ_NAUX] = {};
   // device buffers
-  uint8_t* d_gray = nullptr;          // working-size gray plane: decimated handles, and (allocated on first use) colour submissions at decimate 1
-  uint8_t* d_conv = nullptr;          // full-size mono8 plane of colour submissions that take the conversion launch (decimate > 1, tile_size 8)
+  DevBuf<uint8_t> d_gray;             // working-size gray plane: decimated handles, and (allocated on first use) colour submissions at decimate 1
+  DevBuf<uint8_t> d_conv;             // full-size mono8 plane of colour submissions that take the conversion launch (decimate > 1, tile_size 8)
   size_t conv_pitch = 0;
-  uint8_t* d_thr = nullptr;
-  uint8_t* d_tmin = nullptr;         // per-tile min / max of the two-pass threshold (tile_size != 4 only)
-  uint8_t* d_tmax = nullptr;
-  uint32_t* d_label = nullptr;
-  uint32_t* d_csize = nullptr;
-  uint32_t* d_roots = nullptr;
-  uint32_t* d_perim = nullptr;       // tile perimeters (class + tile-local root per pixel), k_cc_local -> k_cc_border (kernels_cc.h: CcPerim)
-  unsigned long long* d_hkeys = nullptr;
-  uint32_t* d_hcnt = nullptr;
-  uint32_t* d_hoff = nullptr;
-  uint32_t* d_stage = nullptr;       // one word per staged boundary point (kernels_cluster.h, pass 3 of k_points)
-  uint2* d_bhdr = nullptr;           // per block (tile) of k_points: {first staging word, words}
-  uint2* d_btab = nullptr;           // per block: its component-pair table, {pair-table slot, base rank inside the cluster} per entry
-  uint4* d_long = nullptr;           // {slot, rank, packed point}: emissions without a block-table entry
-  uint32_t* d_pts = nullptr;
-  ClusterRec* d_clusters = nullptr;
-  uint32_t* d_work = nullptr;        // work lists of the quad fit (all classes, FqWorkLayout)
+  DevBuf<uint8_t> d_thr;
+  DevBuf<uint8_t> d_tmin;            // per-tile min / max of the two-pass threshold (tile_size != 4 only)
+  DevBuf<uint8_t> d_tmax;
+  DevBuf<uint32_t> d_label;
+  DevBuf<uint32_t> d_csize;
+  DevBuf<uint32_t> d_roots;
+  DevBuf<uint32_t> d_perim;          // tile perimeters (class + tile-local root per pixel), k_cc_local -> k_cc_border (kernels_cc.h: CcPerim)
+  DevBuf<unsigned long long> d_hkeys;
+  DevBuf<uint32_t> d_hcnt;
+  DevBuf<uint32_t> d_hoff;
+  DevBuf<uint32_t> d_stage;          // one word per staged boundary point (kernels_cluster.h, pass 3 of k_points)
+  DevBuf<uint2> d_bhdr;              // per block (tile) of k_points: {first staging word, words}
+  DevBuf<uint2> d_btab;              // per block: its component-pair table, {pair-table slot, base rank inside the cluster} per entry
+  DevBuf<uint4> d_long;              // {slot, rank, packed point}: emissions without a block-table entry
+  DevBuf<uint32_t> d_pts;
+  DevBuf<ClusterRec> d_clusters;
+  DevBuf<uint32_t> d_work;           // work lists of the quad fit (all classes, FqWorkLayout)
   bool tables_dirty = false;         // a submission was cut short after k_points: the pair table is not empty
-  uint32_t* d_workctl = nullptr;     // [0..7] items per class, [8..15] pop cursors, [16..23] items per class after k_fit_prefilter, [24] the prefilter's own cursor
-  uint32_t* d_work2 = nullptr;       // compact work lists of the prefiltered classes (same layout as d_work)
-  unsigned long long* d_keys_scr = nullptr;  // only when a cluster can exceed the LDS key array (large images)
-  QuadRec* d_quads = nullptr;
-  DetRec* d_dets = nullptr;
-  uint16_t* d_order = nullptr;
-  FitCand* d_cands = nullptr;        // quad candidates of k_fit_quads (four lines each), consumed by k_quad_finish
+  DevBuf<uint32_t> d_workctl;        // [0..7] items per class, [8..15] pop cursors, [16..23] items per class after k_fit_prefilter, [24] the prefilter's own cursor
+  DevBuf<uint32_t> d_work2;          // compact work lists of the prefiltered classes (same layout as d_work)
+  DevBuf<unsigned long long> d_keys_scr;     // only when a cluster can exceed the LDS key array (large images)
+  DevBuf<QuadRec> d_quads;
+  DevBuf<DetRec> d_dets;
+  DevBuf<uint16_t> d_order;
+  DevBuf<FitCand> d_cands;           // quad candidates of k_fit_quads (four lines each), consumed by k_quad_finish
   FrameCounters* d_counters = nullptr;
-  FrameDesc* d_frames = nullptr;
-  uint64_t* d_codes[AT_MAX_FAMILIES] = {nullptr, nullptr, nullptr, nullptr};
+  DevBuf<FrameDesc> d_frames;
+  DevBuf<uint64_t> d_codes[AT_MAX_FAMILIES];
+  std::vector<DevAlloc*> owned;      // every holder above that has had an allocation (dev_alloc): what free_all releases
   unsigned long long* d_ptprof = nullptr;  // per-phase cycle counters of k_points (same builds), inside d_fqprof's allocation
-  unsigned long long* d_fqprof = nullptr;  // per-phase cycle counters of k_fit_quads (-DAMDAT_FQ_PROFILE builds only)
+  DevBuf<unsigned long long> d_fqprof;     // per-phase cycle counters of k_fit_quads (-DAMDAT_FQ_PROFILE builds only)
   FqClass cls[FQ_NCLS];
   FqWorkLayout work_layout;
   FqWorkLayout work_layout_small;    // small submissions: the k_fit_small classes are empty, the one-wave class starts at 0 (issue_pipeline)
   int prefilter_class = FQ_C0 + 2;           // first size class whose clusters go through k_fit_prefilter (those above 2048 points)
-  bool grow_points = false;          // point capacity follows the content (no explicit max_points)
-  bool grow_hash = false;            // the same for the component-pair table (no explicit hash_slots)
-  bool grow_quads = false;           // the same for the quad list (no explicit max_quads): doubles up to the cluster capacity
-  bool grow_clusters = false;        // and for the cluster list (no explicit max_clusters): up to ccap_hard
-  uint32_t ccap_hard = 0;            // what the pair table and a work item's index bits admit
-  size_t clusters_bytes = 0;
-  size_t quads_bytes = 0;
-  bool pending_hash_grow = false;
+  GrowLimits grow = {};              // which capacities follow the content, and up to what (growth.h; set at creation)
+  bool pending_hash_grow = false;    // the last submission crowded the pair table: it grows before the next one (begin_batch)
   uint32_t lcap_div = 0;             // long-record capacity = point capacity / lcap_div (alloc_point_buffers; halves when the long records overflow)
   bool unusable = false;             // a capacity change failed twice (grown and original size): buffers are gone, every later call reports it
-  size_t cands_bytes = 0;
-  uint32_t hcap_hard = 0;
-  size_t hash_buffer_bytes[3] = {0, 0, 0};
-  uint32_t pcap_hard = 0;            // 2 points per working pixel: what any content stays below
-  size_t point_buffer_bytes[5] = {0, 0, 0, 0, 0};
-  uint32_t grown = 0;                // number of times the point buffers grew (amdAprilTagsGetDeviceBytes reports the result)
   // pinned host buffers
   FrameDesc* h_frames = nullptr;
   FrameCounters* h_counters = nullptr;
@@ -431,16 +430,34 @@ int amdAprilTagsFamilyFromName(const char* name) {
 
 const char* amdAprilTagsStageName(uint32_t stage) { return stage < AMDAT_NUM_STAGES ? kStageNames[stage] : ""; }
 
+// Every device allocation of a handle goes through these two, and only they change device_bytes (amdAprilTagsGetDeviceBytes).  An
+// empty buffer gets 16 bytes (a valid launch argument).  A failed allocation leaves nothing behind: no holder, no pending error.
+static bool dev_alloc(amdAprilTagsDetector_st* D, DevAlloc& b, size_t bytes) {
+  if (!bytes) bytes = 16;
+  if (hipMalloc(&b.p, bytes) != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return false; }
+  b.bytes = bytes;
+  D->device_bytes += bytes;
+  if (std::find(D->owned.begin(), D->owned.end(), &b) == D->owned.end()) D->owned.push_back(&b);
+  return true;
+}
+static void dev_free(amdAprilTagsDetector_st* D, DevAlloc& b) {
+  if (b.p) hipFree(b.p);
+  D->device_bytes -= b.bytes;
+  b = DevAlloc();
+}
+// Replaces b's buffer, the new one allocated before the old one is freed (b is untouched if that fails).
+static bool dev_regrow(amdAprilTagsDetector_st* D, DevAlloc& b, size_t bytes) {
+  DevAlloc old = b;
+  b = DevAlloc();
+  if (!dev_alloc(D, b, bytes)) { b = old; return false; }
+  dev_free(D, old);
+  return true;
+}
+
 static void free_all(amdAprilTagsDetector_st* D) {
   for (auto& g : D->graphs) if (g.exec) hipGraphExecDestroy(g.exec);
   for (hipGraphExec_t e : D->retired_graphs) hipGraphExecDestroy(e);
-  hipFree(D->d_gray); hipFree(D->d_conv); hipFree(D->d_thr); hipFree(D->d_tmin); hipFree(D->d_tmax); hipFree(D->d_label); hipFree(D->d_csize); hipFree(D->d_roots); hipFree(D->d_perim); hipFree(D->d_hkeys);
-  hipFree(D->d_hcnt); hipFree(D->d_hoff); hipFree(D->d_stage); hipFree(D->d_bhdr); hipFree(D->d_btab); hipFree(D->d_long); hipFree(D->d_pts); hipFree(D->d_clusters);
-  hipFree(D->d_work); hipFree(D->d_work2); hipFree(D->d_workctl); hipFree(D->d_keys_scr); hipFree(D->d_quads);
-  for (auto& c : D->cls) { hipFree(c.d_lf); hipFree(c.d_errs); }
-  hipFree(D->d_fqprof);
-  hipFree(D->d_cands); hipFree(D->d_dets); hipFree(D->d_order); hipFree(D->d_frames);   // (d_counters lives behind d_workctl)
-  for (int i = 0; i < AT_MAX_FAMILIES; i++) hipFree(D->d_codes[i]);
+  for (DevAlloc* b : D->owned) dev_free(D, *b);   // (d_counters and d_ptprof point into d_workctl's and d_fqprof's allocations)
   if (D->h_frames) hipHostFree(D->h_frames);
   if (D->h_counters) hipHostFree(D->h_counters);
   if (D->h_out) hipHostFree(D->h_out);
@@ -473,15 +490,10 @@ static int alloc_hash_buffers(amdAprilTagsDetector_st* D) {
   DetParams& P = D->P;
   const size_t B = D->cfg.max_batch;
   { uint32_t lg = 0; while ((1u << lg) < P.hcap) lg++; P.hshift = 64 - lg; }
-  void** bufs[3] = {(void**)&D->d_hkeys, (void**)&D->d_hcnt, (void**)&D->d_hoff};
-  const size_t bytes[3] = {B * (size_t)P.hcap * 8, B * (size_t)P.hcap * 4, B * (size_t)P.hcap * 4};
-  for (int i = 0; i < 3; i++)
-    if (*bufs[i]) { hipFree(*bufs[i]); *bufs[i] = nullptr; D->device_bytes -= D->hash_buffer_bytes[i]; D->hash_buffer_bytes[i] = 0; }
-  for (int i = 0; i < 3; i++) {
-    if (hipMalloc(bufs[i], bytes[i]) != hipSuccess) return AMDAT_OUT_OF_MEMORY;
-    D->hash_buffer_bytes[i] = bytes[i];
-    D->device_bytes += bytes[i];
-  }
+  dev_free(D, D->d_hkeys); dev_free(D, D->d_hcnt); dev_free(D, D->d_hoff);
+  if (!dev_alloc(D, D->d_hkeys, B * (size_t)P.hcap * 8) || !dev_alloc(D, D->d_hcnt, B * (size_t)P.hcap * 4) ||
+      !dev_alloc(D, D->d_hoff, B * (size_t)P.hcap * 4))
+    return AMDAT_OUT_OF_MEMORY;
   return clear_hash_tables(D);
 }
 
@@ -508,27 +520,21 @@ static int alloc_point_buffers(amdAprilTagsDetector_st* D) {
   D->work_layout_small.lo[FQ_C0] = 23;
   // Long staging records (kernels_cluster.h) only occur where a 64 x 16 tile has more than 2048 emissions -- above two per pixel --
   // or more than 255 component pairs; an eighth of the point capacity is room for them on ordinary content.  An overflow reports
-  // like a point overflow (0x1); the host tells the two apart by the counters and grows the list by itself -- a quarter, half, all
-  // of the point capacity (end_batch): two-level noise near the percolation threshold puts more than a quarter of its points there
-  // (a fuzz case of round 6: such a frame used to keep its overflow flag at the largest point capacity).  Tools builds that shrink
-  // the tile's list start with the whole capacity.
+  // like a point overflow (AMDAT_FLAG_POINTS_OVERFLOW); the host tells the two apart by the counters and grows the list by itself
+  // -- a quarter, half, all of the point capacity (plan_growth, growth.h): two-level noise near the percolation threshold puts more
+  // than a quarter of its points there (a fuzz case of round 6: such a frame used to keep its overflow flag at the largest point
+  // capacity).  Tools builds that shrink the tile's list start with the whole capacity.
 #ifndef AMDAT_LCAP_DIV
 #define AMDAT_LCAP_DIV 8
 #endif
   if (D->lcap_div == 0) D->lcap_div = AMDAT_LCAP_DIV;
-  P.lcap = P.pcap / D->lcap_div > 4096u ? P.pcap / D->lcap_div : 4096u;
-  void** bufs[5] = {(void**)&D->d_stage, (void**)&D->d_long, (void**)&D->d_pts, (void**)&D->d_work, (void**)&D->d_work2};
+  P.lcap = long_capacity(P.pcap, D->lcap_div);
+  DevAlloc* bufs[5] = {&D->d_stage, &D->d_long, &D->d_pts, &D->d_work, &D->d_work2};
   const size_t bytes[5] = {B * (size_t)P.pcap * 4, B * (size_t)P.lcap * 16, B * (size_t)P.pcap * 4, (size_t)off * 4,
                            ((size_t)off - D->work_layout.off[D->prefilter_class]) * 4};
-  for (int i = 0; i < 5; i++) {
-    if (*bufs[i]) { hipFree(*bufs[i]); *bufs[i] = nullptr; D->device_bytes -= D->point_buffer_bytes[i]; D->point_buffer_bytes[i] = 0; }
-  }
-  for (int i = 0; i < 5; i++) {
-    const size_t nb = bytes[i] ? bytes[i] : 16;
-    if (hipMalloc(bufs[i], nb) != hipSuccess) return AMDAT_OUT_OF_MEMORY;
-    D->point_buffer_bytes[i] = nb;
-    D->device_bytes += nb;
-  }
+  for (DevAlloc* b : bufs) dev_free(D, *b);
+  for (int i = 0; i < 5; i++)
+    if (!dev_alloc(D, *bufs[i], bytes[i])) return AMDAT_OUT_OF_MEMORY;
   return AMDAT_SUCCESS;
 }
 
@@ -626,22 +632,22 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
   // Default: 1 per pixel, and the handle GROWS the point buffers (up to the hard 2 per pixel) and repeats the submission
   // when a frame reports AMDAT_FLAG_POINTS_OVERFLOW -- results never depend on the capacity, memory follows the content
   // (15 GB instead of 27 GB for the 256-frame 1080p handle).  An explicit max_points is taken as given and never grown.
-  D->grow_points = cfg.max_points == 0;
-  D->pcap_hard = 2u * npx;
+  D->grow.points = cfg.max_points == 0;
+  D->grow.pcap_hard = 2u * npx;
   P.pcap = cfg.max_points ? cfg.max_points : npx;
   // Component-pair table: one slot per N/8 pixels is what no content overflowed; a sigma-2 1080p frame has ~4 000 pairs, so
   // the table starts at N/32 slots (1 MB instead of 4 MB per frame to clear, probe and scan) and, like the point buffers,
   // doubles when a frame reports AMDAT_FLAG_HASH_OVERFLOW or fills beyond a quarter (an explicit hash_slots is never grown).
-  D->grow_hash = cfg.hash_slots == 0;
-  D->hcap_hard = cfg.hash_slots ? next_pow2(cfg.hash_slots) : next_pow2(npx / 8 > 4096 ? npx / 8 : 4096);
-  if (D->hcap_hard < 256) D->hcap_hard = 256;
-  P.hcap = cfg.hash_slots ? D->hcap_hard : next_pow2(npx / 32 > 4096 ? npx / 32 : 4096);
-  if (P.hcap > D->hcap_hard) P.hcap = D->hcap_hard;
+  D->grow.hash = cfg.hash_slots == 0;
+  D->grow.hcap_hard = cfg.hash_slots ? next_pow2(cfg.hash_slots) : next_pow2(npx / 8 > 4096 ? npx / 8 : 4096);
+  if (D->grow.hcap_hard < 256) D->grow.hcap_hard = 256;
+  P.hcap = cfg.hash_slots ? D->grow.hcap_hard : next_pow2(npx / 32 > 4096 ? npx / 32 : 4096);
+  if (P.hcap > D->grow.hcap_hard) P.hcap = D->grow.hcap_hard;
   // A work item of the quad fit is one word: (frame << wshift) | cluster index.  The frame takes the bits the handle's frame count
   // needs, the index the rest (at most 24): 256 frames per submission leave room for 2^24 clusters per frame, 65 536 frames for
   // 65 536.  A frame has at most one cluster per used slot of the pair table, so min(2^wshift, hcap_hard) bounds the list; it starts
   // at 65 536 (a sigma-2 1080p frame has 4 000 clusters) and, like the point buffers, GROWS when a frame reports
-  // AMDAT_FLAG_CLUSTERS_OVERFLOW -- an eight-megapixel checkerboard of six-pixel cells has 116 000 (end_batch).  An explicit
+  // AMDAT_FLAG_CLUSTERS_OVERFLOW -- an eight-megapixel checkerboard of six-pixel cells has 116 000 (plan_growth).  An explicit
   // max_clusters is taken as given (clamped to the bound) and never grown.
   {
     uint32_t fbits = 0;
@@ -652,12 +658,12 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
 #ifndef AMDAT_CCAP0
 #define AMDAT_CCAP0 65536u   // (tools builds start lower, so that ordinary content exercises the growth)
 #endif
-  D->ccap_hard = D->hcap_hard < (1u << P.wshift) ? D->hcap_hard : (1u << P.wshift);
-  D->grow_clusters = cfg.max_clusters == 0;
-  P.ccap = cfg.max_clusters ? cfg.max_clusters : (D->ccap_hard < AMDAT_CCAP0 ? D->ccap_hard : AMDAT_CCAP0);
-  if (P.ccap > D->ccap_hard) P.ccap = D->ccap_hard;
+  D->grow.ccap_hard = D->grow.hcap_hard < (1u << P.wshift) ? D->grow.hcap_hard : (1u << P.wshift);
+  D->grow.clusters = cfg.max_clusters == 0;
+  P.ccap = cfg.max_clusters ? cfg.max_clusters : (D->grow.ccap_hard < AMDAT_CCAP0 ? D->grow.ccap_hard : AMDAT_CCAP0);
+  if (P.ccap > D->grow.ccap_hard) P.ccap = D->grow.ccap_hard;
   P.qcap = cfg.max_quads ? cfg.max_quads : (P.ccap < 16384 ? P.ccap : 16384);
-  D->grow_quads = cfg.max_quads == 0;   // (a two-megapixel checkerboard of two-pixel cells has 29 000 quads: the list doubles and the
+  D->grow.quads = cfg.max_quads == 0;   // (a two-megapixel checkerboard of two-pixel cells has 29 000 quads: the list doubles and the
                                         // submission is repeated, end_batch; an explicit max_quads reports AMDAT_FLAG_QUADS_OVERFLOW)
   P.dcap = cfg.max_detections ? cfg.max_detections : 1024;
   if (P.dcap > 65535) P.dcap = 65535;
@@ -722,29 +728,24 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
   }
 
   bool ok = true;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (!bytes) bytes = 16;
-    if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false;
-    if (ok) D->device_bytes += bytes;
-  };
-  if (P.decimate > 1) alloc((void**)&D->d_gray, B * (size_t)H * P.WS);
-  alloc((void**)&D->d_thr, B * (size_t)H * P.WS);
-  if (P.tile != 4) { alloc((void**)&D->d_tmin, B * (size_t)P.tw * P.th); alloc((void**)&D->d_tmax, B * (size_t)P.tw * P.th); }
-  alloc((void**)&D->d_label, B * (size_t)npx * 4);
-  alloc((void**)&D->d_csize, B * (size_t)npx * 4);
+  auto alloc = [&](DevAlloc& b, size_t bytes) { if (ok) ok = dev_alloc(D, b, bytes); };
+  if (P.decimate > 1) alloc(D->d_gray, B * (size_t)H * P.WS);
+  alloc(D->d_thr, B * (size_t)H * P.WS);
+  if (P.tile != 4) { alloc(D->d_tmin, B * (size_t)P.tw * P.th); alloc(D->d_tmax, B * (size_t)P.tw * P.th); }
+  alloc(D->d_label, B * (size_t)npx * 4);
+  alloc(D->d_csize, B * (size_t)npx * 4);
   // tile-local roots that go to the list touch their 64 x 64 tile's perimeter, and components are disjoint: at most
   // 252 (perimeter pixels) per tile
   P.rcap = (uint32_t)(((W + CC_T - 1) / CC_T) * ((H + CC_T - 1) / CC_T)) * (4u * CC_T - 4u);
-  alloc((void**)&D->d_roots, B * (size_t)P.rcap * 4);
-  alloc((void**)&D->d_perim, B * (size_t)cc_perim_layout(W, H).words * 4);
+  alloc(D->d_roots, B * (size_t)P.rcap * 4);
+  alloc(D->d_perim, B * (size_t)cc_perim_layout(W, H).words * 4);
   if (ok) ok = alloc_hash_buffers(D) == AMDAT_SUCCESS;   // (before the point buffers: it decides the staging format)
   {   // per block (64 x 16 tile) of k_points: header and component-pair table for k_scatter
     const size_t tiles = (size_t)((W + PT_TW - 1) / PT_TW) * (size_t)((H + PT_TH - 1) / PT_TH);
-    alloc((void**)&D->d_bhdr, B * tiles * sizeof(uint2));
-    alloc((void**)&D->d_btab, B * tiles * PT_TB * sizeof(uint2));
+    alloc(D->d_bhdr, B * tiles * sizeof(uint2));
+    alloc(D->d_btab, B * tiles * PT_TB * sizeof(uint2));
   }
-  alloc((void**)&D->d_clusters, B * (size_t)P.ccap * sizeof(ClusterRec));
-  D->clusters_bytes = B * (size_t)P.ccap * sizeof(ClusterRec);
+  alloc(D->d_clusters, B * (size_t)P.ccap * sizeof(ClusterRec));
   if (ok) { const int rc = alloc_point_buffers(D); if (rc == AMDAT_BATCH_TOO_LARGE) { free_all(D); delete D; return rc; } ok = rc == AMDAT_SUCCESS; }
   for (int k = 0; k < FQ_NCLS; k++) {
     FqClass& c = D->cls[k];
@@ -752,31 +753,29 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
     // bound for "can this class ever see a cluster" is 23, whatever the k_fit_small classes below it would take on the other set)
     const int lo_eff = k == FQ_C0 ? 23 : c.lo;
     if (P.max_cluster_points <= lo_eff || c.small_k == 2 || c.hi <= c.lo) continue;   // (k_fit_small<2> keeps its moments in LDS)
-    alloc((void**)&c.d_lf, (size_t)c.grid * c.slot_cap * 48);
+    alloc(c.d_lf, (size_t)c.grid * c.slot_cap * 48);
     // smoothed errors stay in registers up to FQ_SMOOTH_REGS_OF(threads) points per thread; larger clusters need a second array
-    if (!c.small_k && (c.slot_cap > FQ_SMOOTH_REGS_OF(c.nt) * c.nt || c.slot_cap > c.sort_cap)) alloc((void**)&c.d_errs, (size_t)c.grid * c.slot_cap * 16);
+    if (!c.small_k && (c.slot_cap > FQ_SMOOTH_REGS_OF(c.nt) * c.nt || c.slot_cap > c.sort_cap)) alloc(c.d_errs, (size_t)c.grid * c.slot_cap * 16);
   }
   if (D->cls[FQ_NCLS - 1].slot_cap > D->cls[FQ_NCLS - 1].sort_cap) {   // clusters beyond the LDS key array exist
     const FqClass& c = D->cls[FQ_NCLS - 1];
-    alloc((void**)&D->d_keys_scr, (size_t)c.grid * c.slot_cap * 8);
+    alloc(D->d_keys_scr, (size_t)c.grid * c.slot_cap * 8);
   }
-  alloc((void**)&D->d_quads, B * (size_t)P.qcap * sizeof(QuadRec));
-  D->quads_bytes = B * (size_t)P.qcap * sizeof(QuadRec);
+  alloc(D->d_quads, B * (size_t)P.qcap * sizeof(QuadRec));
   // every kept cluster can become a candidate (ccap); the list starts at the quad capacity and grows when a frame fills it
   P.cand_cap = P.qcap;
-  alloc((void**)&D->d_cands, B * (size_t)P.cand_cap * sizeof(FitCand));
-  D->cands_bytes = B * (size_t)P.cand_cap * sizeof(FitCand);
-  alloc((void**)&D->d_dets, B * (size_t)P.dcap * sizeof(DetRec));
-  alloc((void**)&D->d_order, B * (size_t)P.dcap * 2);
+  alloc(D->d_cands, B * (size_t)P.cand_cap * sizeof(FitCand));
+  alloc(D->d_dets, B * (size_t)P.dcap * sizeof(DetRec));
+  alloc(D->d_order, B * (size_t)P.dcap * 2);
   // work-list control words and frame counters share one allocation, cleared by ONE fill per submission
-  alloc((void**)&D->d_workctl, 32 * 4 + B * sizeof(FrameCounters));
+  alloc(D->d_workctl, 32 * 4 + B * sizeof(FrameCounters));
   if (ok) D->d_counters = reinterpret_cast<FrameCounters*>(D->d_workctl + 32);
-  alloc((void**)&D->d_frames, B * sizeof(FrameDesc));
-  alloc((void**)&D->d_fqprof, (64 + 8) * 8);
+  alloc(D->d_frames, B * sizeof(FrameDesc));
+  alloc(D->d_fqprof, (64 + 8) * 8);
   D->d_ptprof = D->d_fqprof + 64;   // k_points' phase counters follow the quad fit's
   for (int i = 0; ok && i < P.nfam; i++) {
     const std::vector<uint64_t>& codes = fams[i].codes;
-    alloc((void**)&D->d_codes[i], codes.size() * 8);
+    alloc(D->d_codes[i], codes.size() * 8);
     if (ok && (hipMemcpyAsync(D->d_codes[i], codes.data(), codes.size() * 8, hipMemcpyHostToDevice, D->own_stream) != hipSuccess ||
                hipStreamSynchronize(D->own_stream) != hipSuccess)) ok = false;   // (`fams` is pageable: waited for before it goes)
     P.fam[i].codes = D->d_codes[i];
@@ -793,15 +792,11 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
   // Side streams.  The persistent grids of the fit's classes each hold the whole chip's wave slots, so which class's workgroups
   // are placed first decides who runs beside whom.  A handle sized for throughput (more than eight frames per submission) gets
   // PRIORITISED side streams -- greatest, default, least: the class with the longest chains goes on the first and is placed
-  // first, the one-wave and small-cluster kernels fill what it leaves (AMDAT_AUX_PRIO: measured below) -- and never captures
-  // launch graphs: replaying a graph whose branches were captured on prioritised streams costs 0.25 ms per launch on this runtime
-  // (one frame: 0.39 -> 0.65 ms).  A handle of up to eight frames keeps plain side streams and graph replay.  (Both sets on one
-  // handle -- seven streams -- slowed every stage: 17.6 -> 18.1 ms per 256 frames; the runtime multiplexes its streams onto a
-  // few hardware queues.)
-#ifndef AMDAT_AUX_PRIO
-#define AMDAT_AUX_PRIO 1
-#endif
-  D->aux_prioritised = AMDAT_AUX_PRIO && cfg.max_batch > 8 && !cfg.no_stream_priorities;
+  // first, the one-wave and small-cluster kernels fill what it leaves -- and never captures launch graphs: replaying a graph whose
+  // branches were captured on prioritised streams costs 0.25 ms per launch on this runtime (one frame: 0.39 -> 0.65 ms).  A handle
+  // of up to eight frames keeps plain side streams and graph replay.  (Both sets on one handle -- seven streams -- slowed every
+  // stage: 17.6 -> 18.1 ms per 256 frames; the runtime multiplexes its streams onto a few hardware queues.)
+  D->aux_prioritised = cfg.max_batch > 8 && !cfg.no_stream_priorities;
   {
     int lo = 0, hi = 0;   // (numerically hi <= lo: hi is the greatest priority)
     if (D->aux_prioritised && hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { D->aux_prioritised = false; (void)hipGetLastError(); }
@@ -817,21 +812,11 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
     // hardware queues.  The library does not try to steer this: the first row is what a process with one throughput-sized handle
     // gets, a node's process -- one small handle -- never meets a prioritised stream, and a process that mixes both creates the
     // small handles first or sets no_stream_priorities: include/apriltag_amd.h, INTEGRATION.md.)
-    auto prime_plain_queues = [&]() {
-      hipStream_t plain[4] = {};
-      for (auto& q : plain) if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) { q = nullptr; (void)hipGetLastError(); }
-      for (auto& q : plain) if (q) hipStreamDestroy(q);
-    };
-#ifndef AMDAT_PRIME_PLAIN_QUEUES
-#define AMDAT_PRIME_PLAIN_QUEUES 0   // 0: never, 1: before the prioritised streams are created, 2: after (measurement builds)
-#endif
-    if (D->aux_prioritised && AMDAT_PRIME_PLAIN_QUEUES == 1) prime_plain_queues();
     for (int k = 0; k < FQ_NAUX; k++) {
       const int pr = k == 0 ? hi : (k == 1 ? (lo + hi) / 2 : lo);
       if (ok && (D->aux_prioritised ? hipStreamCreateWithPriority(&D->aux_stream[k], hipStreamNonBlocking, pr)
                                     : hipStreamCreateWithFlags(&D->aux_stream[k], hipStreamNonBlocking)) != hipSuccess) ok = false;
     }
-    if (D->aux_prioritised && AMDAT_PRIME_PLAIN_QUEUES == 2) prime_plain_queues();
     if (D->aux_prioritised) D->graph_max_frames = 0;
   }
   if (ok && hipEventCreateWithFlags(&D->ev_fork, hipEventDisableTiming) != hipSuccess) ok = false;
@@ -964,17 +949,14 @@ static int ensure_colour_plane(amdAprilTagsDetector_st* D, uint32_t fmt) {
   if (colour_fused(D, fmt)) {
     if (D->d_gray) return AMDAT_SUCCESS;
     const size_t bytes = B * (size_t)D->P.H * D->P.WS;
-    if (hipMalloc((void**)&D->d_gray, bytes) != hipSuccess) { D->d_gray = nullptr; return AMDAT_OUT_OF_MEMORY; }
-    D->device_bytes += bytes;
+    if (!dev_alloc(D, D->d_gray, bytes)) return AMDAT_OUT_OF_MEMORY;
     if (hipMemsetAsync(D->d_gray, 0, bytes, D->own_stream) != hipSuccess || hipStreamSynchronize(D->own_stream) != hipSuccess) return AMDAT_HIP_ERROR;
     return AMDAT_SUCCESS;
   }
   if (D->d_conv) return AMDAT_SUCCESS;
   D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
   const size_t bytes = B * D->conv_pitch * D->cfg.height;
-  if (hipMalloc((void**)&D->d_conv, bytes) != hipSuccess) { D->d_conv = nullptr; return AMDAT_OUT_OF_MEMORY; }
-  D->device_bytes += bytes;
-  return AMDAT_SUCCESS;
+  return dev_alloc(D, D->d_conv, bytes) ? AMDAT_SUCCESS : AMDAT_OUT_OF_MEMORY;
 }
 
 static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images,
@@ -1347,7 +1329,7 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
   // command and a fill command ahead of the first kernel cost a one-frame call about 15 us, this launch 4
   static_assert(sizeof(FrameDesc) % 4 == 0 && sizeof(FrameDesc) <= 256 && sizeof(FrameCounters) % 4 == 0 && sizeof(FrameCounters) <= 256, "k_prologue: one word per thread");
   hipLaunchKernelGGL(k_prologue, dim3(n), dim3(64), 0, s, reinterpret_cast<const uint32_t*>(D->h_frames),
-                     reinterpret_cast<uint32_t*>(D->d_frames), D->d_workctl, reinterpret_cast<uint32_t*>(D->d_counters),
+                     static_cast<uint32_t*>(D->d_frames.p), D->d_workctl, reinterpret_cast<uint32_t*>(D->d_counters),
                      (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4));
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   mark();
@@ -1369,35 +1351,24 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
 // runtime and completes on ROCm 7.2's.  With the destroy taken out of the way -- retired graphs die with the handle, after its
 // device-wide wait and with no capture behind them -- re-capturing on regrown buffers is clean (tools/stress_regrow.py with
 // replay kept: 15 of 15 runs of 150 handles; with hipGraphExecDestroy at the regrowth: 11 of 12 runs die), so a regrown handle
-// keeps graph replay.  The list is bounded: beyond AMDAT_MAX_RETIRED_GRAPHS the handle stops capturing new graphs (plain
-// enqueues for the submission shapes it has no graph for; it says so once on stderr and through amdAprilTagsDebugGraphReplay).
+// keeps graph replay: the next submission of each shape is captured again on the new buffers.  The list is bounded: beyond
+// AMDAT_MAX_RETIRED_GRAPHS the handle stops capturing new graphs (plain enqueues for the submission shapes it has no graph for;
+// it says so once on stderr and through amdAprilTagsDebugGraphReplay).
 #ifndef AMDAT_MAX_RETIRED_GRAPHS
 #define AMDAT_MAX_RETIRED_GRAPHS 24
 #endif
 static void retire_graph(amdAprilTagsDetector_st* D, amdAprilTagsDetector_st::GraphEntry& g) {
   if (!g.exec) return;
-#ifdef AMDAT_GRAPH_DESTROY_NOW   // (tools build of the crash hunt: what the library did until round 4)
-  hipGraphExecDestroy(g.exec);
-#else
   D->retired_graphs.push_back(g.exec);
   if (D->retired_graphs.size() > AMDAT_MAX_RETIRED_GRAPHS && D->graph_max_frames) {
     D->graph_max_frames = 0;   // (the live cache entries keep replaying; nothing new is captured)
     fprintf(stderr, "[apriltag_amd] handle %p: %zu retired launch graphs -- no new graphs are captured from here on (plain enqueues "
                     "for submission shapes without one)\n", (void*)D, D->retired_graphs.size());
   }
-#endif
   g.exec = nullptr;
 }
 static void drop_graphs(amdAprilTagsDetector_st* D) {
   for (auto& g : D->graphs) retire_graph(D, g);
-}
-// A capacity grew: the captured launches carry the old pointers and capacities.  The next submission of each shape is captured
-// again on the new buffers (rounds 4 and 5 gave replay up for good here, at ~0.1 ms per later one-frame call; see retire_graph).
-static void drop_graphs_for_regrowth(amdAprilTagsDetector_st* D) {
-  drop_graphs(D);
-#ifdef AMDAT_REGROW_DROPS_REPLAY   // (tools build: round 5's behaviour)
-  D->graph_max_frames = 0;
-#endif
 }
 
 // After a capture that did not end in a graph: clear the error state and make sure no stream of the handle is left inside the
@@ -1535,6 +1506,55 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
 }
 
 
+// The capacities the growth policy sees (growth.h) and takes back.  P.lcap follows from pcap and lcap_div (alloc_point_buffers).
+static GrowCaps caps_of(const amdAprilTagsDetector_st* D) {
+  return {D->P.pcap, D->P.lcap, D->P.hcap, D->P.ccap, D->P.qcap, D->P.cand_cap, D->lcap_div};
+}
+static void set_caps(amdAprilTagsDetector_st* D, const GrowCaps& c) {
+  DetParams& P = D->P;
+  P.pcap = c.pcap; P.lcap = c.lcap; P.hcap = c.hcap; P.ccap = c.ccap; P.qcap = c.qcap; P.cand_cap = c.cand_cap; D->lcap_div = c.lcap_div;
+}
+
+// Reallocates what a growth plan names and takes its capacities; false if an allocation failed.  The cluster, quad and candidate
+// lists get their new buffer before the old one goes; the point buffers and the pair table are freed first (alloc_*_buffers), so a
+// failure there reallocates them at the old capacities -- and if even that fails the handle is unusable.  Graphs are retired only
+// when a buffer changed: their launches carry the old pointers and capacities.
+static bool regrow(amdAprilTagsDetector_st* D, const GrowPlan& g) {
+  const size_t B = D->cfg.max_batch;
+  const GrowCaps before = caps_of(D);
+  bool ok = true;
+  switch (g.family) {
+    case GROW_QUADS: ok = dev_regrow(D, D->d_quads, B * g.caps.qcap * sizeof(QuadRec)); break;
+    case GROW_CANDS: ok = dev_regrow(D, D->d_cands, B * g.caps.cand_cap * sizeof(FitCand)); break;
+    case GROW_CLUSTERS: {   // the quad fit's work lists are sized from ccap: the point buffers follow
+      DevBuf<ClusterRec> old = D->d_clusters;
+      D->d_clusters = {};
+      if (!dev_alloc(D, D->d_clusters, B * g.caps.ccap * sizeof(ClusterRec))) { D->d_clusters = old; ok = false; break; }
+      drop_graphs(D);
+      set_caps(D, g.caps);
+      ok = alloc_point_buffers(D) == AMDAT_SUCCESS;
+      if (ok) { dev_free(D, old); break; }
+      dev_free(D, D->d_clusters);   // (the grown list goes before the point buffers are reallocated at the old capacity)
+      D->d_clusters = old;
+      set_caps(D, before);
+      if (alloc_point_buffers(D) != AMDAT_SUCCESS) D->unusable = true;
+      break;
+    }
+    default:   // GROW_POINTS, GROW_HASH (the point buffers also when only the staging format changes)
+      drop_graphs(D);
+      set_caps(D, g.caps);
+      ok = alloc_hash_buffers(D) == AMDAT_SUCCESS && alloc_point_buffers(D) == AMDAT_SUCCESS;
+      if (!ok) {
+        set_caps(D, before);
+        if (alloc_hash_buffers(D) != AMDAT_SUCCESS || alloc_point_buffers(D) != AMDAT_SUCCESS) D->unusable = true;
+      }
+  }
+  if (!ok) return false;
+  drop_graphs(D);   // (a no-op where the case above dropped them)
+  set_caps(D, g.caps);
+  return true;
+}
+
 // One batched submission; results land in h_out / h_counters with `ostride` records per frame.
 // begin_batch fills the descriptor block and enqueues the submission; end_batch waits for it, and where a frame overflowed a
 // capacity the handle may grow, grows it and runs the submission again (the descriptors are still in the pinned block).
@@ -1551,16 +1571,10 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   if (ostride > D->P.dcap) ostride = D->P.dcap;
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
     D->pending_hash_grow = false;
-    if (D->grow_hash && D->P.hcap < D->hcap_hard) {
-      drop_graphs_for_regrowth(D);
-      const uint32_t before = D->P.hcap;
-      D->P.hcap = D->P.hcap * 2 > D->hcap_hard ? D->hcap_hard : D->P.hcap * 2;
-      if (alloc_hash_buffers(D) != AMDAT_SUCCESS || alloc_point_buffers(D) != AMDAT_SUCCESS) {
-        D->P.hcap = before; D->grow_hash = false;
-        if (alloc_hash_buffers(D) != AMDAT_SUCCESS || alloc_point_buffers(D) != AMDAT_SUCCESS) { D->unusable = true; return AMDAT_OUT_OF_MEMORY; }
-      } else {
-        D->grown++;
-      }
+    const GrowPlan g = plan_pending_hash(caps_of(D), D->grow);
+    if (g.family != GROW_NONE && !regrow(D, g)) {
+      if (D->unusable) return AMDAT_OUT_OF_MEMORY;
+      give_up(D->grow, g.family);
     }
   }
   if (D->tables_dirty) { const int crc = clear_hash_tables(D); if (crc) return crc; }
@@ -1582,129 +1596,11 @@ static int end_batch(amdAprilTagsDetector_st* D) {
     const int rc = finish_once(D, s);
     if (rc) return rc;
     D->tables_dirty = false;   // ran to its end: k_cluster_select left the pair table empty
-    // A frame whose boundary points did not fit yields no clusters at all (flag 0x1), one whose component pairs did not fit
-    // loses clusters (0x2).  Unless the host fixed the capacities, the buffers grow -- doubling, up to what no content
-    // exceeds -- and the submission runs again; a pair table filled beyond a quarter grows for the next submission.
-    bool pts_over = false, hash_over = false, hash_crowded = false, long_over = false;
-    uint32_t nlong_max = 0;
-    for (uint32_t f = 0; f < n; f++) {
-      // (0x1 covers both the staging words and the long records: the counters say which list it was -- both count every attempt)
-      if (D->h_counters[f].flags & 0x1u) {
-        if (D->h_counters[f].nlong > D->P.lcap) { long_over = true; if (D->h_counters[f].nlong > nlong_max) nlong_max = D->h_counters[f].nlong; }
-        if (D->h_counters[f].npoints_raw > D->P.pcap || D->h_counters[f].nlong <= D->P.lcap) pts_over = true;
-      }
-      hash_over |= (D->h_counters[f].flags & 0x2u) != 0;
-      hash_crowded |= D->h_counters[f].nclusters > D->P.hcap / 4;
-    }
-    bool cands_over = false;
-    for (uint32_t f = 0; f < n; f++) cands_over |= (D->h_counters[f].flags & AT_FLAG_CANDS) != 0;
-    bool again = false;
-    {   // the cluster list of a handle without an explicit max_clusters follows the content: to the next power of two that holds the
-        // fullest frame (the counter counts every kept cluster, listed or not); the work lists of the quad fit follow it
-      uint32_t ncl_max = 0;
-      for (uint32_t f = 0; f < n; f++)
-        if ((D->h_counters[f].flags & 0x4u) && D->h_counters[f].nclusters > D->P.ccap && D->h_counters[f].nclusters > ncl_max) ncl_max = D->h_counters[f].nclusters;
-      if (ncl_max && D->grow_clusters && D->P.ccap < D->ccap_hard) {
-        uint32_t ncap = D->P.ccap;
-        while (ncap < ncl_max && ncap < D->ccap_hard) ncap *= 2;
-        if (ncap > D->ccap_hard) ncap = D->ccap_hard;
-        ClusterRec* nb = nullptr;
-        const size_t nbytes = (size_t)D->cfg.max_batch * ncap * sizeof(ClusterRec);
-        const uint32_t before = D->P.ccap;
-        if (hipMalloc((void**)&nb, nbytes) == hipSuccess) {
-          drop_graphs_for_regrowth(D);
-          D->P.ccap = ncap;
-          if (alloc_point_buffers(D) == AMDAT_SUCCESS) {
-            hipFree(D->d_clusters);
-            D->d_clusters = nb;
-            D->device_bytes += nbytes - D->clusters_bytes;
-            D->clusters_bytes = nbytes;
-            D->grown++;
-            again = true;
-          } else {   // not enough memory for the longer work lists: the old capacities stay and the overflow is reported
-            (void)hipGetLastError();
-            hipFree(nb);
-            D->P.ccap = before; D->grow_clusters = false;
-            if (alloc_point_buffers(D) != AMDAT_SUCCESS) { D->unusable = true; return AMDAT_OUT_OF_MEMORY; }
-          }
-        } else {
-          (void)hipGetLastError();
-          D->grow_clusters = false;
-        }
-      }
-    }
-    if (!again) {   // the quad list of a handle without an explicit max_quads follows the content like the candidate list
-      bool quads_over = false;
-      for (uint32_t f = 0; f < n; f++) quads_over |= (D->h_counters[f].flags & 0x8u) != 0 && D->h_counters[f].nquads > D->P.qcap;
-      if (quads_over && D->grow_quads && D->P.qcap < D->P.ccap) {
-        const uint64_t want = (uint64_t)D->P.qcap * 2;
-        const uint32_t ncap = want > D->P.ccap ? D->P.ccap : (uint32_t)want;
-        QuadRec* nb = nullptr;
-        const size_t nbytes = (size_t)D->cfg.max_batch * ncap * sizeof(QuadRec);
-        if (hipMalloc((void**)&nb, nbytes) == hipSuccess) {
-          drop_graphs_for_regrowth(D);
-          hipFree(D->d_quads);
-          D->d_quads = nb;
-          D->device_bytes += nbytes - D->quads_bytes;
-          D->quads_bytes = nbytes;
-          D->P.qcap = ncap;
-          D->grown++;
-          again = true;
-        } else {
-          (void)hipGetLastError();
-          D->grow_quads = false;   // (not enough memory: the overflow is reported from here on)
-        }
-      }
-    }
-    if (!again && cands_over) {
-      if (D->P.cand_cap < D->P.ccap) {   // grow the candidate list and repeat
-        drop_graphs_for_regrowth(D);
-        const uint64_t want = (uint64_t)D->P.cand_cap * 2;
-        const uint32_t ncap = want > D->P.ccap ? D->P.ccap : (uint32_t)want;
-        FitCand* nb = nullptr;
-        const size_t nbytes = (size_t)D->cfg.max_batch * ncap * sizeof(FitCand);
-        if (hipMalloc((void**)&nb, nbytes) == hipSuccess) {
-          hipFree(D->d_cands);
-          D->d_cands = nb;
-          D->device_bytes += nbytes - D->cands_bytes;
-          D->cands_bytes = nbytes;
-          D->P.cand_cap = ncap;
-          D->grown++;
-          again = true;
-        }
-      }
-      // cannot grow: report it as what it is for the caller, a quad-list overflow
-      if (!again)
-        for (uint32_t f = 0; f < n; f++)
-          if (D->h_counters[f].flags & AT_FLAG_CANDS) D->h_counters[f].flags = (D->h_counters[f].flags & ~AT_FLAG_CANDS) | 0x8u;
-    }
-    if (!again) {
-      const bool can_pts = D->grow_points && D->P.pcap < D->pcap_hard;
-      const bool can_long = D->grow_points && D->lcap_div > 1;
-      const bool can_hash = D->grow_hash && D->P.hcap < D->hcap_hard;
-      const bool redo = (pts_over && can_pts) || (long_over && can_long) || (hash_over && can_hash);
-      if (!redo) {   // (a crowded table grows before the next submission: this one's buffers may still be inspected)
-        if (hash_crowded && can_hash) D->pending_hash_grow = true;
-        return AMDAT_SUCCESS;
-      }
-      drop_graphs_for_regrowth(D);   // captured launches carry the old pointers and capacities
-      const uint32_t pcap_before = D->P.pcap, hcap_before = D->P.hcap, ldiv_before = D->lcap_div;
-      if (pts_over && can_pts) { const uint64_t want = (uint64_t)D->P.pcap * 2; D->P.pcap = want > D->pcap_hard ? D->pcap_hard : (uint32_t)want; }
-      if (long_over && can_long) {   // the smallest share of the (new) point capacity that holds what this submission asked for
-        do D->lcap_div >>= 1; while (D->lcap_div > 1 && D->P.pcap / D->lcap_div < nlong_max);
-      }
-      if (hash_over && can_hash) D->P.hcap = D->P.hcap * 2 > D->hcap_hard ? D->hcap_hard : D->P.hcap * 2;
-      int grc = alloc_hash_buffers(D);
-      if (grc == AMDAT_SUCCESS) grc = alloc_point_buffers(D);   // (also when only the staging format changed)
-      if (grc != AMDAT_SUCCESS) {   // not enough memory to grow: keep reporting the overflow with the old capacities
-        D->P.pcap = pcap_before; D->P.hcap = hcap_before; D->lcap_div = ldiv_before;
-        D->grow_points = false; D->grow_hash = false;
-        if (alloc_hash_buffers(D) != AMDAT_SUCCESS || alloc_point_buffers(D) != AMDAT_SUCCESS) { D->unusable = true; return AMDAT_OUT_OF_MEMORY; }
-        return AMDAT_SUCCESS;
-      }
-      D->grown++;
-    }
-    // run the submission again on the grown buffers
+    // an overflowed capacity that follows the content grows (growth.h) and the submission runs again; an unusable handle stops
+    const GrowPlan g = grow_round(D->h_counters, n, caps_of(D), D->grow, [&](const GrowPlan& p) { return regrow(D, p) || D->unusable; });
+    if (D->unusable) return AMDAT_OUT_OF_MEMORY;
+    if (g.cands_as_quads) report_cands_as_quads(D->h_counters, n);
+    if (g.family == GROW_NONE) { D->pending_hash_grow = g.hash_next; return AMDAT_SUCCESS; }
     if (D->tables_dirty) { const int crc = clear_hash_tables(D); if (crc) return crc; }
     D->tables_dirty = true;
     const int lrc = launch_once(D, n, ostride, s, D->launched_fmt);
