@@ -262,6 +262,18 @@ int amdAprilTagsWaitBatchEx(amdAprilTagsHandle handle, amdAprilTagsDetectionEx_t
  * here next to the per-frame fx, fy, cx, cy of amdAprilTagsDetectBatch.  Only the pose depends on it. */
 int amdAprilTagsSetFrameSkews(amdAprilTagsHandle handle, uint32_t n, const float* skews);
 
+/* quad_sigma of AprilRobotics' detector (apriltag_ros: `blur` / `sigma`): a Gaussian blur (quad_sigma > 0) or sharpen (< 0) of the
+ * working image ahead of the threshold, with upstream's integer taps.  At decimate 1 every stage reads the filtered
+ * image; at decimate > 1 the threshold through the quad fit read the filtered decimated image, edge refinement and decode the unfiltered
+ * frame.  The caller's buffers are never written.  |quad_sigma| < 0.5 is the identity: no filter (the default).  Callable whenever no
+ * submission is in flight; takes effect with the next submission.  AMDAT_INVALID_ARGUMENT: null handle, NaN / inf, a submission in
+ * flight; AMDAT_UNSUPPORTED: |quad_sigma| > 4; AMDAT_OUT_OF_MEMORY: the filtered plane (decimate 1) could not be allocated.  A refused
+ * call leaves the previous setting in force.  A call that changes the filter (its taps, or on / off) retires the launch graphs the handle
+ * has captured for small submissions; after 24 retired graphs in all (AMDAT_MAX_RETIRED_GRAPHS, counting those of capacity growth and
+ * cache evictions) the handle stops capturing new ones and enqueues such submissions plainly, about 0.1 ms more per one-frame call
+ * (amdAprilTagsDebugGraphReplay reports it).  Set it once after create, or rarely. */
+int amdAprilTagsSetQuadSigma(amdAprilTagsHandle handle, float quad_sigma);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

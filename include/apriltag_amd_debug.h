@@ -52,6 +52,11 @@ int amdAprilTagsDebugLateWaits(amdAprilTagsHandle handle);
  * cache entries and of retired graphs (kept until the handle is destroyed, see csrc/detector.hip: retire_graph) through the outputs. */
 int amdAprilTagsDebugGraphReplay(amdAprilTagsHandle handle, uint32_t* live_graphs, uint32_t* retired_graphs);
 
+/* quad_sigma's taps as amdAprilTagsSetQuadSigma computes them (host only, no device): upstream's kernel size through *ksz (1 for the
+ * identity, |quad_sigma| < 0.5) and, when it is above 1, the ksz taps (capacity >= ksz, else AMDAT_INVALID_ARGUMENT).  Same argument
+ * checks as the setter. */
+int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz);
+
 /* ---- stage inspection (parity tests) ------------------------------------------------------ */
 typedef enum {
   AMDAT_DBG_GRAY = 0,      /* u8  w*h working gray image */

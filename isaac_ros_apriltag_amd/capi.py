@@ -67,7 +67,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsGetDeviceBytes", "amdAprilTagsDebugSetSubmissionPath", "amdAprilTagsDebugLastSubmissionPath", "amdAprilTagsDebugLateWaits",
            "amdAprilTagsEncodingFromName", "amdAprilTagsDetectColor", "amdAprilTagsDetectBatchColor", "amdAprilTagsDetectBatchColorEx",
            "amdAprilTagsSubmitBatchColor", "amdAprilTagsThresholdOnlyColor", "amdAprilTagsCopyToDeviceAsync", "amdAprilTagsStreamCreate",
-           "amdAprilTagsStreamDestroy", "amdAprilTagsDebugGraphReplay", "amdAprilTagsConfigLayoutVersion"]
+           "amdAprilTagsStreamDestroy", "amdAprilTagsDebugGraphReplay", "amdAprilTagsConfigLayoutVersion",
+           "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 ENC_CHANNELS = {"mono8": 1, "rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4}
@@ -140,6 +141,8 @@ def lib():
     L.amdAprilTagsDebugLateWaits.argtypes = [H]
     L.amdAprilTagsDebugGraphReplay.argtypes = [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.amdAprilTagsDebugMath.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.amdAprilTagsSetQuadSigma.argtypes = [H, C.c_float]
+    L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int or name in ("amdAprilTagsFamilyFromName", "amdAprilTagsEncodingFromName"):
@@ -199,3 +202,11 @@ def debug_math(op, a, b):
     out = np.empty_like(a)
     _check("amdAprilTagsDebugMath", lib().amdAprilTagsDebugMath(op, a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data))
     return out
+
+
+def quad_sigma_taps(sigma):
+    """amdAprilTagsDebugQuadSigmaTaps: upstream's taps for quad_sigma (an empty list for the identity)."""
+    taps = (C.c_uint8 * 17)()
+    ksz = C.c_uint32()
+    _check("amdAprilTagsDebugQuadSigmaTaps", lib().amdAprilTagsDebugQuadSigmaTaps(float(sigma), taps, 17, C.byref(ksz)))
+    return [int(taps[i]) for i in range(ksz.value)] if ksz.value > 1 else []

@@ -24,6 +24,7 @@
 #include "kernels_cluster.h"
 #include "kernels_decode.h"
 #include "kernels_decode_wave.h"
+#include "kernels_filter.h"
 #include "kernels_frontend.h"
 #include "kernels_quad.h"
 #include "kernels_quad_small.h"
@@ -179,7 +180,8 @@ struct amdAprilTagsDetector_st {
   bool aux_prioritised = false;      // the side streams carry priorities (handles above eight frames per submission; see creation)
   hipEvent_t ev_fork = nullptr, ev_join[FQ_NAUX] = {};
   // device buffers
-  DevBuf<uint8_t> d_gray;             // working-size gray plane: decimated handles, and (allocated on first use) colour submissions at decimate 1
+  DevBuf<uint8_t> d_gray;             // working-size gray plane: decimated handles, and (allocated on first use) colour submissions and
+                                      // the quad_sigma filter at decimate 1
   DevBuf<uint8_t> d_conv;             // full-size mono8 plane of colour submissions that take the conversion launch (decimate > 1, tile_size 8)
   size_t conv_pitch = 0;
   DevBuf<uint8_t> d_thr;
@@ -251,6 +253,10 @@ struct amdAprilTagsDetector_st {
   int last_path = AMDAT_PATH_AUTO;   // the set the last submission ran (amdAprilTagsDebugLastSubmissionPath)
   float stage_ms[AMDAT_NUM_STAGES] = {};
   uint32_t last_n = 0;
+  // quad_sigma (amdAprilTagsSetQuadSigma): the filter runs while qs_ksz > 1; qs.tk are the taps of the k_quad_sigma<qs_kh> instance
+  uint32_t qs_ksz = 1;
+  int qs_kh = 0;
+  QsTaps qs = {};
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -297,6 +303,26 @@ __global__ __launch_bounds__(256) void k_to_mono8_frames(const FrameDesc* __rest
     const uint32_t R = s[k * NCH + RIDX], G = s[k * NCH + 1], B = s[k * NCH + BIDX];
     d[k] = (uint8_t)((4899u * R + 9617u * G + 1868u * B + 8192u) >> 14);
   }
+}
+
+// quad_sigma's taps, computed on the host once per setting: ksz = (int)(4 |sigma|) made odd, h = ksz / 2,
+// dk[i] = exp(-0.5 ((i - h) / s)^2) normalised by their sum in index order, k[i] = (uint8_t)(dk[i] * 255).  ksz <= 1 is the identity.
+static uint32_t quad_sigma_taps(float sigma, uint8_t k[QS_MAX_KSZ]) {
+  const float s = fabsf(sigma);
+  int ksz = (int)(4.0f * s);
+  if ((ksz & 1) == 0) ksz++;
+  if (ksz <= 1) return 1;
+  if (ksz > QS_MAX_KSZ) return 0;
+  const int h = ksz / 2;
+  double dk[QS_MAX_KSZ];
+  double acc = 0;
+  for (int i = 0; i < ksz; i++) {
+    const double x = (i - h) / (double)s;
+    dk[i] = exp(-0.5 * x * x);
+    acc += dk[i];
+  }
+  for (int i = 0; i < ksz; i++) k[i] = (uint8_t)(dk[i] / acc * 255.0);
+  return (uint32_t)ksz;
 }
 
 static inline uint32_t enc_channels(uint32_t fmt) { return fmt == AMDAT_ENC_MONO8 ? 1u : (fmt <= AMDAT_ENC_BGR8 ? 3u : 4u); }
@@ -889,6 +915,7 @@ int amdAprilTagsSetProfiling(amdAprilTagsHandle handle, int enable) {
 }
 
 static void drop_graphs(amdAprilTagsDetector_st* D);   // (defined with the submission code below)
+static int ensure_gray_plane(amdAprilTagsDetector_st* D);
 
 int amdAprilTagsDebugSetSubmissionPath(amdAprilTagsHandle handle, int path) {
   if (!handle || path < AMDAT_PATH_AUTO || path > AMDAT_PATH_THROUGHPUT) return AMDAT_INVALID_ARGUMENT;
@@ -898,6 +925,44 @@ int amdAprilTagsDebugSetSubmissionPath(amdAprilTagsHandle handle, int path) {
   if (!guard.ok) return AMDAT_HIP_ERROR;
   drop_graphs(handle);   // captured under the other path
   handle->path_mode = path;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetQuadSigma(amdAprilTagsHandle handle, float quad_sigma) {
+  if (!handle || !std::isfinite(quad_sigma) || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
+  uint8_t k[QS_MAX_KSZ] = {};
+  const uint32_t ksz = quad_sigma_taps(quad_sigma, k);
+  QsTaps T = {};
+  int kh = 0;
+  if (ksz > 1) {
+    const int h = (int)ksz / 2;
+    kh = h <= 1 ? 1 : (h <= 2 ? 2 : (h <= 4 ? 4 : 8));
+    for (int i = 0; i < (int)ksz; i++) T.tk[(i + kh - h) >> 2] |= (uint32_t)k[i] << (8 * ((i + kh - h) & 3));
+    T.h = h;
+    T.ksz = (int)ksz;
+    T.sharpen = quad_sigma < 0.0f;
+  }
+  if (ksz == handle->qs_ksz && kh == handle->qs_kh && !memcmp(&T, &handle->qs, sizeof(T))) return AMDAT_SUCCESS;   // (identity -> identity)
+  DeviceGuard guard(handle->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  if (ksz > 1) { const int prc = ensure_gray_plane(handle); if (prc) return prc; }   // the filtered plane
+  drop_graphs(handle);   // captured with the other filter state (the taps travel by value, the launch is there or not)
+  handle->qs_ksz = ksz;
+  handle->qs_kh = kh;
+  handle->qs = T;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
+  if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
+  if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
+  uint8_t k[QS_MAX_KSZ] = {};
+  *ksz = quad_sigma_taps(quad_sigma, k);
+  if (*ksz > 1) {
+    if (!taps || capacity < *ksz) return AMDAT_INVALID_ARGUMENT;
+    memcpy(taps, k, *ksz);
+  }
   return AMDAT_SUCCESS;
 }
 
@@ -941,18 +1006,23 @@ static int check_images(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
 static inline bool colour_fused(const amdAprilTagsDetector_st* D, uint32_t fmt) {
   return fmt != AMDAT_ENC_MONO8 && D->P.decimate == 1 && D->P.tile == 4;
 }
+// The working-size gray plane at decimate 1 (decimated handles have it from creation): allocated on first use by a colour submission
+// that takes the fused loader, or by amdAprilTagsSetQuadSigma for the filtered image.
+static int ensure_gray_plane(amdAprilTagsDetector_st* D) {
+  if (D->d_gray) return AMDAT_SUCCESS;
+  const size_t bytes = (size_t)D->cfg.max_batch * D->P.H * D->P.WS;
+  if (!dev_alloc(D, D->d_gray, bytes)) return AMDAT_OUT_OF_MEMORY;
+  if (hipMemsetAsync(D->d_gray, 0, bytes, D->own_stream) != hipSuccess || hipStreamSynchronize(D->own_stream) != hipSuccess) return AMDAT_HIP_ERROR;
+  return AMDAT_SUCCESS;
+}
 // The gray plane the colour frames of a submission become (allocated on the first colour submission; the pointers travel
 // through the descriptor block, so captured launch sequences of earlier mono8 submissions stay valid).
-static int ensure_colour_plane(amdAprilTagsDetector_st* D, uint32_t fmt) {
-  if (fmt == AMDAT_ENC_MONO8) return AMDAT_SUCCESS;
+// (filt: the submission runs the quad_sigma filter.  At decimate 1 the filter reads the colour frame itself and writes d_gray, which the
+// setter has allocated: no plane here.)
+static int ensure_colour_plane(amdAprilTagsDetector_st* D, uint32_t fmt, bool filt = false) {
+  if (fmt == AMDAT_ENC_MONO8 || (filt && D->P.decimate == 1)) return AMDAT_SUCCESS;
   const size_t B = D->cfg.max_batch;
-  if (colour_fused(D, fmt)) {
-    if (D->d_gray) return AMDAT_SUCCESS;
-    const size_t bytes = B * (size_t)D->P.H * D->P.WS;
-    if (!dev_alloc(D, D->d_gray, bytes)) return AMDAT_OUT_OF_MEMORY;
-    if (hipMemsetAsync(D->d_gray, 0, bytes, D->own_stream) != hipSuccess || hipStreamSynchronize(D->own_stream) != hipSuccess) return AMDAT_HIP_ERROR;
-    return AMDAT_SUCCESS;
-  }
+  if (colour_fused(D, fmt)) return ensure_gray_plane(D);
   if (D->d_conv) return AMDAT_SUCCESS;
   D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
   const size_t bytes = B * D->conv_pitch * D->cfg.height;
@@ -960,10 +1030,15 @@ static int ensure_colour_plane(amdAprilTagsDetector_st* D, uint32_t fmt) {
 }
 
 static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images,
-                        const amdAprilTagsCameraIntrinsics_t* intr, uint32_t fmt = AMDAT_ENC_MONO8) {
+                        const amdAprilTagsCameraIntrinsics_t* intr, uint32_t fmt = AMDAT_ENC_MONO8, bool filt = false) {
   for (uint32_t i = 0; i < n; i++) {
     const amdAprilTagsCameraIntrinsics_t& k = intr ? intr[i] : D->cfg.intrinsics;
-    if (fmt == AMDAT_ENC_MONO8) {
+    if (filt && D->P.decimate == 1) {   // quad_sigma at decimate 1: every stage reads the filtered plane, the filter reads `src`
+      D->h_frames[i].img = D->d_gray + (size_t)i * D->P.H * D->P.WS;
+      D->h_frames[i].pitch = (uint32_t)D->P.WS;
+      D->h_frames[i].src = images[i].dev_ptr;
+      D->h_frames[i].src_pitch = (uint32_t)images[i].pitch;
+    } else if (fmt == AMDAT_ENC_MONO8) {
       D->h_frames[i].img = images[i].dev_ptr;
       D->h_frames[i].pitch = (uint32_t)images[i].pitch;
       D->h_frames[i].src = nullptr; D->h_frames[i].src_pitch = 0;
@@ -982,8 +1057,29 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
   }
 }
 
-static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uint32_t n, hipStream_t s, uint32_t fmt = AMDAT_ENC_MONO8) {
-  if (fmt != AMDAT_ENC_MONO8 && !colour_fused(D, fmt)) {   // conversion launch: src -> the full-size mono8 plane the descriptors name
+// The quad_sigma filter of a submission: each frame's working image (decimate 1: `src`, mono8 or colour; otherwise `img` sampled at the
+// decimation) filtered into its slot of d_gray.
+static void launch_quad_sigma(amdAprilTagsDetector_st* D, const DetParams& P, uint32_t n, hipStream_t s, uint32_t fmt) {
+  QsTaps T = D->qs;
+  T.kind = P.decimate == 1 ? (int)fmt : 3 + (P.decimate < 4 ? P.decimate : 4);
+  const int gx = (P.W + QS_TW - 1) / QS_TW, gy = (P.H + QS_TH - 1) / QS_TH;
+  const unsigned ntiles = (unsigned)gx * gy * n;
+  const dim3 grid(8u * ((ntiles + 7u) / 8u));
+  switch (D->qs_kh) {
+    case 1: hipLaunchKernelGGL(k_quad_sigma<1>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
+    case 2: hipLaunchKernelGGL(k_quad_sigma<2>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
+    case 4: hipLaunchKernelGGL(k_quad_sigma<4>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
+    default: hipLaunchKernelGGL(k_quad_sigma<8>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
+  }
+}
+
+// filt: the submission runs the quad_sigma filter (the handle's setting; amdAprilTagsThresholdOnly never does).  The filter goes first,
+// and the threshold pass then reads the filtered plane at decimate 1 over W x H (the PLANE instances) and leaves it as it is.
+static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uint32_t n, hipStream_t s, uint32_t fmt = AMDAT_ENC_MONO8,
+                             bool filt = false) {
+  // conversion launch: src -> the full-size mono8 plane the descriptors name (with the filter at decimate 1 the filter reads the colour
+  // frame itself; at decimate > 1 decode reads the conversion plane and the filter samples it)
+  if (fmt != AMDAT_ENC_MONO8 && (filt ? P.decimate > 1 : !colour_fused(D, fmt))) {
     const dim3 g((P.W0 + 1023) / 1024, (unsigned)P.H0, n);
     switch (fmt) {
       case AMDAT_ENC_RGB8: hipLaunchKernelGGL((k_to_mono8_frames<3, 0, 2>), g, dim3(256), 0, s, D->d_frames, (uint32_t)P.W0, (uint32_t)P.H0); break;
@@ -993,16 +1089,22 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
     }
     fmt = AMDAT_ENC_MONO8;
   }
+  DetParams Pp = P;   // (PLANE: the source is W x H)
+  if (filt) {
+    launch_quad_sigma(D, P, n, s, fmt);
+    Pp.W0 = P.W; Pp.H0 = P.H;
+  }
   if (P.tile != 4) {   // the two-pass statement (kernels_threshold.h); 4 keeps the one-pass kernel below
     const dim3 g1((unsigned)((P.tw * P.th + 255) / 256), 1, n), g2((unsigned)((P.W + 255) / 256), (unsigned)P.H, n);
-#define TH_ANY(DEC)                                                                                                      \
-    hipLaunchKernelGGL(k_tile_minmax<DEC>, g1, dim3(256), 0, s, D->d_frames, D->d_tmin, D->d_tmax, P.tile, P);           \
-    hipLaunchKernelGGL(k_threshold_any_tile<DEC>, g2, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, D->d_tmin, D->d_tmax, P.tile, P);
-    switch (P.decimate) {
-      case 1: TH_ANY(1) break;
-      case 2: TH_ANY(2) break;
-      case 3: TH_ANY(3) break;
-      default: TH_ANY(4) break;
+#define TH_ANY(DEC, PLANE)                                                                                                       \
+    hipLaunchKernelGGL((k_tile_minmax<DEC, PLANE>), g1, dim3(256), 0, s, D->d_frames, D->d_tmin, D->d_tmax, P.tile, Pp, D->d_gray);  \
+    hipLaunchKernelGGL((k_threshold_any_tile<DEC, PLANE>), g2, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, D->d_tmin, D->d_tmax, P.tile, Pp);
+    if (filt) { TH_ANY(1, true) }
+    else switch (P.decimate) {
+      case 1: TH_ANY(1, false) break;
+      case 2: TH_ANY(2, false) break;
+      case 3: TH_ANY(3, false) break;
+      default: TH_ANY(4, false) break;
     }
 #undef TH_ANY
     return;
@@ -1013,27 +1115,27 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
   const bool leftover = (P.W % 4) || (P.H % 4);
   const int nleft = (P.W - P.tw * 4) * (P.th * 4) + (P.H - P.th * 4) * P.W;
   dim3 lgrid((unsigned)((nleft + 255) / 256), 1, n);
-#define TH_LAUNCH(DEC)                                                                                                   \
-  hipLaunchKernelGGL(k_threshold<DEC>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, gx, gy, (int)n, P);     \
-  if (leftover) hipLaunchKernelGGL(k_threshold_leftover<DEC>, lgrid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, P);
-#define TH_LAUNCH_FMT(FMT)                                                                                                 \
-  hipLaunchKernelGGL((k_threshold<1, FMT>), grid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, gx, gy, (int)n, P);   \
-  if (leftover) hipLaunchKernelGGL((k_threshold_leftover<1, FMT>), lgrid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, P);
+#define TH_LAUNCH(DEC, FMT, PLANE)                                                                                                  \
+  hipLaunchKernelGGL((k_threshold<DEC, FMT, PLANE>), grid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, gx, gy, (int)n, Pp);    \
+  if (leftover) hipLaunchKernelGGL((k_threshold_leftover<DEC, FMT, PLANE>), lgrid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, Pp);
+  if (filt) {
+    TH_LAUNCH(1, 0, true)
+    return;
+  }
   if (fmt != AMDAT_ENC_MONO8) {   // (decimate 1: colour_fused)
     switch (fmt) {
-      case AMDAT_ENC_RGB8: TH_LAUNCH_FMT(1) break;
-      case AMDAT_ENC_BGR8: TH_LAUNCH_FMT(2) break;
-      case AMDAT_ENC_RGBA8: TH_LAUNCH_FMT(3) break;
-      default: TH_LAUNCH_FMT(4) break;
+      case AMDAT_ENC_RGB8: TH_LAUNCH(1, 1, false) break;
+      case AMDAT_ENC_BGR8: TH_LAUNCH(1, 2, false) break;
+      case AMDAT_ENC_RGBA8: TH_LAUNCH(1, 3, false) break;
+      default: TH_LAUNCH(1, 4, false) break;
     }
     return;
   }
-#undef TH_LAUNCH_FMT
   switch (P.decimate) {
-    case 1: TH_LAUNCH(1) break;
-    case 2: TH_LAUNCH(2) break;
-    case 3: TH_LAUNCH(3) break;
-    default: TH_LAUNCH(4) break;
+    case 1: TH_LAUNCH(1, 0, false) break;
+    case 2: TH_LAUNCH(2, 0, false) break;
+    case 3: TH_LAUNCH(3, 0, false) break;
+    default: TH_LAUNCH(4, 0, false) break;
   }
 #undef TH_LAUNCH
 }
@@ -1082,7 +1184,7 @@ static inline uint32_t heuristic_frames(const amdAprilTagsDetector_st* D, uint32
 static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride, hipStream_t s, uint32_t fmt, const std::function<void()>& mark) {
   DetParams P = D->P;
   P.frame0 = 0;
-  launch_threshold(D, P, n, s, fmt);
+  launch_threshold(D, P, n, s, fmt, D->qs_ksz > 1);
   mark();
 #ifndef AMDAT_CC_WIDE
 #define AMDAT_CC_WIDE 1
@@ -1564,8 +1666,9 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   DeviceGuard guard(D->device);
   if (!guard.ok) return AMDAT_HIP_ERROR;
   if (D->unusable) return AMDAT_OUT_OF_MEMORY;   // (never launch on the half-allocated buffers of a failed regrowth)
-  { const int crc = ensure_colour_plane(D, fmt); if (crc) return crc; }
-  fill_frames(D, n, images, intr, fmt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
+  const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
+  { const int crc = ensure_colour_plane(D, fmt, filt); if (crc) return crc; }
+  fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
   D->last_n = n;
   D->last_path = small_submission(D, D->P, n) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;

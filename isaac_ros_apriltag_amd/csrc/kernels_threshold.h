@@ -148,10 +148,13 @@ __device__ __forceinline__ void th_minmax_word(uint32_t w, uint32_t& mn, uint32_
 // (the colour instances take 117 registers -- all loads of both units in flight -- and run at four waves per SIMD against the mono8
 // instance's seven; a budget of 96 or 80 registers makes the compiler spill 12 / 28 of them instead of issuing the loads later, and
 // a scheduling fence between the two units changes nothing: measured 63 - 66 % of 8 TB/s on 5 N bytes as it stands)
-template <int DEC, int FMT = 0>
+// PLANE: the source is the frame's slot of gray_all (pitch P.WS, W x H; the host passes W0 = W, H0 = H), which the quad_sigma filter
+// (kernels_filter.h) has written, and gray_all is not written.
+template <int DEC, int FMT = 0, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__ frames, uint8_t* __restrict__ gray_all,
                                                    uint8_t* __restrict__ thr_all, int gx, int gy, int nframes, DetParams P) {
   static_assert(FMT == 0 || DEC == 1, "the colour loader does not decimate");
+  static_assert(!PLANE || (DEC == 1 && FMT == 0), "the filtered plane is a working-size mono8 image");
   __shared__ __attribute__((aligned(16))) uint8_t smin[10 * TH_LDS_STRIDE];
   __shared__ __attribute__((aligned(16))) uint8_t smax[10 * TH_LDS_STRIDE];
 
@@ -165,8 +168,8 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
   const int bx = trem % gx, by = trem / gx;
   const FrameDesc fd = frames[frame];
   // (a colour submission: the loader reads the caller's interleaved frame, fd.img is the handle's gray plane of pitch WS)
-  const th_gimg_t simg = (th_gimg_t)(FMT ? fd.src : fd.img);
-  const uint32_t spitch = FMT ? fd.src_pitch : fd.pitch;
+  const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_all + (size_t)frame * P.H * P.WS) : (th_gimg_t)(FMT ? fd.src : fd.img);
+  const uint32_t spitch = PLANE ? (uint32_t)P.WS : (FMT ? fd.src_pitch : fd.pitch);
   const bool aligned = ((((uintptr_t)simg) | (uintptr_t)spitch) & 15) == 0;
   const int tid = threadIdx.x;
   const int tx64 = tid & 63, ty4 = tid >> 6;
@@ -320,13 +323,13 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
 // Pixels right of / below the last full tile (only when W or H is not a multiple of 4): threshold
 // against the nearest tile's dilated min/max, recomputed from its 12x12 neighbourhood.  No
 // low-contrast rule there.
-template <int DEC, int FMT = 0>
+template <int DEC, int FMT = 0, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_threshold_leftover(const FrameDesc* __restrict__ frames, uint8_t* __restrict__ gray_all,
                                                             uint8_t* __restrict__ thr_all, DetParams P) {
   const int frame = (int)blockIdx.z + P.frame0;
   const FrameDesc fd = frames[frame];
-  const th_gimg_t simg = (th_gimg_t)(FMT ? fd.src : fd.img);
-  const uint32_t spitch = FMT ? fd.src_pitch : fd.pitch;
+  const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_all + (size_t)frame * P.H * P.WS) : (th_gimg_t)(FMT ? fd.src : fd.img);
+  const uint32_t spitch = PLANE ? (uint32_t)P.WS : (FMT ? fd.src_pitch : fd.pitch);
   const int nright = P.W - P.tw * 4;  // columns per row in the right strip
   const int nbot = P.H - P.th * 4;    // rows in the bottom strip
   const int right_cnt = nright * (P.th * 4);
@@ -358,18 +361,21 @@ __global__ __launch_bounds__(256) void k_threshold_leftover(const FrameDesc* __r
 // accepted size takes the plain statement of SURVEY.md A.2 in two passes -- per-tile min / max to two small global arrays
 // (tw x th bytes per frame), then per pixel the 3 x 3 tile neighbourhood, the low-contrast rule inside the full tiles and the
 // nearest tile's threshold right of / below them.  Same bytes as the oracle's ato_threshold(.., tile, ..); not a tuned kernel.
-template <int DEC>
+// (PLANE as in k_threshold: the source is the filtered plane gray_plane; null otherwise)
+template <int DEC, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_tile_minmax(const FrameDesc* __restrict__ frames, uint8_t* __restrict__ tmin_all,
-                                                     uint8_t* __restrict__ tmax_all, int ts, DetParams P) {
+                                                     uint8_t* __restrict__ tmax_all, int ts, DetParams P, const uint8_t* __restrict__ gray_plane) {
   const int frame = (int)blockIdx.z + P.frame0;
   const FrameDesc fd = frames[frame];
+  const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_plane + (size_t)frame * P.H * P.WS) : (th_gimg_t)fd.img;
+  const uint32_t spitch = PLANE ? (uint32_t)P.WS : fd.pitch;
   const int t = (int)(blockIdx.x * 256 + threadIdx.x);
   if (t >= P.tw * P.th) return;
   const int tx = t % P.tw, ty = t / P.tw;
   uint32_t mn = 255, mx = 0;
   for (int r = 0; r < ts; r++)
     for (int c = 0; c < ts; c++) {
-      const uint32_t v = th_px<DEC>((th_gimg_t)fd.img, fd.pitch, P.W0, P.H0, tx * ts + c, ty * ts + r);
+      const uint32_t v = th_px<DEC>(simg, spitch, P.W0, P.H0, tx * ts + c, ty * ts + r);
       mn = min(mn, v);
       mx = max(mx, v);
     }
@@ -377,12 +383,15 @@ __global__ __launch_bounds__(256) void k_tile_minmax(const FrameDesc* __restrict
   tmax_all[(size_t)frame * P.tw * P.th + t] = (uint8_t)mx;
 }
 
-template <int DEC>
+template <int DEC, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_threshold_any_tile(const FrameDesc* __restrict__ frames, uint8_t* __restrict__ gray_all,
                                                             uint8_t* __restrict__ thr_all, const uint8_t* __restrict__ tmin_all,
                                                             const uint8_t* __restrict__ tmax_all, int ts, DetParams P) {
+  static_assert(!PLANE || DEC == 1, "the filtered plane is a working-size image");
   const int frame = (int)blockIdx.z + P.frame0;
   const FrameDesc fd = frames[frame];
+  const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_all + (size_t)frame * P.H * P.WS) : (th_gimg_t)fd.img;
+  const uint32_t spitch = PLANE ? (uint32_t)P.WS : fd.pitch;
   const int x = (int)(blockIdx.x * 256 + threadIdx.x), y = (int)blockIdx.y;
   if (x >= P.W) return;
   const uint8_t* tmin = tmin_all + (size_t)frame * P.tw * P.th;
@@ -394,7 +403,7 @@ __global__ __launch_bounds__(256) void k_threshold_any_tile(const FrameDesc* __r
       mn = min(mn, (uint32_t)tmin[ty * P.tw + tx]);
       mx = max(mx, (uint32_t)tmax[ty * P.tw + tx]);
     }
-  const uint32_t v = th_px<DEC>((th_gimg_t)fd.img, fd.pitch, P.W0, P.H0, x, y);
+  const uint32_t v = th_px<DEC>(simg, spitch, P.W0, P.H0, x, y);
   const bool in_full_tile = x < P.tw * ts && y < P.th * ts;   // (no low-contrast rule right of / below the last full tile)
   uint8_t o;
   if (in_full_tile && (int)(mx - mn) < P.min_white_black_diff) o = 127;

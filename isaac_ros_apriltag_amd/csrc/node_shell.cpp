@@ -42,6 +42,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsCopyToDeviceAsync) copy_to_device_async = nullptr;
   decltype(&amdAprilTagsStreamCreate) stream_create = nullptr;
   decltype(&amdAprilTagsStreamDestroy) stream_destroy = nullptr;
+  decltype(&amdAprilTagsSetQuadSigma) set_quad_sigma = nullptr;
 };
 
 DetectorApi& api() {
@@ -76,6 +77,7 @@ DetectorApi& api() {
   BIND(copy_to_device_async, "amdAprilTagsCopyToDeviceAsync")
   BIND(stream_create, "amdAprilTagsStreamCreate")
   BIND(stream_destroy, "amdAprilTagsStreamDestroy")
+  BIND(set_quad_sigma, "amdAprilTagsSetQuadSigma")
 #undef BIND
   return a;
 }
@@ -85,6 +87,13 @@ const char* const kKnownFamilyStrings[] = {"tag36h11", "tag16h5", "tag25h9", "ta
                                            "circle49h12", "custom48h12", "standard41h12", "standard52h13"};
 
 // Encodings the node's input conversion accepts (src/apriltag_node.cpp:76-82).
+// NodeOptions::quad_sigma on a freshly created handle (an identity value changes nothing: no plane, no launch)
+void apply_quad_sigma(amdAprilTagsHandle detector, double quad_sigma) {
+  const int error = api().set_quad_sigma(detector, static_cast<float>(quad_sigma));
+  if (error != 0)
+    throw std::runtime_error("'quad_sigma' " + std::to_string(quad_sigma) + " refused (error code " + std::to_string(error) + ")");
+}
+
 int bytes_per_pixel(const std::string& enc) {
   if (enc == "mono8") return 1;
   if (enc == "rgb8" || enc == "bgr8") return 3;
@@ -247,6 +256,7 @@ struct AprilTagNode::Impl {
       // same text as src/apriltag_node.cpp:453-457 with the library name replaced
       throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
     }
+    apply_quad_sigma(detector, opt.quad_sigma);
     width = info.width;
     height = info.height;
     if (!stream && api().stream_create(&stream) != 0) throw std::runtime_error("stream creation failed");
@@ -386,6 +396,7 @@ struct AprilTagMultiCameraNode::Impl {
     cfg.max_batch = S;
     const int error = api().create_ex(&detector, &cfg);
     if (error != 0) throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
+    apply_quad_sigma(detector, opt.quad_sigma);
     width = info.width;
     height = info.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
@@ -549,13 +560,15 @@ struct NodeShellDetection {
 
 extern "C" {
 
-// Returns nullptr and fills err on a constructor exception (mirrors test/apriltag_node_test.cpp).
-NodeShellHarness* node_shell_create(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
-                                    int decimate, char* err, size_t err_len) {
+// Every NodeOptions field the flat view carries (node.py): the create calls below are this one with quad_sigma 0.
+NodeShellHarness* node_shell_create_ex(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                       int decimate, int strict_cuapriltags_encodings, double quad_sigma, char* err, size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.strict_cuapriltags_encodings = strict_cuapriltags_encodings != 0;
+    o.quad_sigma = quad_sigma;
     auto* h = new NodeShellHarness();
     h->node.reset(new AprilTagNode(o));
     h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
@@ -567,23 +580,16 @@ NodeShellHarness* node_shell_create(int max_tags, double size, int tile_size, co
   }
 }
 
+// Returns nullptr and fills err on a constructor exception (mirrors test/apriltag_node_test.cpp).
+NodeShellHarness* node_shell_create(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                    int decimate, char* err, size_t err_len) {
+  return node_shell_create_ex(max_tags, size, tile_size, tag_family, backends, decimate, 0, 0.0, err, err_len);
+}
+
 // the same with NodeOptions::strict_cuapriltags_encodings set
 NodeShellHarness* node_shell_create_strict(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
                                            int decimate, char* err, size_t err_len) {
-  try {
-    NodeOptions o;
-    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
-    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
-    o.strict_cuapriltags_encodings = true;
-    auto* h = new NodeShellHarness();
-    h->node.reset(new AprilTagNode(o));
-    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
-    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
-    return h;
-  } catch (const std::exception& e) {
-    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
-    return nullptr;
-  }
+  return node_shell_create_ex(max_tags, size, tile_size, tag_family, backends, decimate, 1, 0.0, err, err_len);
 }
 
 void node_shell_destroy(NodeShellHarness* h) { delete h; }
@@ -636,12 +642,14 @@ struct MultiShellHarness {
   std::vector<int> publishes;
 };
 
-MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
-                                           const char* backends, int decimate, int auto_flush, char* err, size_t err_len) {
+MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                              const char* backends, int decimate, int auto_flush, double quad_sigma, char* err,
+                                              size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.quad_sigma = quad_sigma;
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
     h->node->set_auto_flush(auto_flush != 0);
@@ -653,6 +661,11 @@ MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+
+MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                           const char* backends, int decimate, int auto_flush, char* err, size_t err_len) {
+  return node_shell_multi_create_ex(num_streams, max_tags, size, tile_size, tag_family, backends, decimate, auto_flush, 0.0, err, err_len);
 }
 
 void node_shell_multi_destroy(MultiShellHarness* h) { delete h; }

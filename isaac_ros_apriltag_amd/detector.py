@@ -43,7 +43,7 @@ def _as_images(frames, width, height, channels=1):
 
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
-                 tile_size=4, device=-1, refine_edges=True, **caps):
+                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -70,6 +70,16 @@ class AprilTagDetector:
         self._h = C.c_void_p()
         capi._check("amdCreateAprilTagsDetectorEx", L.amdCreateAprilTagsDetectorEx(C.byref(self._h), C.byref(cfg)))
         self._L = L
+        if quad_sigma:
+            try:
+                self.set_quad_sigma(quad_sigma)
+            except Exception:
+                self.close()
+                raise
+
+    def set_quad_sigma(self, sigma):
+        """quad_sigma (amdAprilTagsSetQuadSigma): blur (> 0) or sharpen (< 0) of the working image; takes effect with the next submission."""
+        capi._check("amdAprilTagsSetQuadSigma", self._L.amdAprilTagsSetQuadSigma(self._h, float(sigma)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

@@ -29,6 +29,9 @@ def lib():
         L.node_shell_create.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
         L.node_shell_create_strict.restype = C.c_void_p
         L.node_shell_create_strict.argtypes = L.node_shell_create.argtypes
+        L.node_shell_create_ex.restype = C.c_void_p
+        L.node_shell_create_ex.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double,
+                                           C.c_char_p, C.c_size_t]
         L.node_shell_destroy.argtypes = [C.c_void_p]
         L.node_shell_on_frame.restype = C.c_int
         L.node_shell_on_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -36,6 +39,9 @@ def lib():
                                           C.POINTER(ShellDetection), C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         L.node_shell_multi_create.restype = C.c_void_p
         L.node_shell_multi_create.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_ex.restype = C.c_void_p
+        L.node_shell_multi_create_ex.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                 C.c_double, C.c_char_p, C.c_size_t]
         L.node_shell_multi_destroy.argtypes = [C.c_void_p]
         L.node_shell_multi_on_frame.restype = C.c_int
         L.node_shell_multi_on_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -66,11 +72,11 @@ class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True):
+                 auto_flush=True, quad_sigma=0.0):
         err = C.create_string_buffer(1024)
         self._L = lib()
-        self._h = self._L.node_shell_multi_create(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
-                                                  decimate, 1 if auto_flush else 0, err, 1024)
+        self._h = self._L.node_shell_multi_create_ex(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
+                                                     decimate, 1 if auto_flush else 0, float(quad_sigma), err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags, self.num_streams = max_tags, num_streams
@@ -115,11 +121,12 @@ class AprilTagNode:
     """Parameters and defaults of the reference node (apriltag_node.cpp:564-568)."""
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 strict_cuapriltags_encodings=False):
+                 strict_cuapriltags_encodings=False, quad_sigma=0.0):
+        """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma)."""
         err = C.create_string_buffer(1024)
         self._L = lib()
-        create = self._L.node_shell_create_strict if strict_cuapriltags_encodings else self._L.node_shell_create
-        self._h = create(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate, err, 1024)
+        self._h = self._L.node_shell_create_ex(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                               1 if strict_cuapriltags_encodings else 0, float(quad_sigma), err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags = max_tags

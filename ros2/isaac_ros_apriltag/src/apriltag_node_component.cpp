@@ -47,6 +47,7 @@ public:
     opt.tag_family = declare_parameter<std::string>("tag_family", "tag36h11");
     opt.backends = declare_parameter<std::string>("backends", "CUDA");  // name or comma list; exactly "CUDA" = cuAprilTags mode
     opt.decimate = static_cast<uint32_t>(declare_parameter<int>("decimate", 1));
+    opt.quad_sigma = declare_parameter<double>("quad_sigma", 0.0);   // AprilRobotics quad_sigma (apriltag_ros `blur` / `sigma`)
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);

@@ -22,6 +22,7 @@ if os.environ.get("AMDAT_LIB"):   # measurement / stress variant (isaac_ros_apri
     capi.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "isaac_ros_apriltag_amd", "libapriltag_amd_%s.so" % os.environ["AMDAT_LIB"])
 from isaac_ros_apriltag_amd.detector import AprilTagDetector  # noqa: E402
 import parity_util as pu  # noqa: E402
+import quad_sigma_ref as qs  # noqa: E402
 
 
 def gen_content(rng, h, w):
@@ -109,7 +110,7 @@ def colour_frame(rng, gray_like, encoding, pitch_pad):
 MAX_DETS = 256   # records a call asks for: a frame with more (noise fields under tag16h5) comes back as the first MAX_DETS of the canonical order
 
 
-def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1, only=None, dump=None, colour=False, tile=4, params=False, layout=False):
+def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1, only=None, dump=None, colour=False, tile=4, params=False, layout=False, quad_sigma=False):
     """Returns (cases run, list of failure strings).  path: None (the library picks the launch set by size: the latency set at these
     sizes), "latency", "throughput", or "alternate" (even cases latency, odd cases throughput).  batch > 1: every case submits `batch` frames
     of the case's size, each with content of its own, in ONE call, and every frame is compared (frame indexing of every stage)."""
@@ -164,6 +165,10 @@ def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1
             fails.append("case %d: create failed for %dx%d dec %d: %s" % (case, w, h, dec, e))
             out(fails[-1])
             continue
+        qsig = 0.0
+        if quad_sigma:   # quad_sigma in [-4, 4] (a generator of its own); the oracle runs on the filtered frame (tests/quad_sigma_ref.py)
+            qsig = float(np.float32(np.random.default_rng(seed * 104729 + case).uniform(-4.0, 4.0)))
+            det.set_quad_sigma(qsig)
         if path is not None:
             det.set_submission_path(("latency", "throughput")[case & 1] if path == "alternate" else path)
         enc = "mono8"
@@ -190,14 +195,19 @@ def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1
         gs = det.detect_batch_ex(ptrs if ptrs else [(t.data_ptr(), pitch) for t in ts], max_dets=MAX_DETS, encoding=enc)
         errs = []
         for f in range(batch):
-            e, odets = pu.compare_stages(det, f, np.ascontiguousarray(imgs[f]), fams, K, dec, tag_size=tag_size, tile_size=tile, **more)
-            e += pu.compare_detections(gs[f], odets[:MAX_DETS])
+            oimg = np.ascontiguousarray(imgs[f])
+            if qsig:   # decimate 1: every stage reads the filtered frame; decimate > 1: J, compared through the quads
+                filt = qs.filter_image(qs.decimate(oimg, dec), qsig)
+                oimg = filt if dec == 1 else qs.embed_decimated(oimg, filt, dec)
+            e, odets = pu.compare_stages(det, f, oimg, fams, K, dec, tag_size=tag_size, tile_size=tile, **more)
+            if not qsig or dec == 1:
+                e += pu.compare_detections(gs[f], odets[:MAX_DETS])
             errs += ["frame %d: %s" % (f, x) for x in e] if batch > 1 else e
         det.close()
         done += 1
         if errs:
-            fails.append("case %d FAIL kind %s %dx%d pitch %d dec %d fams %s enc %s %s: %s" % (case, kind, w, h, pitch, dec, fams, enc,
-                                                                                            more, errs[:3]))
+            fails.append("case %d FAIL kind %s %dx%d pitch %d dec %d fams %s enc %s %s quad_sigma %r: %s" % (case, kind, w, h, pitch, dec, fams,
+                                                                                                           enc, more, qsig, errs[:3]))
             out(fails[-1])
     return done, fails
 
@@ -215,11 +225,13 @@ def main():
     ap.add_argument("--colour", action="store_true", help="submit the content as rgb8 / bgr8 / rgba8 / bgra8 frames with random chroma")
     ap.add_argument("--params", action="store_true", help="random decode parameters (refine_edges, max_hamming 0..3, decode_sharpening, skew, tag_size)")
     ap.add_argument("--layout", action="store_true", help="every frame at a base address (any byte) and a pitch of its own")
+    ap.add_argument("--quad-sigma", action="store_true", help="random quad_sigma in [-4, 4] per case (blur or sharpen of the working image)")
     ap.add_argument("--path", default="alternate", help="launch set: latency | throughput | alternate | auto")
     a = ap.parse_args()
     t0 = time.time()
     done, fails = run_cases(a.cases, a.seed, a.maxdim, a.budget, out=lambda m: print(m, flush=True), path=None if a.path == "auto" else a.path, batch=a.batch,
-                            only=a.only, dump=a.dump, colour=a.colour, tile=a.tile, params=a.params, layout=a.layout)
+                            only=a.only, dump=a.dump, colour=a.colour, tile=a.tile, params=a.params, layout=a.layout,
+                            quad_sigma=a.quad_sigma)
     print("fuzz: %d cases, %d failed, %.1f s" % (done, len(fails), time.time() - t0))
     sys.exit(1 if fails else 0)
 
