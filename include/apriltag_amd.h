@@ -269,7 +269,7 @@ int amdAprilTagsSetFrameSkews(amdAprilTagsHandle handle, uint32_t n, const float
  * submission is in flight; takes effect with the next submission.  AMDAT_INVALID_ARGUMENT: null handle, NaN / inf, a submission in
  * flight; AMDAT_UNSUPPORTED: |quad_sigma| > 4; AMDAT_OUT_OF_MEMORY: the filtered plane (decimate 1) could not be allocated.  A refused
  * call leaves the previous setting in force.  A call that changes the filter (its taps, or on / off) retires the launch graphs the handle
- * has captured for small submissions; after 24 retired graphs in all (AMDAT_MAX_RETIRED_GRAPHS, counting those of capacity growth and
+ * has captured for small submissions; after 24 retired graphs in all (counting those of capacity growth and
  * cache evictions) the handle stops capturing new ones and enqueues such submissions plainly, about 0.1 ms more per one-frame call
  * (amdAprilTagsDebugGraphReplay reports it).  Set it once after create, or rarely. */
 int amdAprilTagsSetQuadSigma(amdAprilTagsHandle handle, float quad_sigma);

@@ -29,6 +29,7 @@
 #include "kernels_quad.h"
 #include "kernels_quad_small.h"
 #include "kernels_threshold.h"
+#include "launch_plan.h"
 
 static_assert(sizeof(DetRec) == sizeof(amdAprilTagsDetectionEx_t), "DetRec must match the public record");
 static_assert(sizeof(QuadRec) == 48, "QuadRec layout");
@@ -151,18 +152,8 @@ template <class T> struct DevBuf : DevAlloc {
 };
 }  // namespace
 
-// One size class of the quad fit: workgroup size, LDS key capacity, cluster sizes (lo, hi], persistent grid,
-// scratch slot size (points) and its slice of the work array.
-// Side streams of the quad fit.  Three, as in every earlier round: a captured submission with six parallel branches (five side
-// streams + the submission stream) crashed inside hipGraphLaunch (hip::Graph::UpdateStreams, ROCm 7.2) in about one of seven
-// 300-case fuzz runs; with four branches it never has.  Classes that launch share the streams round-robin.
-#define FQ_NAUX 3
-struct FqClass {
-  int nt, sort_cap, lo, hi;
-  unsigned grid;
-  int slot_cap;
-  int pop;                                // clusters taken from the work list per atomic
-  int small_k = 0;                        // > 0: k_fit_small<small_k> (keys and sweep state in registers, moments in LDS), no scratch
+// Scratch of one k_fit_quads class (launch_plan.h: FqClassSpec); k_fit_small keeps its moments in LDS and has none.
+struct FqScratch {
   DevBuf<double> d_lf;                    // grid x slot_cap x 6 doubles
   DevBuf<double> d_errs;                  // grid x slot_cap x 2 doubles: error arrays of clusters that exceed what the
                                           // kernel keeps in LDS / registers (slot_cap > 16 x nt, or > sort_cap)
@@ -215,10 +206,9 @@ struct amdAprilTagsDetector_st {
   std::vector<DevAlloc*> owned;      // every holder above that has had an allocation (dev_alloc): what free_all releases
   unsigned long long* d_ptprof = nullptr;  // per-phase cycle counters of k_points (same builds), inside d_fqprof's allocation
   DevBuf<unsigned long long> d_fqprof;     // per-phase cycle counters of k_fit_quads (-DAMDAT_FQ_PROFILE builds only)
-  FqClass cls[FQ_NCLS];
-  FqWorkLayout work_layout;
-  FqWorkLayout work_layout_small;    // small submissions: the k_fit_small classes are empty, the one-wave class starts at 0 (issue_pipeline)
-  int prefilter_class = FQ_C0 + 2;           // first size class whose clusters go through k_fit_prefilter (those above 2048 points)
+  FqClassTable fq;                   // size classes of the quad fit (launch_plan.h; set at creation)
+  FqScratch fq_scratch[FQ_NCLS];
+  FqWorkLayouts work_layout;         // their work lists on either launch set (alloc_point_buffers)
   GrowLimits grow = {};              // which capacities follow the content, and up to what (growth.h; set at creation)
   bool pending_hash_grow = false;    // the last submission crowded the pair table: it grows before the next one (begin_batch)
   uint32_t lcap_div = 0;             // long-record capacity = point capacity / lcap_div (alloc_point_buffers; halves when the long records overflow)
@@ -528,22 +518,8 @@ static int alloc_hash_buffers(amdAprilTagsDetector_st* D) {
 static int alloc_point_buffers(amdAprilTagsDetector_st* D) {
   DetParams& P = D->P;
   const size_t B = D->cfg.max_batch;
-  uint64_t off = 0;
-  for (int k = 0; k < FQ_NCLS; k++) {
-    const FqClass& c = D->cls[k];
-    D->work_layout.lo[k] = c.lo < 23 ? 23 : c.lo;
-    D->work_layout.hi[k] = c.hi;
-    // (the one-wave class of k_fit_quads also takes the k_fit_small classes' clusters on small submissions: sized from 24 points)
-    const uint32_t per_frame = P.pcap / (uint32_t)((k == FQ_C0 ? 23 : D->work_layout.lo[k]) + 1) + 1;
-    const uint64_t cap = c.hi <= c.lo ? 16 : (uint64_t)B * (per_frame < P.ccap ? per_frame : P.ccap);   // (an empty class keeps a token range)
-    if (cap > 0x7FFFFFFFull || off + cap > 0xFFFFFFFFull) return AMDAT_BATCH_TOO_LARGE;   // offsets and cursors are 32-bit
-    D->work_layout.off[k] = (uint32_t)off;
-    D->work_layout.cap[k] = (uint32_t)cap;
-    off += cap;
-  }
-  D->work_layout_small = D->work_layout;
-  for (int k = 0; k < FQ_C0; k++) { D->work_layout_small.lo[k] = 23; D->work_layout_small.hi[k] = 0; }
-  D->work_layout_small.lo[FQ_C0] = 23;
+  { const int rc = plan_work_layouts(D->fq, P.pcap, P.ccap, (uint32_t)B, &D->work_layout); if (rc) return rc; }
+  const size_t off = D->work_layout.words;
   // Long staging records (kernels_cluster.h) only occur where a 64 x 16 tile has more than 2048 emissions -- above two per pixel --
   // or more than 255 component pairs; an eighth of the point capacity is room for them on ordinary content.  An overflow reports
   // like a point overflow (AMDAT_FLAG_POINTS_OVERFLOW); the host tells the two apart by the counters and grows the list by itself
@@ -556,8 +532,8 @@ static int alloc_point_buffers(amdAprilTagsDetector_st* D) {
   if (D->lcap_div == 0) D->lcap_div = AMDAT_LCAP_DIV;
   P.lcap = long_capacity(P.pcap, D->lcap_div);
   DevAlloc* bufs[5] = {&D->d_stage, &D->d_long, &D->d_pts, &D->d_work, &D->d_work2};
-  const size_t bytes[5] = {B * (size_t)P.pcap * 4, B * (size_t)P.lcap * 16, B * (size_t)P.pcap * 4, (size_t)off * 4,
-                           ((size_t)off - D->work_layout.off[D->prefilter_class]) * 4};
+  const size_t bytes[5] = {B * (size_t)P.pcap * 4, B * (size_t)P.lcap * 16, B * (size_t)P.pcap * 4, off * 4,
+                           (off - D->work_layout.all.off[D->fq.prefilter_class]) * 4};
   for (DevAlloc* b : bufs) dev_free(D, *b);
   for (int i = 0; i < 5; i++)
     if (!dev_alloc(D, *bufs[i], bytes[i])) return AMDAT_OUT_OF_MEMORY;
@@ -695,63 +671,7 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
   if (P.dcap > 65535) P.dcap = 65535;
 
   const size_t B = cfg.max_batch;
-  // ---- size classes of the quad fit ------------------------------------------------------------------
-  // one wave per small cluster, bigger workgroups and LDS key arrays above; persistent grids sized to the
-  // chip (CUs x workgroups that fit one CU) but not beyond what a submission of B frames can feed.
-  // The two large classes need most of a CU's LDS for their key arrays, so they cannot share a CU with the other
-  // classes' persistent workgroups: they run first and alone, at the 128-register budget of the other classes --
-  // clusters above 8192 points in 1024-thread workgroups (16 waves, one workgroup per CU), then 4096..8192 points in
-  // 512-thread workgroups, two per CU.  (With 512 threads at twice the registers and no room for a neighbour the
-  // largest clusters used to run at a quarter of the chip's occupancy, mostly at the end of the stage: 17 ms of wall
-  // time for 4 % of the stage's instructions.)
-  {
-    const unsigned cus = (unsigned)D->num_cus;
-    auto minu = [](unsigned a, unsigned b) { return a < b ? a : b; };
-    FqClass* c = D->cls;
-    // Class boundaries: the one-wave class has no workgroup barriers at all and runs closest to the VALU issue rate
-    // (82 % against 53-57 % for the 128- and 256-thread classes), so it takes clusters up to 768 points, the most its
-    // 16 workgroups per CU can hold in LDS (9 KB each); measured 16.1 ms (256 / 1024) -> 15.5 (512 / 1024) -> 15.35
-    // (768 / 2048); 896 and 1024 are slower again (fewer resident workgroups).
-#ifndef FQ_B01
-#define FQ_B01 768
-#define FQ_B12 2048
-#endif
-    // Clusters per pop: one atomic per cluster saturates the list cursor (one-wave class: 18.7 ms), chunks of 16 / 8 / 2
-    // leave workgroups with up to 16 clusters of work while others have drained the list (15.4 ms); 4 / 2 / 1: 15.0.
-#ifndef FQ_POP0
-#define FQ_POP0 4
-#define FQ_POP1 2
-#define FQ_POP2 1
-#endif
-    // The two smallest classes run k_fit_small (kernels_quad_small.h): clusters up to 128 (and 256) points, whose keys and
-    // sweep state fit a wave's registers and whose cumulative moments fit LDS.  They exist on the two-double path only
-    // (working images up to 2048 x 2048); otherwise their ranges are empty and the one-wave class starts at 0.
-#ifndef FS_B0
-#define FS_B0 128
-#endif
-#ifndef FS_B1
-#define FS_B1 FS_B0   // (= FS_B0: no K = 4 class)
-#endif
-#ifndef FS_K4_GROWS
-#define FS_K4_GROWS true   // the K = 4 class's moments: true -- global scratch slot; false -- LDS (14 KB per workgroup)
-#endif
-    const int sb0 = P.split_moments ? FS_B0 : 0, sb1 = P.split_moments ? FS_B1 : 0;
-    c[0] = {64, 0, 0, sb0, minu((unsigned)FS_GRID_K2 * cus, 4096u * (unsigned)B), sb0, FQ_POP0, 2};
-    c[1] = {64, 0, sb0, sb1, minu((unsigned)FS_GRID_K4 * cus, 4096u * (unsigned)B), sb1 > 256 ? sb1 : 256, FQ_POP0, 4};   // (slot: 256 rows of moments)
-    FqClass* const q = c + FQ_C0;   // the classes of k_fit_quads
-    q[0] = {64, FQ_B01, sb1, FQ_B01, minu((unsigned)FQ_GRID_64 * cus, 4096u * (unsigned)B), FQ_B01, FQ_POP0};
-    q[1] = {128, FQ_B12, FQ_B01, FQ_B12, minu((unsigned)FQ_GRID_128 * cus, 1024u * (unsigned)B), FQ_B12, FQ_POP1};
-    q[2] = {256, 4096, FQ_B12, 4096, minu(4u * cus, 256u * (unsigned)B), 4096, FQ_POP2};
-    q[3] = {512, 8192, 4096, 8192, minu(2u * cus, 64u * (unsigned)B), 8192, 1};
-    // (a "latency layout" for small-batch handles -- about three times the threads per cluster: 64 up to 256 points, 128 up
-    // to 768, 256 up to 2048, 512 up to 8192 -- measured slower on one-frame submissions, 0.36 against 0.28 ms for the
-    // stage: the larger workgroups' barriers cost more than the shorter per-lane runs save)
-    D->prefilter_class = FQ_C0 + 2;
-    q[4] = {FQ_NT_BIG, 16384, 8192, 0x7FFFFFFF, minu(cus, 16u * (unsigned)B), P.max_cluster_points, 1};
-    static_assert(FQ_C0 + 5 == FQ_NCLS, "class table");
-    if (P.max_cluster_points > 16384 && P.max_cluster_points <= 18432) q[4].sort_cap = (P.max_cluster_points + 63) & ~63;
-    if (q[4].slot_cap < 8193) q[4].slot_cap = 8193;
-  }
+  D->fq = plan_classes(P.max_cluster_points, P.split_moments != 0, (unsigned)D->num_cus, (uint32_t)B);
 
   bool ok = true;
   auto alloc = [&](DevAlloc& b, size_t bytes) { if (ok) ok = dev_alloc(D, b, bytes); };
@@ -774,17 +694,14 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
   alloc(D->d_clusters, B * (size_t)P.ccap * sizeof(ClusterRec));
   if (ok) { const int rc = alloc_point_buffers(D); if (rc == AMDAT_BATCH_TOO_LARGE) { free_all(D); delete D; return rc; } ok = rc == AMDAT_SUCCESS; }
   for (int k = 0; k < FQ_NCLS; k++) {
-    FqClass& c = D->cls[k];
-    // (the one-wave class of k_fit_quads takes every cluster from 24 points on when a submission runs the latency set: its lower
-    // bound for "can this class ever see a cluster" is 23, whatever the k_fit_small classes below it would take on the other set)
-    const int lo_eff = k == FQ_C0 ? 23 : c.lo;
-    if (P.max_cluster_points <= lo_eff || c.small_k == 2 || c.hi <= c.lo) continue;   // (k_fit_small<2> keeps its moments in LDS)
-    alloc(c.d_lf, (size_t)c.grid * c.slot_cap * 48);
+    const FqClassSpec& c = D->fq.cls[k];
+    if (c.kernel != FQ_QUADS || !(class_sees_clusters(D->fq, k, false) || class_sees_clusters(D->fq, k, true))) continue;
+    alloc(D->fq_scratch[k].d_lf, (size_t)c.grid * c.slot_cap * 48);
     // smoothed errors stay in registers up to FQ_SMOOTH_REGS_OF(threads) points per thread; larger clusters need a second array
-    if (!c.small_k && (c.slot_cap > FQ_SMOOTH_REGS_OF(c.nt) * c.nt || c.slot_cap > c.sort_cap)) alloc(c.d_errs, (size_t)c.grid * c.slot_cap * 16);
+    if (c.slot_cap > FQ_SMOOTH_REGS_OF(c.nt) * c.nt || c.slot_cap > c.sort_cap) alloc(D->fq_scratch[k].d_errs, (size_t)c.grid * c.slot_cap * 16);
   }
-  if (D->cls[FQ_NCLS - 1].slot_cap > D->cls[FQ_NCLS - 1].sort_cap) {   // clusters beyond the LDS key array exist
-    const FqClass& c = D->cls[FQ_NCLS - 1];
+  if (D->fq.cls[FQ_NCLS - 1].slot_cap > D->fq.cls[FQ_NCLS - 1].sort_cap) {   // clusters beyond the LDS key array exist
+    const FqClassSpec& c = D->fq.cls[FQ_NCLS - 1];
     alloc(D->d_keys_scr, (size_t)c.grid * c.slot_cap * 8);
   }
   alloc(D->d_quads, B * (size_t)P.qcap * sizeof(QuadRec));
@@ -1140,8 +1057,6 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
 #undef TH_LAUNCH
 }
 
-// Issues the whole stage sequence for batch slots [0, n) on stream s.  mark() is called between stages
-// (event timing when profiling).
 // first launch of a submission: frame descriptors from the pinned host block to device memory, work-list control words
 // and frame counters to zero (one block per frame)
 __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ host_frames, uint32_t* __restrict__ frames,
@@ -1156,45 +1071,21 @@ __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ ho
 // after the last kernel (about 10 us of a one-frame call; at 256 frames the strided 3.8 MB copy of mostly empty record slots cost
 // 0.08 ms per step against the ~0.6 MB of real records the kernel writes: 17.85 -> 17.77 ms).
 
-// A small submission (the node's one-frame calls, up to eight 1080p frames) is about latency, not throughput: every cluster
-// is a workgroup's only one, the stage ends with its longest chain, and a launch more costs more than k_fit_small's shorter
-// chain per small cluster saves (measured: 0.54 against 0.47 ms per one-frame call).  Such a submission buckets all clusters
-// up to the one-wave class's bound into that class (work_layout_small) and launches no k_fit_small.
-#ifndef AMDAT_SMALL_PX
-#define AMDAT_SMALL_PX (16ull << 20)
-#endif
-#ifndef AMDAT_SMALL_PX_CC      // k_cc_local<16> below this many working pixels per submission (eight 1080p frames: 0.089 ms with
-#define AMDAT_SMALL_PX_CC (8ull << 20)   // four waves per tile against 0.123 with sixteen -- the chip is full by then; four frames: 0.068 either way)
-#endif
-#ifndef AMDAT_SMALL_PX_PF      // CU-wide prefilter workgroups below this
-#define AMDAT_SMALL_PX_PF AMDAT_SMALL_PX
-#endif
-static inline bool small_submission(const amdAprilTagsDetector_st* D, const DetParams& P, uint32_t n, uint64_t limit = AMDAT_SMALL_PX) {
-  if (D->path_mode != AMDAT_PATH_AUTO) return D->path_mode == AMDAT_PATH_LATENCY;
-  return (uint64_t)n * (uint64_t)P.W * (uint64_t)P.H < limit;
-}
-// the frame count the launch heuristics see (chunks of k_cluster_select, clusters per pop): a pinned path takes the values of
-// the submissions that path is for, whatever the real count
-static inline uint32_t heuristic_frames(const amdAprilTagsDetector_st* D, uint32_t n) {
-  if (D->path_mode == AMDAT_PATH_THROUGHPUT) return n < 64u ? 64u : n;
-  if (D->path_mode == AMDAT_PATH_LATENCY) return n > 8u ? 8u : n;
-  return n;
-}
-
+// Enqueues the stage sequence of plan_launch (launch_plan.h) for batch slots [0, n) on stream s.  mark() is called between stages
+// (event timing when profiling).
 static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride, hipStream_t s, uint32_t fmt, const std::function<void()>& mark) {
   DetParams P = D->P;
   P.frame0 = 0;
+  const LaunchPlan plan = plan_launch(D->fq, n, P.W, P.H, P.hcap, D->path_mode, (unsigned)D->num_cus, FQ_SOUND_EXIT_PREFILTER);
   launch_threshold(D, P, n, s, fmt, D->qs_ksz > 1);
   mark();
-#ifndef AMDAT_CC_WIDE
-#define AMDAT_CC_WIDE 1
-#endif
-  if (AMDAT_CC_WIDE && small_submission(D, P, n, AMDAT_SMALL_PX_CC))   // sixteen waves per tile: a quarter of the rows per lane (latency, not throughput)
-    hipLaunchKernelGGL((k_cc_local<16>), dim3((P.W + CC_T - 1) / CC_T, (P.H + CC_T - 1) / CC_T, n), dim3(1024), 0, s, D->d_thr,
-                     D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, P);
-  else
-    hipLaunchKernelGGL((k_cc_local<4>), dim3((P.W + CC_T - 1) / CC_T, (P.H + CC_T - 1) / CC_T, n), dim3(256), 0, s, D->d_thr,
-                     D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, P);
+  {
+    const dim3 grid((P.W + CC_T - 1) / CC_T, (P.H + CC_T - 1) / CC_T, n);
+    if (plan.cc_waves == 16)
+      hipLaunchKernelGGL((k_cc_local<16>), grid, dim3(1024), 0, s, D->d_thr, D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, P);
+    else
+      hipLaunchKernelGGL((k_cc_local<4>), grid, dim3(256), 0, s, D->d_thr, D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, P);
+  }
   mark();
   {
     const int nrows = (P.H - 1) / CC_T, ncols = (P.W - 1) / CC_T;
@@ -1202,203 +1093,73 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
     if (total > 0) {
 #define BORDER_ARGS dim3((unsigned)((total + 255) / 256) * n), dim3(256), 0, s, D->d_perim, D->d_label, D->d_roots, D->d_counters,   \
                     (uint32_t)((total + 255) / 256), n, P
-#ifndef AMDAT_BORDER_PER_WAVE
-#define AMDAT_BORDER_PER_WAVE 1
-#endif
-      if (!AMDAT_BORDER_PER_WAVE || small_submission(D, P, n)) hipLaunchKernelGGL((k_cc_border<false>), BORDER_ARGS);   // (one list append per block)
-      else hipLaunchKernelGGL((k_cc_border<true>), BORDER_ARGS);                               // (per wave, no barriers)
+      if (plan.border_per_wave) hipLaunchKernelGGL((k_cc_border<true>), BORDER_ARGS);
+      else hipLaunchKernelGGL((k_cc_border<false>), BORDER_ARGS);
 #undef BORDER_ARGS
     }
   }
   mark();
-  {
-    unsigned gr = (unsigned)(((size_t)P.W * P.H / 16 + 255) / 256);
-    if (gr < 1) gr = 1;
-#ifndef AMDAT_CC_ROOT_GRID
-#define AMDAT_CC_ROOT_GRID 1024
-#endif
-    if (gr > AMDAT_CC_ROOT_GRID) gr = AMDAT_CC_ROOT_GRID;
-    hipLaunchKernelGGL(k_cc_sizes, dim3(gr, 1, n), dim3(256), 0, s, D->d_label, D->d_csize, D->d_roots, D->d_counters, P);
-    hipLaunchKernelGGL(k_cc_resolve, dim3(gr, 1, n), dim3(256), 0, s, D->d_label, D->d_csize, D->d_roots, D->d_counters, P);
-  }
+  hipLaunchKernelGGL(k_cc_sizes, dim3(plan.cc_root_grid, 1, n), dim3(256), 0, s, D->d_label, D->d_csize, D->d_roots, D->d_counters, P);
+  hipLaunchKernelGGL(k_cc_resolve, dim3(plan.cc_root_grid, 1, n), dim3(256), 0, s, D->d_label, D->d_csize, D->d_roots, D->d_counters, P);
   mark();
-  {
-    const uint32_t gxt = (uint32_t)((P.W + PT_TW - 1) / PT_TW), gyt = (uint32_t)((P.H + PT_TH - 1) / PT_TH);
-    hipLaunchKernelGGL(k_points, dim3(gxt * gyt * n), dim3(256), 0, s, D->d_thr, D->d_label, D->d_hkeys, D->d_hcnt,
-                       D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_counters, (D->fq_counters ? D->d_ptprof : nullptr), gxt, gyt, n, P);
-  }
+  const uint32_t gxt = (uint32_t)((P.W + PT_TW - 1) / PT_TW), gyt = (uint32_t)((P.H + PT_TH - 1) / PT_TH);
+  hipLaunchKernelGGL(k_points, dim3(gxt * gyt * n), dim3(256), 0, s, D->d_thr, D->d_label, D->d_hkeys, D->d_hcnt,
+                     D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_counters, (D->fq_counters ? D->d_ptprof : nullptr), gxt, gyt, n, P);
   mark();
-  {
-    const int nchunks = heuristic_frames(D, n) >= 16 ? SEL_CHUNKS : 1;   // (see the kernel)
-    hipLaunchKernelGGL(k_cluster_select, dim3((P.hcap + 1024 * nchunks - 1) / (1024 * nchunks), 1, n), dim3(256), 0, s, D->d_hkeys,
-                       D->d_hcnt, D->d_hoff, D->d_clusters, D->d_counters, D->d_work, D->d_workctl,
-                       small_submission(D, P, n) ? D->work_layout_small : D->work_layout, nchunks, P);
-  }
+  const FqWorkLayout& L = D->work_layout.all;
+  hipLaunchKernelGGL(k_cluster_select, dim3(plan.select_grid, 1, n), dim3(256), 0, s, D->d_hkeys, D->d_hcnt, D->d_hoff, D->d_clusters,
+                     D->d_counters, D->d_work, D->d_workctl, plan.latency ? D->work_layout.latency : L, plan.select_chunks, P);
   mark();
-  {
-    const uint32_t gxt = (uint32_t)((P.W + PT_TW - 1) / PT_TW), gyt = (uint32_t)((P.H + PT_TH - 1) / PT_TH);
-    hipLaunchKernelGGL(k_scatter, dim3((gxt * gyt + 3) / 4, 1, n), dim3(256), 0, s, D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_hoff, D->d_pts,
-                       D->d_counters, gxt, gyt, P);
-  }
+  hipLaunchKernelGGL(k_scatter, dim3((gxt * gyt + 3) / 4, 1, n), dim3(256), 0, s, D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_hoff, D->d_pts,
+                     D->d_counters, gxt, gyt, P);
   mark();
   {
     // keys | pair-table region
     // skewed key array (later: errors, candidates, pair tables) | group prefixes of the early-exit test (not in the one-wave class)
-    auto lds_bytes = [](const FqClass& c) { return FQ_KEY_BYTES(c.sort_cap) + (c.nt > 64 ? (size_t)FQ_TABLE_DOUBLES * 8 : 0); };
-
-    // The classes are independent (they only append to the quad list).  Every class's persistent grid can fill the
-    // chip's register file by itself, so whichever workgroups are placed first stay until their list is empty, and the
-    // stage is work-conserving whatever the order of the three small classes (17.97 - 18.34 ms over five stream
-    // assignments).  The two large classes are different: their workgroups only find room on (half-)empty CUs.  Next
-    // to the small classes they were placed last and ran at the end of the stage at a quarter of the chip's
-    // occupancy, so a throughput-sized submission runs them first, one after the other on the submission stream, and
-    // the small classes start when both are done: 16.9 -> 15.8 ms.  (Queuing the largest class on a stream of its own
-    // next to the second one cost 0.9 ms: its queue sat stalled until the scheduler looked at it again.)
-    // A small submission is about latency: all classes start together.
-    // cheap exits of the large classes (bounding box, border direction, sector test) at full occupancy, ahead of their
-    // persistent workgroups, which pop the survivors from the compact lists it writes (d_work2, counts at d_workctl + 16)
-    const bool prefilter = FQ_SOUND_EXIT_PREFILTER && P.max_cluster_points > D->cls[D->prefilter_class].lo && D->d_work2;   // (tools_hooks.h: 1)
-    uint32_t* const work2 = D->d_work2 ? D->d_work2 - D->work_layout.off[D->prefilter_class] : nullptr;   // (indexed with the common layout)
-    // A small submission (the node's one-frame calls) is over when its slowest chain is: there the 256-thread class starts
-    // at once beside the small classes (its in-kernel test after the first walk still drops most of its clusters) and
-    // only the two largest classes wait for the prefilter -- prefilter, then the survivors' sort, was the longest chain.
-    const bool small = small_submission(D, P, n);
-    const int pf_first = small ? D->prefilter_class + 1 : D->prefilter_class;
-    auto launch_prefilter = [&](hipStream_t sp) {
-      if (!prefilter) return;
-      if (FQ_SKIP_PREFILTER()) return;   // (tools_hooks.h: always 0 in the product build)
-      // small submissions: one cluster per CU-wide workgroup (latency); otherwise one per wave (throughput)
-      const bool wide = small_submission(D, P, n, AMDAT_SMALL_PX_PF);
+    auto lds_bytes = [](const FqClassSpec& c) { return FQ_KEY_BYTES(c.sort_cap) + (c.nt > 64 ? (size_t)FQ_TABLE_DOUBLES * 8 : 0); };
+    // the prefilter's compact lists (d_work2, counts at d_workctl + 16), indexed with the common layout
+    uint32_t* const work2 = D->d_work2 - L.off[D->fq.prefilter_class];
+    const hipStream_t* aux = D->aux_stream;
+    for (int i = 0; i < plan.nsteps; i++) {
+      const FitStep& st = plan.steps[i];
+      const hipStream_t sc = st.stream == FIT_MAIN ? s : aux[st.stream];
+      const dim3 grid(st.grid);
+      if (st.kind == FIT_FORK) {
+        HIP_TRY(hipEventRecord(D->ev_fork, s));
+        for (int a = 0; a < FQ_NAUX; a++) HIP_TRY(hipStreamWaitEvent(aux[a], D->ev_fork, 0));
+      } else if (st.kind == FIT_PREFILTER) {
+        if (FQ_SKIP_PREFILTER()) continue;   // (tools_hooks.h: always 0 in the product build)
 #define PF_ARGS D->d_frames, D->d_gray, D->d_pts, D->d_clusters, D->d_work, D->d_workctl, work2, D->d_workctl + 16, D->d_workctl + 24,   \
-                D->work_layout, pf_first, (D->fq_counters ? D->d_fqprof : nullptr), P
-      if (wide) {
-        unsigned gp = 2u * (unsigned)D->num_cus;
-        if (gp > 256u * n) gp = 256u * n;
-        hipLaunchKernelGGL(k_fit_prefilter<1024>, dim3(gp), dim3(1024), 0, sp, PF_ARGS);
-      } else {
-        unsigned gp = 32u * (unsigned)D->num_cus;
-        if (gp > 256u * n) gp = 256u * n;
-        hipLaunchKernelGGL(k_fit_prefilter<64>, dim3(gp), dim3(64), 0, sp, PF_ARGS);
-      }
+                L, plan.prefilter_first, (D->fq_counters ? D->d_fqprof : nullptr), P
+        if (plan.prefilter_nt == 1024) hipLaunchKernelGGL(k_fit_prefilter<1024>, grid, dim3(1024), 0, sc, PF_ARGS);
+        else hipLaunchKernelGGL(k_fit_prefilter<64>, grid, dim3(64), 0, sc, PF_ARGS);
 #undef PF_ARGS
-    };
-    auto launch_class = [&](int c, hipStream_t sc) -> bool {   // false: the class has no clusters on this handle, nothing was launched
-      const FqClass& cl = D->cls[c];
-      // (working images so small that no cluster can exceed the k_fit_small classes' bound -- 3 (2 W + 2 H) <= 128 -- still need the
-      // one-wave class on the latency set, where it takes everything from 24 points on; found by the fuzzer in round 5: a 9 x 8
-      // working image whose only cluster, 34 points, was bucketed into a list no kernel was launched for)
-      const int lo_eff = (small && c == FQ_C0) ? 23 : cl.lo;
-      if (P.max_cluster_points <= lo_eff || cl.hi <= cl.lo || (!cl.small_k && !cl.d_lf)) return false;
-      if (small && cl.small_k) return false;   // (their clusters are in the one-wave class's list: work_layout_small)
-      if (FQ_SKIP_CLASS(c)) return false;   // (tools_hooks.h: always 0 in the product build)
-#ifndef AMDAT_SMALL_GRID64
-#define AMDAT_SMALL_GRID64 8   // workgroups per CU of the one-wave class on the latency set (0: the handle's grid)
-#endif
-#ifndef AMDAT_SMALL_GRID128
-#define AMDAT_SMALL_GRID128 2
-#endif
-      // (latency set: the one-wave class's sixteen workgroups per CU -- the throughput grid -- leave the 128- and 256-thread classes'
-      // workgroups waiting for slots; eight per CU: one 1080p frame 0.395 -> 0.383 ms, four 0.682 -> 0.650, eight 1.028 -> 1.00;
-      // six: the same; four: 0.397 / 0.723 / 1.12)
-      unsigned gsz = cl.grid;
-      if (AMDAT_SMALL_GRID64 && small && c == FQ_C0 && gsz > (unsigned)AMDAT_SMALL_GRID64 * (unsigned)D->num_cus) gsz = (unsigned)AMDAT_SMALL_GRID64 * (unsigned)D->num_cus;
-#ifndef AMDAT_SMALL_GRID256
-#define AMDAT_SMALL_GRID256 1
-#endif
-      if (AMDAT_SMALL_GRID256 && small && c == FQ_C0 + 2 && gsz > (unsigned)AMDAT_SMALL_GRID256 * (unsigned)D->num_cus) gsz = (unsigned)AMDAT_SMALL_GRID256 * (unsigned)D->num_cus;
-      if (AMDAT_SMALL_GRID128 && small && c == FQ_C0 + 1 && gsz > (unsigned)AMDAT_SMALL_GRID128 * (unsigned)D->num_cus) gsz = (unsigned)AMDAT_SMALL_GRID128 * (unsigned)D->num_cus;
-      const dim3 grid(gsz);   // (a submission of n < max_batch frames still gets the handle's persistent grid)
-      const size_t lds = lds_bytes(cl);
-      const bool big = c == FQ_NCLS - 1;
-      // a small submission spreads its clusters over the workgroups one by one (latency); large ones pop in chunks
-      const int nh16 = (int)(heuristic_frames(D, n) / 16u);
-      const int pop = cl.pop < nh16 ? cl.pop : (nh16 < 1 ? 1 : nh16);
-      const bool filtered = prefilter && c >= pf_first;
-      if (cl.small_k) {
-#define FS_ARGS D->d_frames, D->d_gray, D->d_pts, D->d_clusters, D->d_work + D->work_layout.off[c], D->d_workctl + c,               \
-                D->work_layout.cap[c], D->d_workctl + 8 + c, cl.d_lf, D->d_cands, D->d_counters, pop, P
-        if (cl.small_k == 2) hipLaunchKernelGGL((k_fit_small<2, false>), grid, dim3(64), FS_LDS_BYTES(2, false), sc, FS_ARGS);
-        else hipLaunchKernelGGL((k_fit_small<4, FS_K4_GROWS>), grid, dim3(64), FS_LDS_BYTES(4, FS_K4_GROWS), sc, FS_ARGS);
-#undef FS_ARGS
-        return true;
-      }
-#define FQ_ARGS D->d_frames, D->d_gray, D->d_pts, D->d_clusters, (filtered ? work2 : D->d_work) + D->work_layout.off[c],                 \
-                D->d_workctl + (filtered ? 16 : 0) + c,                                                                                \
-                D->work_layout.cap[c], D->d_workctl + 8 + c, cl.d_lf, (big ? D->d_keys_scr : nullptr), cl.d_errs,                        \
-                D->d_cands, D->d_counters, (D->fq_counters ? D->d_fqprof + 8 * (c - FQ_C0) : nullptr), cl.sort_cap, cl.slot_cap, pop, P
+      } else {
+        const int c = st.cls;
+        if (FQ_SKIP_CLASS(c)) continue;   // (tools_hooks.h: always 0 in the product build)
+        const FqClassSpec& cl = D->fq.cls[c];
+        const FqScratch& scr = D->fq_scratch[c];
+        if (cl.kernel == FQ_SMALL) {
+          hipLaunchKernelGGL(k_fit_small<2>, grid, dim3(64), FS_LDS_BYTES(2), sc, D->d_frames, D->d_gray, D->d_pts, D->d_clusters,
+                             D->d_work + L.off[c], D->d_workctl + c, L.cap[c], D->d_workctl + 8 + c, (double*)nullptr, D->d_cands, D->d_counters, st.pop, P);
+          continue;
+        }
+        const size_t lds = lds_bytes(cl);
+#define FQ_ARGS D->d_frames, D->d_gray, D->d_pts, D->d_clusters, (st.compact ? work2 : D->d_work) + L.off[c],                       \
+                D->d_workctl + (st.compact ? 16 : 0) + c, L.cap[c], D->d_workctl + 8 + c, scr.d_lf,                                \
+                (c == FQ_NCLS - 1 ? D->d_keys_scr : nullptr), scr.d_errs, D->d_cands, D->d_counters,                               \
+                (D->fq_counters ? D->d_fqprof + 8 * (c - FQ_C0) : nullptr), cl.sort_cap, cl.slot_cap, st.pop, P
 #define FQ_LAUNCH(NTV)                                                                                          \
   if (P.split_moments) hipLaunchKernelGGL((k_fit_quads<NTV, true>), grid, dim3(NTV), lds, sc, FQ_ARGS);          \
   else hipLaunchKernelGGL((k_fit_quads<NTV, false>), grid, dim3(NTV), lds, sc, FQ_ARGS);
-      if (cl.nt == 64) { FQ_LAUNCH(64) }
-      else if (cl.nt == 128) { FQ_LAUNCH(128) }
-      else if (cl.nt == 256) { FQ_LAUNCH(256) }
-      else if (cl.nt == 512) { FQ_LAUNCH(512) }
-      else { FQ_LAUNCH(FQ_NT_BIG) }
+        if (cl.nt == 64) { FQ_LAUNCH(64) }
+        else if (cl.nt == 128) { FQ_LAUNCH(128) }
+        else if (cl.nt == 256) { FQ_LAUNCH(256) }
+        else if (cl.nt == 512) { FQ_LAUNCH(512) }
+        else { FQ_LAUNCH(FQ_NT_BIG) }
 #undef FQ_LAUNCH
 #undef FQ_ARGS
-      return true;
-    };
-    hipStream_t* aux = D->aux_stream;
-    // (throughput-sized: from about 32 1080p working images on; below that the two extra dependent launches cost more
-    // than the placement gains -- 64 half-resolution frames measured 3.00 vs 2.88 ms)
-#ifndef AMDAT_FQ_ORDER
-#define AMDAT_FQ_ORDER 0
-#endif
-    const bool large_first = AMDAT_FQ_ORDER != 2 && (uint64_t)n * (uint64_t)P.W * (uint64_t)P.H >= (64ull << 20);
-    HIP_TRY(hipEventRecord(D->ev_fork, s));
-    if (prefilter) {
-      // The prefilter runs first and alone (a fraction of a millisecond at full occupancy; started beside the small classes
-      // it starved behind their persistent workgroups and finished last).  Then everything starts together: the large
-      // classes first on the submission stream -- they find only the prefilter's few survivors in their lists and are gone
-      // before the small classes have filled the chip -- and the two small classes on side streams, the 128-thread class
-      // (the longest chain) first.
-      // A small submission leaves most of the chip empty either way: its classes below the prefilter start at once on the
-      // side streams, beside the prefilter.
-      if (!small) launch_prefilter(s);
-      // The two largest classes need (half) a CU's LDS per workgroup: queued beside the small classes' persistent grids they found no
-      // room until those drained -- the 1024-thread class, 15 us of work, sat behind k_fit_small for 1.4 ms whenever it lost that race
-      // (profiles/r05_v4_fit_timeline.txt) -- so a throughput-sized submission runs them right behind the prefilter, on the empty
-      // chip, and everything else starts when they are through (their lists hold the prefilter's few survivors).
-#ifndef AMDAT_BIG_FIRST
-#define AMDAT_BIG_FIRST 1
-#endif
-      const int big_first = (!small && AMDAT_BIG_FIRST) ? pf_first + 1 : FQ_NCLS;
-      for (int c = big_first; c < FQ_NCLS; c++) launch_class(c, s);
-      HIP_TRY(hipEventRecord(D->ev_fork, s));
-      for (int a = 0; a < FQ_NAUX; a++) HIP_TRY(hipStreamWaitEvent(aux[a], D->ev_fork, 0));
-      if (small) launch_prefilter(s);
-      for (int c = pf_first; c < big_first; c++) launch_class(c, s);   // (nearly all survivors are in the first of them)
-      // the longest chains first; classes that launch nothing take no stream.  (The one-wave class on the submission stream itself,
-      // so that it starts without the 60 .. 90 us the fork event takes to reach a side stream -- measured with the wall clock inside
-      // the kernels -- cost 0.5 ms: its persistent grid then holds the chip before the 128-thread class is placed, which ends up
-      // running last and alone.)
-      // (holding the shorter-chained classes of a small submission back a few microseconds with a one-wave wait kernel ahead of
-      // them, to get on plain streams -- a captured graph -- the placement order stream priorities give, measured nothing: 0.395 vs
-      // 0.395 ms for one frame, 1.055 vs 1.065 for eight.  Priorities act on every slot that frees up, not on the first placement.)
-      int a = 0;
-      for (int c = pf_first - 1; c >= 0; c--)
-        if (launch_class(c, aux[a < FQ_NAUX ? a : FQ_NAUX - 1])) a++;   // (a fourth class queues behind the third: the two k_fit_small classes)
-    } else {
-    if (large_first) {
-      launch_class(FQ_C0 + 3, s);
-      launch_class(FQ_C0 + 4, s);
-      if (AMDAT_FQ_ORDER == 1) launch_class(FQ_C0 + 2, s);
-      HIP_TRY(hipEventRecord(D->ev_fork, s));   // both large classes are done
-    }
-    for (int a = 0; a < FQ_NAUX; a++) HIP_TRY(hipStreamWaitEvent(aux[a], D->ev_fork, 0));
-    // (which small class shares the chip with which was measured over seven assignments: 16.0 - 16.9 ms; best when
-    // the 256-thread class is the one that ends up running last)
-    if (large_first) {
-      for (int c = 0, a2 = 0; c < FQ_C0 + (AMDAT_FQ_ORDER == 1 ? 2 : 3); c++) if (launch_class(c, aux[a2 % FQ_NAUX])) a2++;
-    } else {   // the longest chains side by side: the largest clusters | 4096..8192 then the one-wave class | the other two
-      launch_class(FQ_C0 + 4, s);
-      launch_class(FQ_C0 + 3, aux[0]);
-      launch_class(FQ_C0 + 2, aux[1]);
-      launch_class(FQ_C0 + 1, aux[2]);
-      launch_class(FQ_C0 + 0, aux[0]);
-      launch_class(1, aux[1]);
-      launch_class(0, aux[2]);
-    }
+      }
     }
     for (int a = 0; a < FQ_NAUX; a++) {
       HIP_TRY(hipEventRecord(D->ev_join[a], aux[a]));
@@ -1408,17 +1169,10 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
     hipLaunchKernelGGL(k_quad_finish, dim3(16, n), dim3(256), 0, s, D->d_cands, D->d_quads, D->d_counters, P);
   }
   mark();
-  {
-    unsigned gq = 2048u / n;
-    if (gq < 96u) gq = 96u;   // about one wave per candidate quad of a noisy frame (16 per frame measured 0.36 ms slower)
-    if (gq > 256u) gq = 256u;
-    hipLaunchKernelGGL(k_decode_wave, dim3(gq, n), dim3(64), 0, s, D->d_frames, D->d_quads, D->d_dets, D->d_counters, P);
-  }
+  hipLaunchKernelGGL(k_decode_wave, dim3(plan.decode_grid, n), dim3(64), 0, s, D->d_frames, D->d_quads, D->d_dets, D->d_counters, P);
   mark();
-  {
-    hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
-                       D->h_counters, P);
-  }
+  hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
+                     D->h_counters, P);
   mark();
   return AMDAT_SUCCESS;
 }
@@ -1454,15 +1208,13 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
 // device-wide wait and with no capture behind them -- re-capturing on regrown buffers is clean (tools/stress_regrow.py with
 // replay kept: 15 of 15 runs of 150 handles; with hipGraphExecDestroy at the regrowth: 11 of 12 runs die), so a regrown handle
 // keeps graph replay: the next submission of each shape is captured again on the new buffers.  The list is bounded: beyond
-// AMDAT_MAX_RETIRED_GRAPHS the handle stops capturing new graphs (plain enqueues for the submission shapes it has no graph for;
+// kMaxRetiredGraphs the handle stops capturing new graphs (plain enqueues for the submission shapes it has no graph for;
 // it says so once on stderr and through amdAprilTagsDebugGraphReplay).
-#ifndef AMDAT_MAX_RETIRED_GRAPHS
-#define AMDAT_MAX_RETIRED_GRAPHS 24
-#endif
+constexpr size_t kMaxRetiredGraphs = 24;
 static void retire_graph(amdAprilTagsDetector_st* D, amdAprilTagsDetector_st::GraphEntry& g) {
   if (!g.exec) return;
   D->retired_graphs.push_back(g.exec);
-  if (D->retired_graphs.size() > AMDAT_MAX_RETIRED_GRAPHS && D->graph_max_frames) {
+  if (D->retired_graphs.size() > kMaxRetiredGraphs && D->graph_max_frames) {
     D->graph_max_frames = 0;   // (the live cache entries keep replaying; nothing new is captured)
     fprintf(stderr, "[apriltag_amd] handle %p: %zu retired launch graphs -- no new graphs are captured from here on (plain enqueues "
                     "for submission shapes without one)\n", (void*)D, D->retired_graphs.size());
@@ -1670,7 +1422,7 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   { const int crc = ensure_colour_plane(D, fmt, filt); if (crc) return crc; }
   fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
   D->last_n = n;
-  D->last_path = small_submission(D, D->P, n) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
+  D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
     D->pending_hash_grow = false;

@@ -15,6 +15,7 @@
 //                     cluster is fixed later by the slope sort, so arrival order never shows).
 #pragma once
 #include "common.h"
+#include "launch_plan.h"   // FqWorkLayout, FQ_NCLS
 
 #define PT_TW 64
 #define PT_TH 16
@@ -154,10 +155,7 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
   // below: no per-entry bounds tests, row addresses as a uniform base plus the lane's offset (the general form pays two 64-bit
   // multiply-adds per entry), the halo column with wave 1 and row 16 with wave 0 (five entries per thread instead of six in the
   // wave the barrier waits for).
-#ifndef PT_INTERIOR
-#define PT_INTERIOR 1
-#endif
-  const bool interior = PT_INTERIOR && bx_ >= 1 && by_ >= 1 && X0 + PT_TW + 1 <= W && Y0 + PT_TH + 1 <= H;
+  const bool interior = bx_ >= 1 && by_ >= 1 && X0 + PT_TW + 1 <= W && Y0 + PT_TH + 1 <= H;
   if (interior) {
     const int lane_ = tid & 63;
     const int wvu = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -359,7 +357,6 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
     const uint64_t key = ((uint64_t)min(r0, r1) << 32) | max(r0, r1);
     const int e = ltab_insert(tkey, key);
     uint32_t ee = 255u, rk = 0u;
-#ifndef PT_NO_LEADER_ADD
     // Most emissions of a wave's trip belong to ONE pair (the background's two big components meet in almost every tile):
     // 64 lanes adding 1 to the same counter serialise in the LDS pipeline (the kernel's "bank conflicts" are these
     // same-address atomics).  The lanes that share the first active lane's entry take their ranks from ONE add of their
@@ -374,9 +371,7 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
       gbase = (uint32_t)__builtin_amdgcn_readlane((int)gbase, leader);
       ee = (uint32_t)e;
       rk = gbase + (uint32_t)__popcll(gm & ((1ull << (tid & 63)) - 1ull));
-    } else
-#endif
-    if (e >= 0 && e < 255) { ee = (uint32_t)e; rk = atomicAdd(&tcnt[e], 1u); }
+    } else if (e >= 0 && e < 255) { ee = (uint32_t)e; rk = atomicAdd(&tcnt[e], 1u); }
     if (ee != 255u) {
       // (pixel | direction << 10 of the list record are the word's bits 19..30 as they stand; value step v1 - v0 = +-255: bit 31
       // set when it is negative, v0 white.  Written once, read once by k_scatter two kernels later: non-temporal stores keep it
@@ -387,18 +382,13 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
   }
   PT_TICK(3)
   PT_STOP_AT(3, stage_all[(size_t)frame * P.pcap + (blk_ % 64u) * 256 + tid] = emask ^ off ^ elist[tid] ^ sbase)
-#ifndef PT_EARLY_PROBE
-#define PT_EARLY_PROBE 1
-#endif
   // The frame-table phase at the end of the block is a chain of two or three dependent round trips to the memory side per table
   // entry (0.37 ms of the kernel: a build that stops before it).  Its first one -- the load of the key's home slot -- is issued
   // HERE, as soon as this wave is through its share of the list, for the entry the thread will own (other waves may still add
   // entries: those are probed at the end as before), and is in flight while the wave waits at the barrier below.
-  unsigned long long pf_key = AT_EMPTY_KEY, pf_cur = 0;
-  if (PT_EARLY_PROBE) {
-    pf_key = __hip_atomic_load(&tkey[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (pf_key != AT_EMPTY_KEY) pf_cur = __hip_atomic_load(&hkeys[hash_slot(pf_key, P.hshift)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const unsigned long long pf_key = __hip_atomic_load(&tkey[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  unsigned long long pf_cur = 0;
+  if (pf_key != AT_EMPTY_KEY) pf_cur = __hip_atomic_load(&hkeys[hash_slot(pf_key, P.hshift)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (off + cnt > PT_ELIST) {   // this thread's emissions beyond the list
     uint32_t q = off, m = emask;
     while (m) {
@@ -411,13 +401,9 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
   // the block table's counts are complete.  (An LDS-only barrier: nothing global is handed from thread to thread across it, and
   // __syncthreads' fence would wait for the probe above -- every outstanding global access -- in front of the barrier, in the
   // wave that arrives last as in the others.)
-  if (PT_EARLY_PROBE) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  } else {
-    __syncthreads();
-  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
   PT_TICK(4)
   PT_STOP_AT(5, (void)0)
   {
@@ -428,8 +414,8 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
     // behind a barrier: 0.8 ms of the kernel).
     const unsigned long long key = tkey[tid];
     if (key != AT_EMPTY_KEY) {
-      const uint32_t slot = (PT_EARLY_PROBE && key == pf_key) ? hash_insert_probed(hkeys, P.hcap, P.hshift, key, pf_cur)
-                                                              : hash_insert(hkeys, P.hcap, P.hshift, key);
+      const uint32_t slot = key == pf_key ? hash_insert_probed(hkeys, P.hcap, P.hshift, key, pf_cur)
+                                          : hash_insert(hkeys, P.hcap, P.hshift, key);
       uint32_t kbase = 0;
       if (slot != AT_INVALID_SLOT) kbase = atomicAdd(&hcnt[slot], tcnt[tid]);
       else atomicOr(&counters[frame].flags, 0x2u);
@@ -443,13 +429,7 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
 // Work lists of the quad fit: the kept clusters of all frames of the submission, bucketed by size class
 // (class c holds lo[c] < count <= hi[c]).  An item is (frame << P.wshift) | cluster index (wshift >= 16: DetParams).  k_cluster_select appends them as it
 // creates the cluster records; appends are aggregated per block in LDS, so every class counter sees one global atomic per
-// block.  (A separate k_worklist pass over the records cost a launch and a round trip through them.)
-#define FQ_NCLS 7
-#define FQ_C0 2     // classes 0 .. FQ_C0 - 1: k_fit_small (K = 2, 4); FQ_C0 ..: k_fit_quads (64 ... 1024 threads)
-struct FqWorkLayout {
-  int lo[FQ_NCLS], hi[FQ_NCLS];
-  uint32_t off[FQ_NCLS], cap[FQ_NCLS];   // item range of class c inside the work array
-};
+// block.  (A separate k_worklist pass over the records cost a launch and a round trip through them.)  The layouts: launch_plan.h.
 
 // One thread per four pair-table slots, SEL_CHUNKS chunks of 1024 slots per block (`nchunks` of them used: a large submission
 // takes all four, so that the shared class counters of the work lists see a quarter of the blocks' atomics -- every
@@ -569,10 +549,6 @@ __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ st
   const uint2* btab = btab_all + ((size_t)frame * bpf + blk) * PT_TB;
   const uint32_t* stage = stage_all + (size_t)frame * P.pcap + hdr.x;
   const int X0 = (int)(blk % gx_tiles) * PT_TW, Y0 = (int)(blk / gx_tiles) * PT_TH;
-#ifndef SC_LDS_TABLE
-#define SC_LDS_TABLE 1
-#endif
-#if SC_LDS_TABLE
   // The tile's pair table is resolved ONCE per wave into LDS -- entry -> first position of the tile's points of that pair in the
   // cluster's range, hoff[slot] + base rank -- so a record is one load (its staging word), one LDS read and one store; with the
   // table entry and the range start fetched per record it was three dependent loads.  All 256 entries are resolved: which of them
@@ -614,35 +590,6 @@ __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ st
                                           ((uint32_t)(ddx * sgn + 1) << 2) | (uint32_t)(ddy * sgn + 1);
     }
   }
-#else
-  // Three dependent loads per record (staging word -> table entry -> range start).  A tile has a few records per thread:
-  // they are taken SC_U at a time, level by level, so that the latencies of a thread's records overlap instead of adding up.
-  for (uint32_t i0 = lane; i0 < hdr.y; i0 += SC_U * 64) {
-    uint32_t w[SC_U], off[SC_U];
-    uint2 tb[SC_U];
-#pragma unroll
-    for (int u = 0; u < SC_U; u++) {
-      const uint32_t i = i0 + (uint32_t)u * 64u;
-      w[u] = i < hdr.y ? __builtin_nontemporal_load(stage + i) : 0xFFFFFFFFu;
-    }
-#pragma unroll
-    for (int u = 0; u < SC_U; u++) tb[u] = (w[u] & 255u) != 255u ? btab[w[u] & 255u] : make_uint2(AT_INVALID_SLOT, 0u);
-#pragma unroll
-    for (int u = 0; u < SC_U; u++) off[u] = tb[u].x != AT_INVALID_SLOT ? hoff[tb[u].x] : AT_INVALID_SLOT;
-#pragma unroll
-    for (int u = 0; u < SC_U; u++) {
-      if (off[u] == AT_INVALID_SLOT) continue;
-      const uint32_t pix = (w[u] >> 19) & 1023u;
-      const int ly = (int)(pix >> 6), plx = (int)(pix & 63u), d = (int)((w[u] >> 29) & 3u);
-      const int ddx = (d == 2) ? -1 : (d == 1 ? 0 : 1), ddy = (d == 0) ? 0 : 1;
-      // packed point = x << 18 | y << 4 | (sign of gx + 1) << 2 | (sign of gy + 1), the gradient (dx, dy) * (+-255): pack_point
-      // without its divisions by 255
-      const int sgn = (w[u] >> 31) ? -1 : 1;
-      pts[off[u] + tb[u].y + ((w[u] >> 8) & 2047u)] = ((uint32_t)(2 * (X0 + plx) + ddx) << 18) | ((uint32_t)(2 * (Y0 + ly) + ddy) << 4) |
-                                                       ((uint32_t)(ddx * sgn + 1) << 2) | (uint32_t)(ddy * sgn + 1);
-    }
-  }
-#endif
   uint32_t nl = counters[frame].nlong;
   if (nl > P.lcap) nl = P.lcap;
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nl; i += gridDim.x * 256) {

@@ -23,6 +23,7 @@
 // The product build carries neither.
 #pragma once
 #include "common.h"
+#include "launch_plan.h"   // FqWorkLayout, FQ_NCLS, FQ_NT_BIG
 #include "tools_hooks.h"
 
 
@@ -296,13 +297,10 @@ __device__ __forceinline__ void fit_line_dev(const double* lf, int sz, int i0, i
 // test rejects with 64 groups, 68 % with 32 (tools/early_exit_power.py, CPU restatement); the one-wave class (up to
 // 768 points) gains nothing from it and does not run it.
 #define FQ_XG 32
-// The pre-sort sector test runs in k_fit_prefilter for the clusters above 2048 points.  (Inside k_fit_quads --
-// kept for comparison builds, -DFQ_PRESORT_MIN_NT=256 -- the large classes paid for it with one or two workgroups per CU;
-// the 128-thread class gains nothing from it either way: 7 % of its points rejected for 27 % of its cycles, its clusters
-// are small against the 64 x 16 tiles the points arrive in, so the sector changes at almost every point.)
-#ifndef FQ_PRESORT_MIN_NT
-#define FQ_PRESORT_MIN_NT (1 << 20)
-#endif
+// The pre-sort sector test runs in k_fit_prefilter for the clusters above 2048 points.  (Inside k_fit_quads the large classes
+// paid for it with one or two workgroups per CU; the 128-thread class gains nothing from it either way: 7 % of its points rejected
+// for 27 % of its cycles, its clusters are small against the 64 x 16 tiles the points arrive in, so the sector changes at almost
+// every point.)
 // Moments m = hi - lo (+ add) of the groups strictly between two cuts; returns false only if lambda_min of their scatter
 // certainly exceeds thr * Wc.  Division- and root-free: with W = m5, A = W m2 - m0^2, B = W m3 - m0 m1, C = W m4 - m1^2 (W times
 // the scatter matrix) and c = thr * Wc, both eigenvalues of the scatter exceed c exactly when (A - cW) + (C - cW) > 0 and
@@ -383,18 +381,10 @@ __device__ __forceinline__ bool fq_feasible(const double* sP, double mse_limit, 
 // (1,1) point of one pixel and the (-1,1) point of its right neighbour); both copies carry the same weight and fall
 // into the same sector, so entering every odd-odd point with HALF its weight keeps the scatter of any union of
 // sectors below that of its duplicate-free points, line by line; the weight bound takes every point in full.
-// 32 sectors, eight per quadrant band of the slope key, cut at multiples of 11.25 degrees.
-__device__ __forceinline__ int fq_sector(float slope) {
-  const int qi = (slope >= 0.0f ? 1 : 0) + (slope >= 65536.0f ? 1 : 0) + (slope >= 131072.0f ? 1 : 0);
-  const float r = slope - (float)(qi - 1) * 65536.0f;   // monotone in slope inside a band
-  const int sub = (r >= 0.19891237f ? 1 : 0) + (r >= 0.41421357f ? 1 : 0) + (r >= 0.66817864f ? 1 : 0) + (r >= 1.0f ? 1 : 0) +
-                  (r >= 1.4966058f ? 1 : 0) + (r >= 2.4142137f ? 1 : 0) + (r >= 5.0273395f ? 1 : 0);
-  return qi * 8 + sub;
-}
-// 64 sectors (sixteen per band, cut at multiples of 5.625 degrees); sector s of fq_sector is the union of 2s and 2s + 1
+// 64 sectors, sixteen per quadrant band of the slope key, cut at multiples of 5.625 degrees (32 sectors: the unions of 2s and 2s + 1).
 __device__ __forceinline__ int fq_sector64(float slope) {
   const int qi = (slope >= 0.0f ? 1 : 0) + (slope >= 65536.0f ? 1 : 0) + (slope >= 131072.0f ? 1 : 0);
-  const float r = slope - (float)(qi - 1) * 65536.0f;
+  const float r = slope - (float)(qi - 1) * 65536.0f;   // monotone in slope inside a band
   const int sub = (r >= 0.09849140f ? 1 : 0) + (r >= 0.19891237f ? 1 : 0) + (r >= 0.30334668f ? 1 : 0) + (r >= 0.41421357f ? 1 : 0) +
                   (r >= 0.53451114f ? 1 : 0) + (r >= 0.66817864f ? 1 : 0) + (r >= 0.82067879f ? 1 : 0) + (r >= 1.0f ? 1 : 0) +
                   (r >= 1.2185035f ? 1 : 0) + (r >= 1.4966058f ? 1 : 0) + (r >= 1.8708684f ? 1 : 0) + (r >= 2.4142137f ? 1 : 0) +
@@ -862,12 +852,6 @@ template <int NT, bool SPLIT>
 #define FQ_WPE_128 4
 #define FQ_WPE_256 4
 #endif
-// persistent workgroups per CU of the two small classes (they fill FQ_WPE waves per SIMD when alone on a CU)
-#define FQ_NT_BIG 1024   // threads of the largest class: one workgroup fills a CU (16 waves, 4 per SIMD)
-#ifndef FQ_GRID_64
-#define FQ_GRID_64 16
-#define FQ_GRID_128 8
-#endif
 // (the body of k_fit_quads)
 __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
                                                    const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
@@ -1038,66 +1022,7 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
     const bool padded = in_lds && (1 << lpow) <= sort_cap;
     if (padded)
       for (int i = sz + tid; i < (1 << lpow); i += NT) skeys[FQ_KP(i)] = AT_KEY_PAD;
-    constexpr bool kPresort = FQ_SOUND_EXIT_PRESORT && SPLIT && NT >= FQ_PRESORT_MIN_NT;   // (tools_hooks.h: 1 in the product build)
-    if constexpr (kPresort)
-      for (int t = tid; t < (FQ_XG + 1) * 7; t += NT) chunk[t] = 0.0;   // sector sums (pair-table region: free until the maxima exist)
     __syncthreads();
-    if constexpr (kPresort) {
-      // ---- sound early exit before the sort (see fq_sector above) -------------------------------------------------
-      // Every lane walks a run of consecutive keys of the (still unsorted) list -- points arrive tile by tile, so a run
-      // mostly stays inside one sector -- and keeps the sector's seven sums in registers; they go to the sector's LDS
-      // entry (seven f64 atomics) only when the sector changes.
-      double* const sB = chunk;   // [(FQ_XG + 1)][7]: entry s + 1 = sums of sector s, then prefix sums
-      {
-        int E = (sz + NT - 1) / NT;
-        if (!in_lds && E >= 8) E |= 1;
-        if (in_lds && (E & 31) == 31) E++;
-        const int i0 = tid * E, i1 = min(sz, i0 + E);
-        double a[7];
-        int cur = -1;
-        auto flush = [&]() {
-#pragma unroll
-          for (int j = 0; j < 7; j++) __hip_atomic_fetch_add(&sB[(cur + 1) * 7 + j], a[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        };
-        for (int i = i0; i < i1; i++) {
-          const unsigned long long key = key_dec(in_lds ? skeys[FQ_KP(i)] : gkeys[i]);
-          const uint32_t fs = (uint32_t)(key >> 32);
-          const float slope = __uint_as_float((fs & 0x80000000u) ? (fs & 0x7FFFFFFFu) : ~fs);   // inverse of float_sortable
-          const int sec = fq_sector(slope);
-          const uint32_t px = (uint32_t)((key >> 4) & 0x3FFF), py = (uint32_t)((key >> 18) & 0x3FFF);
-          const double x = (int)(px + 1) * .5, y = (int)(py + 1) * .5;
-          const int ix = (int)((px + 1) >> 1), iy = (int)((py + 1) >> 1);
-          uint32_t G = 0;
-          if (((unsigned)(ix - 1) < (unsigned)(W - 2)) & ((unsigned)(iy - 1) < (unsigned)(H - 2))) {
-            const uint32_t o = __umul24((uint32_t)iy, (uint32_t)gpitch) + (uint32_t)ix;   // (rows below 2^14, pitches below 2^24: check_images)
-            const int g_r = ggray[o + 1], g_l = ggray[o - 1], g_d = ggray[o + (uint32_t)gpitch], g_u = ggray[o - (uint32_t)gpitch];
-            const int grad_x = g_r - g_l, grad_y = g_d - g_u;
-            G = (uint32_t)(grad_x * grad_x + grad_y * grad_y);
-          }
-          const double Wt = sqrt_u18(G) + 1;
-          const double wl = (px & py & 1u) ? 0.5 * Wt : Wt;
-          if (sec != cur) {
-            if (cur >= 0) flush();
-            cur = sec;
-#pragma unroll
-            for (int j = 0; j < 7; j++) a[j] = 0.0;
-          }
-          const double wx = wl * x, wy = wl * y;
-          a[0] += wx; a[1] += wy; a[2] += wx * x; a[3] += wx * y; a[4] += wy * y; a[5] += wl; a[6] += Wt;
-        }
-        if (cur >= 0) flush();
-      }
-      __syncthreads();
-      if (tid < 7) {
-        double run = 0.0;
-        for (int sct = 1; sct <= FQ_XG; sct++) { run += sB[sct * 7 + tid]; sB[sct * 7 + tid] = run; }
-      }
-      __syncthreads();
-      const bool feas_pre = fq_feasible<NT, 7, 6>(sB, P.max_line_fit_mse, W, H, s_okf, s_okw, &s_feasible);
-      FQ_TICK(3)
-      FQ_COUNT(0, sz)
-      if (!feas_pre) { FQ_COUNT(1, sz) continue; }
-    }
     // (a wave's own LDS accesses are ordered: the one-wave class needs no barrier around the register sort)
 #ifndef FQ_REGSORT_MAX_LPOW
 #define FQ_REGSORT_MAX_LPOW 8
@@ -1701,7 +1626,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
 // keys, run as one or two persistent workgroups per CU and, on frames with textured background, almost all end at "no
 // admissible corner choice" (config 2: every one of them).  This kernel takes exactly those work items and applies the
 // exits that need neither the sort nor the key array -- bounding box, border direction (the same statements as
-// k_fit_quads) and the sound sector test (fq_sector / fq_feasible above) -- at full occupancy: 256 threads and about
+// k_fit_quads) and the sound sector test (fq_sector64 / fq_feasible above) -- at full occupancy: 256 threads and about
 // 10 KB of LDS per cluster.  The surviving items are appended to a second, compact work list per class, which is what the
 // persistent workgroups of these classes pop from (marking the rejected items in place left them popping tens of thousands
 // of dead items through one cursor word: 0.25 ms per class at the ~90 atomics per microsecond one word sustains).  Nothing

@@ -15,10 +15,9 @@
 //     normals or errors, with the pair indices of the 210 choices from a compile-time table.
 // One wave per cluster, no workgroup barriers that synchronise anything (a one-wave workgroup's barrier is only a
 // compiler fence).
-// K = 2 (clusters up to 128 points, moments in LDS) is the instance the library launches.  K = 4 (129 .. 256 points, GROWS: moments
-// in a global scratch slot, because 12 KB of them per workgroup would cut the resident workgroups to 10 per CU) compiles and is
-// bit-exact too, but measured no gain over k_fit_quads<64> for its sizes and is off: FS_B1 == FS_B0 in
-// detector.hip's class table leaves its class empty.
+// K = 2 (clusters up to 128 points) is the instance the library launches.  K = 4 (129 .. 256 points, its moments in a global
+// scratch slot) measured no gain over k_fit_quads<64> for its sizes: class 1 of the class table
+// (launch_plan.h) is empty.
 #pragma once
 #include "kernels_quad.h"
 
@@ -32,18 +31,11 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 #ifndef FS_WPE
 #define FS_WPE 4   // waves per SIMD the register allocation must allow
 #endif
-#ifndef FS_GRID_K2
-#define FS_GRID_K2 16   // persistent workgroups per CU of the K = 2 class
-#endif
-#ifndef FS_GRID_K4
-#define FS_GRID_K4 16   // persistent workgroups per CU of the K = 4 class
-#endif
 #define FS_TAB_BYTES (FQT_DOUBLES * 8)   // pair tables + staged moment rows
-// LDS of a workgroup: GROWS = false -- moments [64 K][6] | errors [64 K], the tables over the moments once they are dead;
-//                     GROWS = true  -- tables | errors [64 K]; the moments live in the workgroup's global scratch slot
-#define FS_LDS_BYTES(K, GROWS) ((GROWS) ? (FS_TAB_BYTES + 64 * (K) * 8) : ((64 * (K) * 56) > FS_TAB_BYTES ? (64 * (K) * 56) : FS_TAB_BYTES))
+// LDS of a workgroup: moments [64 K][6] | errors [64 K], the tables over the moments once they are dead
+#define FS_LDS_BYTES(K) ((64 * (K) * 56) > FS_TAB_BYTES ? (64 * (K) * 56) : FS_TAB_BYTES)
 
-template <int K, bool GROWS>
+template <int K>
 __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
                                                           const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
                                                           const uint32_t* __restrict__ work, const uint32_t* __restrict__ work_n, uint32_t work_cap,
@@ -51,16 +43,15 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
                                                           FrameCounters* __restrict__ counters, int pop, DetParams P) {
   constexpr int CAP = 64 * K;
   extern __shared__ __attribute__((aligned(16))) unsigned char fs_smem[];
-  // [CAP][6] cumulative moments of the kept points: in LDS, or (GROWS: the K = 4 class, whose 12 KB of moments would cut
-  // the resident workgroups to 10 per CU) in the workgroup's slot of a global scratch array, which stays in L2
+  // [CAP][6] cumulative moments of the kept points
   double* const lds = reinterpret_cast<double*>(fs_smem);
-  double* const rows = GROWS ? lf_scratch + (size_t)blockIdx.x * CAP * 6 : lds;
+  double* const rows = lds;
   // [CAP] windowed errors, then the smoothed ones, then the maxima list
-  double* const errs = GROWS ? lds + FQT_DOUBLES : lds + CAP * 6;
+  double* const errs = lds + CAP * 6;
   // the pair tables and the staged rows (FQT_* layout, kernels_quad.h): in the moments' place once the maxima are selected
   double* const s_tab = lds;
   double* const s_rows = s_tab + FQT_ROWS;
-  static_assert(GROWS || FQT_DOUBLES * 8 <= 64 * K * 56, "tables fit the moment region");
+  static_assert(FQT_DOUBLES * 8 <= 64 * K * 56, "tables fit the moment region");
   __shared__ uint32_t s_cpairs[210];
   __shared__ int s_maxidx[16];
 
@@ -427,11 +418,12 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
   }
 }
 
-template <int K, bool GROWS>
+// (lf_scratch: unused)
+template <int K>
 __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
                                                           const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
                                                           const uint32_t* __restrict__ work, const uint32_t* __restrict__ work_n, uint32_t work_cap,
                                                           uint32_t* __restrict__ work_cursor, double* __restrict__ lf_scratch, FitCand* __restrict__ cands_all,
                                                           FrameCounters* __restrict__ counters, int pop, DetParams P) {
-  fit_small_body<K, GROWS>(frames, gray_all, pts_all, clusters_all, work, work_n, work_cap, work_cursor, lf_scratch, cands_all, counters, pop, P);
+  fit_small_body<K>(frames, gray_all, pts_all, clusters_all, work, work_n, work_cap, work_cursor, lf_scratch, cands_all, counters, pop, P);
 }

@@ -66,8 +66,8 @@
 #endif
 
 #if defined(AMDAT_FQ_PROFILE)
-// points of the clusters that reach the pre-sort test (0), that it rejects (1), that the test after the first walk rejects
-// (2): prof[40 + 4 * class + k] (the launch passes prof + 8 * class)
+// points of the clusters that the test after the first walk rejects (k = 2): prof[40 + 4 * class + k] (the launch passes
+// prof + 8 * class)
 #define FQ_HOOKS_DECL unsigned long long t_prev_ = prof ? __builtin_readcyclecounter() : 0ull;
 #define FQ_TICK(slot)                                                                  \
   if (prof && tid == 0) {                                                              \
@@ -126,16 +126,11 @@
 #endif
 
 // ---- the SOUND early exits of the quad fit can be compiled out, one by one, to show that no result depends on them
-// (-DAMDAT_FQ_NO_PRESORT_EXIT, -DAMDAT_FQ_NO_EARLY_EXIT, -DAMDAT_FQ_NO_PREFILTER: the A/B builds give the same bytes) ---------
+// (-DAMDAT_FQ_NO_EARLY_EXIT, -DAMDAT_FQ_NO_PREFILTER: the A/B builds give the same bytes) ----------------------------------------
 #if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 3
 #define PF_MUT_EXTRA_SECTOR(nt) ((nt) == 64 ? 1 : 0)
 #else
 #define PF_MUT_EXTRA_SECTOR(nt) 0
-#endif
-#ifdef AMDAT_FQ_NO_PRESORT_EXIT
-#define FQ_SOUND_EXIT_PRESORT 0
-#else
-#define FQ_SOUND_EXIT_PRESORT 1
 #endif
 #ifdef AMDAT_FQ_NO_EARLY_EXIT
 #define FQ_SOUND_EXIT_AFTER_WALK1 0
