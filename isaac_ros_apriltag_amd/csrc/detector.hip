@@ -1169,7 +1169,8 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
     hipLaunchKernelGGL(k_quad_finish, dim3(16, n), dim3(256), 0, s, D->d_cands, D->d_quads, D->d_counters, P);
   }
   mark();
-  hipLaunchKernelGGL(k_decode_wave, dim3(plan.decode_grid, n), dim3(64), 0, s, D->d_frames, D->d_quads, D->d_dets, D->d_counters, P);
+  hipLaunchKernelGGL(k_decode_wave, dim3(plan.decode_grid, n), dim3(64), 0, s, D->d_frames, D->d_quads, D->d_dets, D->d_counters,
+                     DECODE_PARAMS(P, D->qs_ksz > 1));   // (tools_hooks.h: P in the product build)
   mark();
   hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
                      D->h_counters, P);

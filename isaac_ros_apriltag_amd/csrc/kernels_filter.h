@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
     uint32_t d[10];
 #pragma unroll
     for (int q = 0; q < 5; q++) { const uint2 t = src[q]; d[2 * q] = t.x; d[2 * q + 1] = t.y; }
-    const bool interior = rows_filter && x >= T.h && x + 15 <= P.W - T.h - 2;
+    const bool interior = rows_filter && x >= T.h && x + 15 <= P.W - QS_FAR_EDGE_H(KH, T.h) - 2;   // (tools_hooks.h: T.h)
     uint32_t o[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int p = 0; p < 16; p++) {
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
       uint32_t t = acc >> 8;
       if (!interior) {
         const int xp = x + p;
-        if (!(rows_filter && xp >= T.h && xp <= P.W - T.h - 2)) t = (d[(8 + p) / 4] >> (8 * ((8 + p) & 3))) & 0xFFu;
+        if (!(rows_filter && xp >= T.h && xp <= P.W - QS_FAR_EDGE_H(KH, T.h) - 2)) t = (d[(8 + p) / 4] >> (8 * ((8 + p) & 3))) & 0xFFu;
       }
       o[p >> 2] |= t << (8 * (p & 3));
     }
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
   const int y = y0 + r, x = x0 + 16 * c;
   if (y >= P.H || x >= P.WS) return;
   uint32_t o[4];
-  if (cols_filter && y >= T.h && y <= P.H - T.h - 2) {
+  if (cols_filter && y >= T.h && y <= P.H - QS_FAR_EDGE_H(KH, T.h) - 2) {
     qs_u16x2 lo[4], hi[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) { lo[q] = (qs_u16x2)(0); hi[q] = (qs_u16x2)(0); }

@@ -14,7 +14,11 @@
 //                           3 = k_fit_prefilter<64>'s 64-sector test counts one sector too many at either end of every forward arc
 //                               (the cut sectors themselves, which hold the corners): it then "proves" real quads above 2048 points
 //                               impossible and drops them
-//                           the GPU suite ships all three (build.py: build_mutants) and asserts that its stage tests FAIL on each
+//                           4 = k_quad_sigma's copy rule takes the instance's padded half width KH for the tap half width h on the right
+//                               and bottom edges: wrong values in the last KH - h filtered columns / rows, for h < KH only (h = 3, 5, 6, 7)
+//                           5 = with the quad_sigma filter on at decimate > 1 the decode launch runs as if refine_edges were 0
+//                           (4 and 5 change values only: no address, index bound or launch size)
+//                           the GPU suite ships all five (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
@@ -38,6 +42,13 @@
 #define CC_LAST_ROW_OFFSET(NW) ((NW) == 4 ? 2 : 1)
 #else
 #define CC_LAST_ROW_OFFSET(NW) 1
+#endif
+
+// ---- k_quad_sigma: the half width of the copy rule on the far (right / bottom) edge of a pass --------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 4
+#define QS_FAR_EDGE_H(KH, h) (KH)
+#else
+#define QS_FAR_EDGE_H(KH, h) (h)
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------
@@ -153,4 +164,11 @@
 #else
 #define FQ_SKIP_PREFILTER() 0
 #define FQ_SKIP_CLASS(c) 0
+#endif
+
+// the parameter block of the decode launch (filt: the submission runs the quad_sigma filter)
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 5
+#define DECODE_PARAMS(P, filt) [&] { DetParams q_ = (P); if ((filt) && q_.decimate > 1) q_.refine_edges = 0; return q_; }()
+#else
+#define DECODE_PARAMS(P, filt) (P)
 #endif

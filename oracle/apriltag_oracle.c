@@ -110,6 +110,55 @@ void ato_decimate(const uint8_t* in, int w, int h, int pitch, int f, uint8_t* ou
 }
 
 /* ------------------------------------------------------------------------------------------- */
+/* S1b quad_sigma: Gaussian blur or sharpen of the working image (DESIGN.md section 7a;         */
+/*     AprilRobotics apriltag_detector_detect / image_u8_gaussian_blur)                          */
+/* ------------------------------------------------------------------------------------------- */
+/* one 1-D pass over a line of n samples `stride` bytes apart: y[i] = (sum_j k[j] x[i-hw+j]) >> 8 for hw <= i <= n-hw-2, every other
+ * sample copied (hw on the left, hw + 1 on the right); a line of n <= ksz samples is copied whole */
+static void quad_sigma_line(const uint8_t* x, uint8_t* y, int n, int stride, const uint8_t* k, int ksz) {
+  const int hw = ksz / 2;
+  for (int i = 0; i < n; i++) {
+    if (n <= ksz || i < hw || i > n - hw - 2) { y[(size_t)i * stride] = x[(size_t)i * stride]; continue; }
+    uint32_t acc = 0;
+    for (int j = 0; j < ksz; j++) acc += (uint32_t)k[j] * x[(size_t)(i - hw + j) * stride];
+    y[(size_t)i * stride] = (uint8_t)(acc >> 8);
+  }
+}
+
+int ato_quad_sigma(uint8_t* im, int w, int h, double quad_sigma) {
+  const float s = fabsf((float)quad_sigma);
+  if (!(s <= 64.0f)) return 0;          /* (NaN, inf and absurd widths: ato_detect refuses them before it gets here) */
+  int ksz = (int)(4.0f * s);
+  if ((ksz & 1) == 0) ksz++;
+  if (ksz <= 1) return 0;
+  const int hw = ksz / 2;
+  double* dk = (double*)malloc((size_t)ksz * sizeof(double));
+  uint8_t* k = (uint8_t*)malloc((size_t)ksz);
+  double acc = 0.0;
+  for (int i = 0; i < ksz; i++) {
+    const double u = (double)(i - hw) / (double)s;
+    dk[i] = exp(-0.5 * u * u);
+  }
+  for (int i = 0; i < ksz; i++) acc += dk[i];
+  for (int i = 0; i < ksz; i++) k[i] = (uint8_t)((dk[i] / acc) * 255.0);
+  const size_t n = (size_t)w * h;
+  uint8_t* t = (uint8_t*)malloc(n);
+  uint8_t* b = (uint8_t*)malloc(n);
+  for (int y = 0; y < h; y++) quad_sigma_line(im + (size_t)y * w, t + (size_t)y * w, w, 1, k, ksz);   /* rows of G */
+  for (int x = 0; x < w; x++) quad_sigma_line(t + x, b + x, h, w, k, ksz);                              /* columns: B */
+  if (quad_sigma > 0) {
+    memcpy(im, b, n);
+  } else {                              /* sharpen: clamp(2 G - B, 0, 255) */
+    for (size_t i = 0; i < n; i++) {
+      const int v = 2 * (int)im[i] - (int)b[i];
+      im[i] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+    }
+  }
+  free(dk); free(k); free(t); free(b);
+  return 1;
+}
+
+/* ------------------------------------------------------------------------------------------- */
 /* S2  adaptive tile min/max threshold (A.2)                                                    */
 /* ------------------------------------------------------------------------------------------- */
 void ato_threshold(const uint8_t* im, int w, int h, int tile, int min_diff, uint8_t* out) {
@@ -1371,6 +1420,7 @@ static int quad_key_cmp(const void* a, const void* b) {
 int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, const uint8_t* image, int width,
                int height, int pitch, ato_detection_t* out, int max_det, ato_dump_t* dump) {
   if (nfam < 1 || nfam > ATO_MAX_FAMILIES || prm->decimate < 1 || prm->tile_size < 1) return -1;
+  if (!(fabs(prm->quad_sigma) <= 64.0)) return -1;   /* (NaN included; the library itself serves |sigma| <= 4) */
   int f = prm->decimate;
   int w = 1 + (width - 1) / f, h = 1 + (height - 1) / f;
   if (w / prm->tile_size < 1 || h / prm->tile_size < 1 || 2 * w + 1 >= (1 << 14) || 2 * h + 1 >= (1 << 14)) return -2;
@@ -1381,6 +1431,11 @@ int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, cons
   uint32_t* csize = (uint32_t*)malloc(n * 4);
   int sw, sh;
   ato_decimate(image, width, height, pitch, f, gray, &sw, &sh);
+  /* quad_sigma: at decimate 1 every later stage reads the filtered frame; at decimate > 1 only the stages up to the quad fit do
+   * (they read `gray`), edge refinement and decode keep the untouched input */
+  const uint8_t* fimage = image;
+  int fpitch = pitch;
+  if (ato_quad_sigma(gray, w, h, prm->quad_sigma) && f == 1) { fimage = gray; fpitch = w; }
   ato_threshold(gray, w, h, prm->tile_size, prm->min_white_black_diff, thr);
   ato_connected_components(thr, w, h, label, csize);
 
@@ -1436,7 +1491,7 @@ int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, cons
   ato_detection_t* dets = (ato_detection_t*)malloc(dcap * sizeof(ato_detection_t));
   for (size_t qi = 0; qi < nq; qi++) {
     ato_quad_t q = quads[qi];
-    if (prm->refine_edges) refine_edges(prm, image, width, height, pitch, &q);
+    if (prm->refine_edges) refine_edges(prm, fimage, width, height, fpitch, &q);
     double corr[4][4], H[9];
     for (int i = 0; i < 4; i++) {
       corr[i][0] = (i == 0 || i == 3) ? -1 : 1;
@@ -1448,7 +1503,7 @@ int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, cons
     for (int fi = 0; fi < nfam; fi++) {
       if (fams[fi].reversed_border != q.reversed_border) continue;
       int id = 0, hamming = 0, rotation = 0, found = 0;
-      float margin = quad_decode(prm, &fams[fi], image, width, height, pitch, H, &id, &hamming, &rotation, &found);
+      float margin = quad_decode(prm, &fams[fi], fimage, width, height, fpitch, H, &id, &hamming, &rotation, &found);
       if (!(margin >= 0 && found)) continue;
       if (nd == dcap) { dcap *= 2; dets = (ato_detection_t*)realloc(dets, dcap * sizeof(ato_detection_t)); }
       ato_detection_t* det = &dets[nd++];

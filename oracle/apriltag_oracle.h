@@ -62,6 +62,10 @@ typedef struct {
   int32_t variant;               /* 0 = canonical definitions (what the HIP path is checked against bit for bit);
                                   * ATO_VAR_* bits switch single steps to AprilRobotics' own formulation, used only
                                   * to BOUND the distance between the two (tests/test_oracle_variants_cpu.py) */
+  double quad_sigma;             /* 0: Gaussian blur (> 0) or sharpen (< 0) of the working image; |sigma| < 0.5
+                                  * is the identity.  Decimate 1: every later stage reads the filtered frame.  Decimate > 1: the
+                                  * threshold through the quad fit read the filtered working image, edge refinement and decode the
+                                  * untouched input */
 } ato_params_t;
 
 /* upstream formulations of the steps this restatement defines canonically */
@@ -107,7 +111,7 @@ typedef struct {
 /* Stage dump of one frame (all arrays malloc'ed by ato_detect_dump, freed by ato_dump_free). */
 typedef struct {
   int32_t w, h;                 /* working-image size */
-  uint8_t* gray;                /* decimated gray image, w*h */
+  uint8_t* gray;                /* decimated gray image (after quad_sigma's filter, if set), w*h */
   uint8_t* thr;                 /* threshold image, w*h */
   uint32_t* label;              /* w*h, canonical representative (min pixel index) or ATO_NO_LABEL */
   uint32_t* csize;              /* w*h, component size stored at the representative's index */
@@ -131,6 +135,8 @@ int ato_custom_family(const char* name, uint32_t nbits, const int8_t* bit_x, con
 
 /* stage entry points (each follows the cited public algorithm step) */
 void ato_decimate(const uint8_t* in, int w, int h, int pitch, int f, uint8_t* out, int* sw, int* sh);
+/* quad_sigma's filter of a tightly packed w x h image, in place.  Returns 1 if it filtered, 0 for the identity (|sigma| < 0.5). */
+int ato_quad_sigma(uint8_t* im, int w, int h, double quad_sigma);
 void ato_threshold(const uint8_t* im, int w, int h, int tile, int min_diff, uint8_t* out);
 void ato_connected_components(const uint8_t* thr, int w, int h, uint32_t* label, uint32_t* csize);
 

@@ -27,7 +27,8 @@ class Params(C.Structure):
                 ("max_line_fit_mse", C.c_double), ("refine_edges", C.c_int32),
                 ("decode_sharpening", C.c_double), ("max_hamming", C.c_int32),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
-                ("tag_size", C.c_double), ("skew", C.c_double), ("variant", C.c_int32)]
+                ("tag_size", C.c_double), ("skew", C.c_double), ("variant", C.c_int32),
+                ("quad_sigma", C.c_double)]
 
 
 class Detection(C.Structure):
@@ -88,6 +89,8 @@ def lib():
         _lib.ato_connected_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ato_decimate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib.ato_quad_sigma.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
+        _lib.ato_quad_sigma.restype = C.c_int
         _lib.ato_resize_mono8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
         _lib.ato_rectify_mono8.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -168,6 +171,13 @@ def decimate(img, f):
     out = np.empty((1 + (h - 1) // f, 1 + (w - 1) // f), dtype=np.uint8)
     sw, sh = C.c_int(), C.c_int()
     lib().ato_decimate(img.ctypes.data, w, h, img.strides[0], f, out.ctypes.data, C.byref(sw), C.byref(sh))
+    return out
+
+
+def quad_sigma(img, sigma):
+    """quad_sigma's filter of a working image (the C statement of DESIGN.md section 7a)."""
+    out = np.array(img, dtype=np.uint8, order="C", copy=True)
+    lib().ato_quad_sigma(out.ctypes.data, out.shape[1], out.shape[0], float(sigma))
     return out
 
 

@@ -7,7 +7,8 @@ from oracle import pyoracle as po
 
 def oracle_params(K, decimate=1, tag_size=0.22, tile_size=4, **more):
     # the C ABI carries float intrinsics (like cuAprilTagsCameraIntrinsics_t); give the oracle the same values
-    # (more: refine_edges, max_hamming, decode_sharpening, skew ... -- the oracle's fields of the same names; floats as the ABI's f32)
+    # (more: refine_edges, max_hamming, decode_sharpening, skew, quad_sigma ... -- the oracle's fields of the same names; floats as the
+    # ABI's f32.  quad_sigma: the oracle filters its own working image, so `img` is the frame as submitted.)
     f32 = lambda v: float(np.float32(v))
     more = {k: (f32(v) if isinstance(v, float) else v) for k, v in more.items()}
     return po.default_params(fx=f32(K[0, 0]), fy=f32(K[1, 1]), cx=f32(K[0, 2]), cy=f32(K[1, 2]), decimate=decimate,

@@ -22,6 +22,12 @@ def taps(sigma):
     return [int((v / acc) * 255.0) for v in dk]
 
 
+# one sigma for every half width h = ksz / 2 the library serves (|sigma| <= 4: h = 1 .. 8; h = 8 is sigma 4.0 alone), each used with
+# both signs, and the ends of the accepted range
+SIGMA_OF_H = {1: 0.8, 2: 1.2, 3: 1.7, 4: 2.2, 5: 2.7, 6: 3.2, 7: 3.7, 8: 4.0}
+ALL_SIGMAS = tuple(s * sign for s in SIGMA_OF_H.values() for sign in (1, -1)) + (0.5, -0.5)
+
+
 def pass_1d(x, k):
     """One pass along the last axis: y[i] = (sum_j k[j] x[i-h+j]) >> 8 for h <= i <= n-h-2, every other sample copied."""
     x = np.asarray(x, dtype=np.uint8)

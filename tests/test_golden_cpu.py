@@ -24,7 +24,8 @@ def test_oracle_matches_golden(built, path):
     rec = json.load(open(path))
     img, K = load_scene(rec)
     assert zlib.crc32(img.tobytes()) == rec["image_crc32"], "renderer bytes changed"
-    dets, dump = po.detect(img, families=tuple(rec["families"]), params=pu.oracle_params(K, rec["decimate"]), want_dump=True)
+    dets, dump = po.detect(img, families=tuple(rec["families"]), params=pu.oracle_params(K, rec["decimate"], quad_sigma=float(rec.get("quad_sigma", 0.0))),
+                           want_dump=True)
     assert zlib.crc32(dump["thr"].tobytes()) == rec["thr_crc32"]
     assert zlib.crc32(dump["label"].tobytes()) == rec["label_crc32"]
     assert zlib.crc32(dump["points"].tobytes()) == rec["points_crc32"]

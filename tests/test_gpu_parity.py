@@ -295,7 +295,8 @@ def test_against_committed_golden_vectors(built, path, subpath):
     r = getattr(synth, rec["scene"])(**rec["kwargs"])
     img, K = r[0], r[1]
     assert zlib.crc32(img.tobytes()) == rec["image_crc32"]
-    det, g = _run(img, K, tuple(rec["families"]), rec["decimate"], path=subpath)
+    more = {"quad_sigma": float(rec["quad_sigma"])} if rec.get("quad_sigma") else {}   # (optional key of a record, default 0)
+    det, g = _run(img, K, tuple(rec["families"]), rec["decimate"], path=subpath, **more)
     h, w = (1 + (img.shape[0] - 1) // rec["decimate"]), (1 + (img.shape[1] - 1) // rec["decimate"])
     assert zlib.crc32(det.debug(0, capi.DBG_THRESH).tobytes()) == rec["thr_crc32"]
     assert zlib.crc32(det.debug(0, capi.DBG_LABEL).tobytes()) == rec["label_crc32"]
@@ -1692,16 +1693,22 @@ _MUTANT_SELECTIONS = {
     2: "test_throughput_set_every_stage_of_every_frame or (test_stage_and_detection_parity and throughput and c2) or "
        "(test_integer_stages_on_noise_ragged_sizes and throughput and 644)",
     3: "test_large_quads_survive_the_prefilter",   # (its latency-set cases run the CU-wide prefilter instance and still pass)
+    # 4 and 5 live in the quad_sigma filter and its pairing with decode: (file, selection)
+    4: ("test_quad_sigma_gpu.py", "test_every_tap_width_on_edge_shapes and dec2"),   # (h = 1, 2, 4, 8 are h == KH and still pass)
+    5: ("test_quad_sigma_gpu.py", "test_decimated_records and c1_dec3"),
 }
 
 
 @pytest.mark.parametrize("mutant", sorted(_MUTANT_SELECTIONS))
 def test_the_suite_fails_on_wrong_builds(built, mutant):
-    """The stage tests BITE: three deliberately wrong builds of the same sources ship next to the product
+    """The stage tests BITE: five deliberately wrong builds of the same sources ship next to the product
     library -- 1: the launch sequence without k_fit_small, 2: one row constant off in k_cc_local<4>, 3: one sector too many in
-    k_fit_prefilter<64>'s test (csrc/tools_hooks.h) -- and a selection of this file's stage tests, run against each in a process
-    of its own, must FAIL, while the same selection passes on the product library.  The latency-set twins of the selected tests
-    must still pass on mutants 1 and 2, whose errors live in the throughput set only."""
+    k_fit_prefilter<64>'s test, 4: k_quad_sigma's copy rule with the padded half width KH for h on the right / bottom edge (wrong
+    for h < KH only), 5: no edge refinement when the filter runs at decimate > 1 (csrc/tools_hooks.h) -- and a selection of the
+    suite's stage tests (this file's, or tests/test_quad_sigma_gpu.py's for 4 and 5), run against each in a process of its own,
+    must FAIL, while the same selection passes on the product library.  The latency-set twins of the selected tests must still
+    pass on mutants 1 and 2, whose errors live in the throughput set only; on mutant 4 exactly the half widths h = 3, 5, 6, 7
+    fail (h == KH cannot see it), on mutant 5 the stages through the quads are right and the records alone differ."""
     import subprocess
     import sys
     from isaac_ros_apriltag_amd import build as bld
@@ -1709,13 +1716,14 @@ def test_the_suite_fails_on_wrong_builds(built, mutant):
     if not os.path.exists(bld.lib_mutant(mutant)):
         bld.build_mutants()
     sel = _MUTANT_SELECTIONS[mutant]
+    test_file, sel = sel if isinstance(sel, tuple) else ("test_gpu_parity.py", sel)
 
     def run(lib):
         env = dict(os.environ)
         env.pop("AMDAT_LIB", None)
         if lib:
             env["AMDAT_LIB"] = lib
-        out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_parity.py"), "-m", "gpu", "-q",
+        out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", test_file), "-m", "gpu", "-q",
                               "-p", "no:cacheprovider", "-k", sel], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
         tail = [l for l in out.stdout.splitlines() if " passed" in l or " failed" in l or l.startswith("FAILED")]
         return out.returncode, tail, out
@@ -1725,5 +1733,10 @@ def test_the_suite_fails_on_wrong_builds(built, mutant):
     assert nfailed >= 2, tail_bad
     if mutant == 1:   # every selected test fails (none of them can pass without the small-cluster fit)
         assert not any(" passed" in l and " failed" not in l for l in tail_bad), tail_bad
+    if mutant == 4:   # the half widths below their instance's KH, and only those
+        failed = sorted(l.split("[")[1].split("-")[0] for l in tail_bad if l.startswith("FAILED"))
+        assert failed == ["h3", "h5", "h6", "h7"], tail_bad
+    if mutant == 5:   # the filtered plane and the stages are right: what differs is a record field
+        assert "field" in out_bad.stdout and "gray:" not in out_bad.stdout and "quad key" not in out_bad.stdout, out_bad.stdout[-1500:]
     rc_ok, tail_ok, out_ok = run(None)
     assert rc_ok == 0 and any(" passed" in l for l in tail_ok) and not any(" failed" in l for l in tail_ok), (tail_ok, out_ok.stdout[-1500:])

@@ -110,10 +110,15 @@ def colour_frame(rng, gray_like, encoding, pitch_pad):
 MAX_DETS = 256   # records a call asks for: a frame with more (noise fields under tag16h5) comes back as the first MAX_DETS of the canonical order
 
 
-def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1, only=None, dump=None, colour=False, tile=4, params=False, layout=False, quad_sigma=False):
+def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1, only=None, dump=None, colour=False, tile=4, params=False, layout=False, quad_sigma=False,
+              stats=None):
     """Returns (cases run, list of failure strings).  path: None (the library picks the launch set by size: the latency set at these
     sizes), "latency", "throughput", or "alternate" (even cases latency, odd cases throughput).  batch > 1: every case submits `batch` frames
-    of the case's size, each with content of its own, in ONE call, and every frame is compared (frame indexing of every stage)."""
+    of the case's size, each with content of its own, in ONE call, and every frame is compared (frame indexing of every stage).
+    stats: a dict that receives "left_out", the number of cases the run left out because the library refuses their handle by design
+    (tile 8 and a working image below 8 pixels a side); they are not in `cases run`."""
+    if stats is not None:
+        stats["left_out"] = 0
     rng = np.random.default_rng(seed)
     t0 = time.time()
     fails = []
@@ -161,12 +166,14 @@ def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1
                                    max_batch=batch, tile_size=tile, tag_size=tag_size, **more)
         except Exception as e:  # noqa: BLE001
             if tile > 4 and min(1 + (w - 1) // dec, 1 + (h - 1) // dec) < tile:
+                if stats is not None:
+                    stats["left_out"] += 1
                 continue   # (a working image below one tile a side is refused at creation: AMDAT_UNSUPPORTED, by design)
             fails.append("case %d: create failed for %dx%d dec %d: %s" % (case, w, h, dec, e))
             out(fails[-1])
             continue
         qsig = 0.0
-        if quad_sigma:   # quad_sigma in [-4, 4] (a generator of its own); the oracle runs on the filtered frame (tests/quad_sigma_ref.py)
+        if quad_sigma:   # quad_sigma in [-4, 4] (a generator of its own); the oracle filters its working image itself (ato_params_t.quad_sigma)
             qsig = float(np.float32(np.random.default_rng(seed * 104729 + case).uniform(-4.0, 4.0)))
             det.set_quad_sigma(qsig)
         if path is not None:
@@ -196,12 +203,13 @@ def run_cases(cases, seed, maxdim=420, budget=1e9, out=print, path=None, batch=1
         errs = []
         for f in range(batch):
             oimg = np.ascontiguousarray(imgs[f])
-            if qsig:   # decimate 1: every stage reads the filtered frame; decimate > 1: J, compared through the quads
-                filt = qs.filter_image(qs.decimate(oimg, dec), qsig)
-                oimg = filt if dec == 1 else qs.embed_decimated(oimg, filt, dec)
-            e, odets = pu.compare_stages(det, f, oimg, fams, K, dec, tag_size=tag_size, tile_size=tile, **more)
-            if not qsig or dec == 1:
-                e += pu.compare_detections(gs[f], odets[:MAX_DETS])
+            qmore = dict(more, quad_sigma=qsig) if qsig else more
+            e, odets = pu.compare_stages(det, f, oimg, fams, K, dec, tag_size=tag_size, tile_size=tile, **qmore)
+            if qsig:   # ... and the filtered plane against the numpy statement as well (tests/quad_sigma_ref.py)
+                wk, hk = det.debug(f, capi.DBG_COUNTS)[6:8]
+                if not np.array_equal(det.debug(f, capi.DBG_GRAY).reshape(int(hk), int(wk)), qs.filter_image(qs.decimate(oimg, dec), qsig)):
+                    e.append("gray differs from quad_sigma_ref.filter_image")
+            e += pu.compare_detections(gs[f], odets[:MAX_DETS])   # (every decimate: the oracle's records are the detector's)
             errs += ["frame %d: %s" % (f, x) for x in e] if batch > 1 else e
         det.close()
         done += 1

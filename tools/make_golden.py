@@ -25,6 +25,8 @@ SCENES = {
     "c2_high_ids_sigma2": dict(scene="scene_c2_ids", kwargs={"ids": [100, 137, 211, 298, 333, 402, 467, 511, 560, 586], "seed": 1301, "sigma": 2.0},
                                families=["tag36h11"], decimate=1),
     "c5_two_families": dict(scene="scene_c5", kwargs={"seed": 1234, "sigma": 2.0}, families=["tag36h11", "tag25h9"], decimate=1),
+    # quad_sigma (optional key, default 0): the filter at decimate 2 -- quads from the filtered working image, records from the frame itself
+    "c2_dec2_quad_sigma08": dict(scene="scene_c2", kwargs={"seed": 1234, "sigma": 2.0}, families=["tag36h11"], decimate=2, quad_sigma=0.8),
 }
 
 
@@ -34,7 +36,8 @@ def main():
     for name, spec in SCENES.items():
         r = getattr(synth, spec["scene"])(**spec["kwargs"])
         img, K = r[0], r[1]
-        dets, dump = po.detect(img, families=tuple(spec["families"]), params=pu.oracle_params(K, spec["decimate"]), want_dump=True)
+        dets, dump = po.detect(img, families=tuple(spec["families"]), params=pu.oracle_params(K, spec["decimate"], quad_sigma=float(spec.get("quad_sigma", 0.0))),
+                               want_dump=True)
         rec = dict(spec)
         rec["image_crc32"] = zlib.crc32(img.tobytes())
         rec["K"] = [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])]
