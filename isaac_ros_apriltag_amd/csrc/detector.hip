@@ -1114,9 +1114,6 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
                      D->d_counters, gxt, gyt, P);
   mark();
   {
-    // keys | pair-table region
-    // skewed key array (later: errors, candidates, pair tables) | group prefixes of the early-exit test (not in the one-wave class)
-    auto lds_bytes = [](const FqClassSpec& c) { return FQ_KEY_BYTES(c.sort_cap) + (c.nt > 64 ? (size_t)FQ_TABLE_DOUBLES * 8 : 0); };
     // the prefilter's compact lists (d_work2, counts at d_workctl + 16), indexed with the common layout
     uint32_t* const work2 = D->d_work2 - L.off[D->fq.prefilter_class];
     const hipStream_t* aux = D->aux_stream;
@@ -1141,10 +1138,10 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
         const FqScratch& scr = D->fq_scratch[c];
         if (cl.kernel == FQ_SMALL) {
           hipLaunchKernelGGL(k_fit_small<2>, grid, dim3(64), FS_LDS_BYTES(2), sc, D->d_frames, D->d_gray, D->d_pts, D->d_clusters,
-                             D->d_work + L.off[c], D->d_workctl + c, L.cap[c], D->d_workctl + 8 + c, (double*)nullptr, D->d_cands, D->d_counters, st.pop, P);
+                             D->d_work + L.off[c], D->d_workctl + c, L.cap[c], D->d_workctl + 8 + c, D->d_cands, D->d_counters, st.pop, P);
           continue;
         }
-        const size_t lds = lds_bytes(cl);
+        const size_t lds = FQ_LDS_BYTES(cl.nt, cl.sort_cap);   // (kernels_quad.h: the kernel's dynamic-LDS layout)
 #define FQ_ARGS D->d_frames, D->d_gray, D->d_pts, D->d_clusters, (st.compact ? work2 : D->d_work) + L.off[c],                       \
                 D->d_workctl + (st.compact ? 16 : 0) + c, L.cap[c], D->d_workctl + 8 + c, scr.d_lf,                                \
                 (c == FQ_NCLS - 1 ? D->d_keys_scr : nullptr), scr.d_errs, D->d_cands, D->d_counters,                               \

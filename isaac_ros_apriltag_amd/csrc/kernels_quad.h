@@ -32,6 +32,17 @@
 // idempotent operations a lane without a source keeps its own value (old = v, bound_ctrl off).
 #define AT_DPP_STEPS(OP)          \
   OP(0x111, 0xF) OP(0x112, 0xF) OP(0x114, 0xF) OP(0x118, 0xF) OP(0x142, 0xA) OP(0x143, 0xC)
+// a 64-bit value of lane l, read as two 32-bit halves (readlane: l uniform, result in SGPRs; shfl: any l)
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+  return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) |
+         ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32);
+}
+__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int l) {
+  return (unsigned long long)(uint32_t)__shfl((int)(uint32_t)v, l, 64) | ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(v >> 32), l, 64) << 32);
+}
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
 __device__ __forceinline__ int wave_min_i(int v) {
 #define OP(C, M) v = min(v, __builtin_amdgcn_update_dpp(v, v, C, M, 0xF, false));
   AT_DPP_STEPS(OP)
@@ -53,9 +64,7 @@ __device__ __forceinline__ long long wave_sum_ll(long long v) {
   }
   AT_DPP_STEPS(OP)
 #undef OP
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), 63);
-  return (long long)((unsigned long long)lo | ((unsigned long long)hi << 32));
+  return (long long)readlane_u64((unsigned long long)v, 63);
 }
 // max of an unsigned 64-bit key over the wave (used for arg-max with an order-preserving key)
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -68,9 +77,7 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   }
   AT_DPP_STEPS(OP)
 #undef OP
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-  return (unsigned long long)lo | ((unsigned long long)hi << 32);
+  return readlane_u64(v, 63);
 }
 // order-preserving map double -> u64 (total order of the finite values, -0 < +0)
 __device__ __forceinline__ unsigned long long double_sortable(double d) {
@@ -205,9 +212,26 @@ __device__ __forceinline__ double wave_scan_f64(double v) {
   v += f64_dpp<0x143, 0xC>(v);
   return v;
 }
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+
+// Sort keys are stored so that their order as IEEE doubles equals the wanted unsigned order: a
+// compare-exchange is then v_min_f64 + v_max_f64 (two instructions instead of a 64-bit compare and four
+// selects).  u >= 2^63 -> positive double with the same lower 63 bits; u < 2^63 -> ~u, a negative double
+// whose magnitude falls as u grows.  The upper word of u is float_sortable(slope) <= 0xFF800000 and
+// >= 0x387FFFFF (+ bias), so no encoded key has an all-ones exponent (no NaN, no infinity); +infinity is
+// the pad.
+// A bias of 2^20 on the upper word keeps the slope +0.0 (upper word 0x80000000) away from the denormal
+// doubles, so the result does not depend on the denormal mode of the min/max instructions.
+#define AT_KEY_BIAS 0x0010000000000000ull
+__device__ __forceinline__ unsigned long long key_enc(unsigned long long u) {
+  u += AT_KEY_BIAS;
+  return (u >> 63) ? (u ^ 0x8000000000000000ull) : ~u;
 }
+__device__ __forceinline__ unsigned long long key_dec(unsigned long long k) {
+  return ((k >> 63) ? ~k : (k | 0x8000000000000000ull)) - AT_KEY_BIAS;
+}
+#define AT_KEY_PAD 0x7FF0000000000000ull
+
+#include "fit_statements.h"   // the statements the three fit kernels share (uses D2, split_term, wave_scan_f64, key_enc)
 
 // n / d with the reciprocal refinement hoisted: shared_recip is v_rcp_f64 + two Newton steps (the
 // operations the compiler's f64 division expands to), div_by is quotient, exact residual, correction.
@@ -383,8 +407,8 @@ __device__ __forceinline__ bool fq_feasible(const double* sP, double mse_limit, 
 // sectors below that of its duplicate-free points, line by line; the weight bound takes every point in full.
 // 64 sectors, sixteen per quadrant band of the slope key, cut at multiples of 5.625 degrees (32 sectors: the unions of 2s and 2s + 1).
 __device__ __forceinline__ int fq_sector64(float slope) {
-  const int qi = (slope >= 0.0f ? 1 : 0) + (slope >= 65536.0f ? 1 : 0) + (slope >= 131072.0f ? 1 : 0);
-  const float r = slope - (float)(qi - 1) * 65536.0f;   // monotone in slope inside a band
+  const int qi = (slope >= 0.0f ? 1 : 0) + (slope >= FIT_BAND ? 1 : 0) + (slope >= FIT_BAND2 ? 1 : 0);
+  const float r = slope - (float)(qi - 1) * FIT_BAND;   // monotone in slope inside a band
   const int sub = (r >= 0.09849140f ? 1 : 0) + (r >= 0.19891237f ? 1 : 0) + (r >= 0.30334668f ? 1 : 0) + (r >= 0.41421357f ? 1 : 0) +
                   (r >= 0.53451114f ? 1 : 0) + (r >= 0.66817864f ? 1 : 0) + (r >= 0.82067879f ? 1 : 0) + (r >= 1.0f ? 1 : 0) +
                   (r >= 1.2185035f ? 1 : 0) + (r >= 1.4966058f ? 1 : 0) + (r >= 1.8708684f ? 1 : 0) + (r >= 2.4142137f ? 1 : 0) +
@@ -410,35 +434,13 @@ __device__ __forceinline__ bool fq_feasible64(const double* sP, double mse_limit
     const unsigned long long mf = __ballot(okf && b >= a), mw = __ballot(okw && b >= a);
     if (b == a) { rowf = mf; roww = mw; }
   }
-  auto row_of = [&](int l) {
-    return (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)rowf, l) |
-           ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rowf >> 32), l) << 32);
-  };
   unsigned long long r2 = 0, r3 = 0;
 #pragma unroll 8
-  for (int l = 0; l < 64; l++) r2 |= ((rowf >> l) & 1ull) ? row_of(l) : 0ull;
+  for (int l = 0; l < 64; l++) r2 |= ((rowf >> l) & 1ull) ? readlane_u64(rowf, l) : 0ull;
 #pragma unroll 8
-  for (int l = 0; l < 64; l++) r3 |= ((r2 >> l) & 1ull) ? row_of(l) : 0ull;
+  for (int l = 0; l < 64; l++) r3 |= ((r2 >> l) & 1ull) ? readlane_u64(rowf, l) : 0ull;
   return __ballot((r3 & roww) != 0ull) != 0ull;
 }
-
-// Sort keys are stored so that their order as IEEE doubles equals the wanted unsigned order: a
-// compare-exchange is then v_min_f64 + v_max_f64 (two instructions instead of a 64-bit compare and four
-// selects).  u >= 2^63 -> positive double with the same lower 63 bits; u < 2^63 -> ~u, a negative double
-// whose magnitude falls as u grows.  The upper word of u is float_sortable(slope) <= 0xFF800000 and
-// >= 0x387FFFFF (+ bias), so no encoded key has an all-ones exponent (no NaN, no infinity); +infinity is
-// the pad.
-// A bias of 2^20 on the upper word keeps the slope +0.0 (upper word 0x80000000) away from the denormal
-// doubles, so the result does not depend on the denormal mode of the min/max instructions.
-#define AT_KEY_BIAS 0x0010000000000000ull
-__device__ __forceinline__ unsigned long long key_enc(unsigned long long u) {
-  u += AT_KEY_BIAS;
-  return (u >> 63) ? (u ^ 0x8000000000000000ull) : ~u;
-}
-__device__ __forceinline__ unsigned long long key_dec(unsigned long long k) {
-  return ((k >> 63) ? ~k : (k | 0x8000000000000000ull)) - AT_KEY_BIAS;
-}
-#define AT_KEY_PAD 0x7FF0000000000000ull
 
 // Up to three network steps per pass: a thread owns a group of 2^r elements that is closed under r
 // consecutive steps (a flip followed by half-cleaners, or half-cleaners only), so every element is
@@ -837,23 +839,62 @@ __device__ __forceinline__ void fq_corner_search(const double* s_tab, const uint
 // Dynamic LDS layout: [0, 8*sort_cap) slope keys (later: raw/smoothed errors, then maxima candidates) |
 // FQ_TABLE_DOUBLES doubles for the group prefixes of the early-exit test (none in the one-wave class).  Clusters with size in (size_lo, size_hi] are processed by this
 // launch; those above sort_cap (only possible in the last class) sort in global scratch.
-FQ_TIMELINE_GLOBALS   // (tools_hooks.h: nothing in the product build)
-template <int NT, bool SPLIT>
-#ifndef FQ_EPT
 #define FQ_EPT(NT) ((NT) >= 256 ? 2 : 1)   // elements per lane in the moment sweep
-#endif
+#define FQ_REGSORT_MAX_LPOW 8   // one-wave class: clusters of up to 2^8 keys (pads included) sort in the wave's registers (fq_wave_sort)
 #define FQ_SEL_REGS 8          // maxima candidates per lane held in registers during the top-10 selection
 #define FQ_SMOOTH_REGS_OF(NT) ((NT) >= 1024 ? 8 : 16)   // smoothed errors per thread kept in registers (clusters up to that many x threads)
 #define FQ_TABLE_DOUBLES ((FQ_XG + 1) * 7)   // prefixes over FQ_XG groups, up to seven sums each
 // bytes of the key array region: the skewed keys, and at least the twelve pair tables + the 21 staged prefix rows that take the region over later
 #define FQ_KEY_BYTES(sort_cap) ((size_t)FQ_KP(sort_cap) * 8 > (size_t)(756 * 8) ? (size_t)FQ_KP(sort_cap) * 8 : (size_t)(756 * 8))   /* 756 = FQT_DOUBLES */
-#ifndef FQ_WPE_64
+// dynamic LDS of a launch with nt threads (the host's launch and the kernel's pointers both follow from this)
+#define FQ_LDS_BYTES(nt, sort_cap) (FQ_KEY_BYTES(sort_cap) + ((nt) > 64 ? (size_t)FQ_TABLE_DOUBLES * 8 : 0))
+// minimum waves per SIMD the register allocation must allow (second launch-bound argument)
 #define FQ_WPE_64 4
 #define FQ_WPE_128 4
 #define FQ_WPE_256 4
-#endif
-// (the body of k_fit_quads)
-__device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
+
+// A work item decoded (k_fit_quads and k_fit_prefilter; k_fit_small pipelines the same loads by hand): frame, the image the
+// gradients are read from -- the decimated working image, or the caller's frame at decimate 1 -- cluster record and points.
+struct FqItem {
+  int frame;
+  int gpitch;
+  const uint8_t* gray;
+  fit_gray_ptr ggray;   // gray in the global address space
+  ClusterRec cl;
+  const uint32_t* pts;
+};
+__device__ __forceinline__ FqItem fq_decode_item(uint32_t wi, const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
+                                                 const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
+                                                 const DetParams& P) {
+  FqItem it;
+  it.frame = (int)(wi >> P.wshift);
+  const FrameDesc fd = frames[it.frame];
+  it.gray = (P.decimate > 1) ? gray_all + (size_t)it.frame * P.H * P.WS : fd.img;
+  it.gpitch = (P.decimate > 1) ? P.WS : (int)fd.pitch;
+  it.ggray = (fit_gray_ptr)it.gray;
+  it.cl = clusters_all[(size_t)it.frame * P.ccap + (wi & ((1u << P.wshift) - 1u))];
+  it.pts = pts_all + (size_t)it.frame * P.pcap + it.cl.start;
+  return it;
+}
+
+// The local maxima of one ballot appended to the candidate list (values, and indices behind them): one LDS atomic per wave
+__device__ __forceinline__ void fq_push_maxima(bool is_max, double val, int idx, int* s_ncand, double* cand_val, int* cand_idx) {
+  const unsigned long long mm = __ballot(is_max);
+  if (mm) {
+    int kbase = 0;
+    if (lane_id() == 0) kbase = atomicAdd(s_ncand, (int)__popcll(mm));
+    kbase = __builtin_amdgcn_readfirstlane(kbase);
+    if (is_max) {
+      const int k = kbase + (int)__popcll(mm & ((1ull << lane_id()) - 1ull));
+      cand_val[k] = val;
+      cand_idx[k] = idx;
+    }
+  }
+}
+
+FQ_TIMELINE_GLOBALS   // (tools_hooks.h: nothing in the product build)
+template <int NT, bool SPLIT>
+__global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 : NT == 256 ? FQ_WPE_256 : 4)) void k_fit_quads(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
                                                    const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
                                                    const uint32_t* __restrict__ work, const uint32_t* __restrict__ work_n, uint32_t work_cap,
                                                    uint32_t* __restrict__ work_cursor, double* __restrict__ lf_scratch,
@@ -921,21 +962,17 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
     chunk_left--;
     FQ_TL_NEXT_CLUSTER()
     if (item >= nwork) break;
-    const uint32_t wi = (uint32_t)__builtin_amdgcn_readfirstlane((int)work[item]);
-    const int frame = (int)(wi >> P.wshift);
-    const FrameDesc fd = frames[frame];
-    const uint8_t* gray = (P.decimate > 1) ? gray_all + (size_t)frame * P.H * P.WS : fd.img;
-    const int gpitch = (P.decimate > 1) ? P.WS : (int)fd.pitch;
-    const __attribute__((address_space(1))) uint8_t* const ggray = (const __attribute__((address_space(1))) uint8_t*)gray;   // global, not generic
-    const ClusterRec cl = clusters_all[(size_t)frame * P.ccap + (wi & ((1u << P.wshift) - 1u))];
-    const int sz = (int)cl.count;
+    const FqItem fi = fq_decode_item((uint32_t)__builtin_amdgcn_readfirstlane((int)work[item]), frames, gray_all, pts_all, clusters_all, P);
+    const int frame = fi.frame, gpitch = fi.gpitch, sz = (int)fi.cl.count;
+    const uint8_t* const gray = fi.gray;
+    const fit_gray_ptr ggray = fi.ggray;
+    const uint32_t* const pts = fi.pts;
     FQ_TL_SIZE(sz)
     if (sz < 24 || sz > slot_cap) continue;   // (the work list only holds clusters of this class)
     FQ_TICK(0)
-    const uint32_t* pts = pts_all + (size_t)frame * P.pcap + cl.start;
 
     // ---- bbox and exact gradient dot -----------------------------------------------------------
-    int xmin = 1 << 30, xmax = -1, ymin = 1 << 30, ymax = -1;
+    FitBox box;
     long long sxg = 0, sgx = 0, sgy = 0;
     // (four independent loads per trip: one load per trip left the loop waiting a full memory latency per 64 points.
     // A lane without a point in some slot repeats its first point with a zero gradient, which changes neither the box
@@ -946,50 +983,41 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       for (int u = 0; u < 4; u++) pq[u] = pts[min(i + u * NT, sz - 1)];
       // gradient signs (-1, 0, 1) summed in 32 bits per trip (4 x 2^15 at most) with 24-bit multiplies, scaled by 255 once per
       // trip: as 64-bit multiply-adds per point this loop spent a third of its cycles in two quarter-rate instructions a point
-      int t_xg = 0, t_gx = 0, t_gy = 0;
+      FitDotPart t;
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const uint32_t p = (i + u * NT < sz) ? pq[u] : ((pq[0] & ~15u) | 5u);
-        const int x = (int)(p >> 18), y = (int)((p >> 4) & 0x3FFF);
-        const int gx = (int)((p >> 2) & 3) - 1, gy = (int)(p & 3) - 1;
-        xmin = min(xmin, x); xmax = max(xmax, x); ymin = min(ymin, y); ymax = max(ymax, y);
-        t_xg += __mul24(x, gx) + __mul24(y, gy);
-        t_gx += gx; t_gy += gy;
-      }
-      sxg += (long long)(t_xg * 255); sgx += t_gx * 255; sgy += t_gy * 255;
+      for (int u = 0; u < 4; u++) fit_box_add(box, t, i + u * NT < sz, pq[u], pq[0]);
+      sxg += (long long)(t.xg * 255); sgx += t.gx * 255; sgy += t.gy * 255;
     }
     // seven reductions, one barrier: every wave reduces on the DPP network and parks its results
-    xmin = wave_min_i(xmin); xmax = wave_max_i(xmax); ymin = wave_min_i(ymin); ymax = wave_max_i(ymax);
+    box.xmin = wave_min_i(box.xmin); box.xmax = wave_max_i(box.xmax); box.ymin = wave_min_i(box.ymin); box.ymax = wave_max_i(box.ymax);
     sxg = wave_sum_ll(sxg); sgx = wave_sum_ll(sgx); sgy = wave_sum_ll(sgy);
     if (NW > 1) {
       const int wv = tid >> 6;
       if (lane_id() == 0) {
-        s_box[wv][0] = xmin; s_box[wv][1] = xmax; s_box[wv][2] = ymin; s_box[wv][3] = ymax;
+        s_box[wv][0] = box.xmin; s_box[wv][1] = box.xmax; s_box[wv][2] = box.ymin; s_box[wv][3] = box.ymax;
         s_dot[wv][0] = sxg; s_dot[wv][1] = sgx; s_dot[wv][2] = sgy;
       }
       __syncthreads();
-      xmin = s_box[0][0]; xmax = s_box[0][1]; ymin = s_box[0][2]; ymax = s_box[0][3];
+      box.xmin = s_box[0][0]; box.xmax = s_box[0][1]; box.ymin = s_box[0][2]; box.ymax = s_box[0][3];
       sxg = s_dot[0][0]; sgx = s_dot[0][1]; sgy = s_dot[0][2];
       // (not unrolled for the 16-wave instance: the unrolled loads cost it 34 spilled registers, and a kernel that uses
       // scratch started 0.13 ms late)
       constexpr int kUnrollWaves = NW > 8 ? 1 : NW;
 #pragma unroll kUnrollWaves
       for (int w = 1; w < NW; w++) {
-        xmin = min(xmin, s_box[w][0]); xmax = max(xmax, s_box[w][1]); ymin = min(ymin, s_box[w][2]); ymax = max(ymax, s_box[w][3]);
+        box.xmin = min(box.xmin, s_box[w][0]); box.xmax = max(box.xmax, s_box[w][1]); box.ymin = min(box.ymin, s_box[w][2]); box.ymax = max(box.ymax, s_box[w][3]);
         sxg += s_dot[w][0]; sgx += s_dot[w][1]; sgy += s_dot[w][2];
       }
     }
-    if ((xmax - xmin) * (ymax - ymin) < P.min_tag_width) continue;
-    const double cxd = (xmin + xmax) * 0.5 + 0.05118, cyd = (ymin + ymax) * 0.5 + -0.028581;
-    const double dot = (double)sxg - cxd * (double)sgx - cyd * (double)sgy;
-    const int q_reversed = dot < 0;
-    if (!P.reversed_border && q_reversed) continue;
-    if (!P.normal_border && !q_reversed) continue;
+    if (fit_box_too_small(box, P)) continue;
+    const FitCentre ctr = fit_centre(box);
+    const int q_reversed = fit_border_reversed(ctr, (double)sxg, (double)sgx, (double)sgy);
+    if (fit_border_unwanted(q_reversed, P)) continue;
     FQ_TICK(1)
     FQ_STOP_AT(1)
 
     // ---- slope keys + sort -----------------------------------------------------------------------
-    const float cx = (float)cxd, cy = (float)cyd;
+    const float cx = (float)ctr.x, cy = (float)ctr.y;
     // only the largest class (FQ_NT_BIG threads) can meet clusters beyond its LDS key array: every smaller instance
     // addresses LDS unconditionally (no generic-address loads)
     const bool in_lds = NT < FQ_NT_BIG || sz <= sort_cap;
@@ -1001,17 +1029,7 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       for (int u = 0; u < 4; u++) {
       const int i = i4 + u * NT;
       if (i >= sz) break;
-      const uint32_t p = pq[u];
-      const int x = (int)(p >> 18), y = (int)((p >> 4) & 0x3FFF);
-      float dx = (float)x - cx, dy = (float)y - cy;
-      float quadrant;
-      if (dy > 0) quadrant = (dx > 0) ? 65536.0f : 131072.0f;
-      else quadrant = (dx > 0) ? 0.0f : -65536.0f;
-      if (dy < 0) { dy = -dy; dx = -dx; }
-      if (dx < 0) { float tmp = dx; dx = dy; dy = -tmp; }
-      const float slope = quadrant + __fdiv_rn(dy, dx);
-      const unsigned long long key = key_enc(((unsigned long long)float_sortable(slope) << 32) | ((unsigned long long)y << 18) |
-                                             ((unsigned long long)x << 4) | (unsigned long long)(p & 15u));
+      const unsigned long long key = fit_sort_key(fit_slope(pq[u], cx, cy), pq[u]);
       if (in_lds) skeys[FQ_KP(i)] = key; else gkeys[i] = key;
       }
     }
@@ -1024,9 +1042,6 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       for (int i = sz + tid; i < (1 << lpow); i += NT) skeys[FQ_KP(i)] = AT_KEY_PAD;
     __syncthreads();
     // (a wave's own LDS accesses are ordered: the one-wave class needs no barrier around the register sort)
-#ifndef FQ_REGSORT_MAX_LPOW
-#define FQ_REGSORT_MAX_LPOW 8
-#endif
     if (NT == 64 && padded && lpow <= FQ_REGSORT_MAX_LPOW) {
       if (lpow <= 6) fq_wave_sort<1>(skeys); else if (lpow == 7) fq_wave_sort<2>(skeys); else fq_wave_sort<4>(skeys);
     }
@@ -1071,28 +1086,13 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       int kept = 0;
       for (int i = i0; i < i1; i++) {
         const unsigned long long key = key_dec(in_lds ? skeys[FQ_KP(i)] : gkeys[i]);
-        const bool keep = (i == 0) || ((key >> 4) != (prev >> 4));
+        const bool keep = (i == 0) || fit_key_moved(key, prev);
         prev = key;
-        const uint32_t px = (uint32_t)((key >> 4) & 0x3FFF), py = (uint32_t)((key >> 18) & 0x3FFF);
+        const uint32_t px = fit_key_px(key), py = fit_key_py(key);
         uint32_t G = 0;   // squared gradient magnitude; 0 also stands for "no gradient taken" (weight 1 either way)
         if (keep) {
-          // x = px / 2 + 1/2 exactly; its integer part and the image offset stay in 32-bit integers (a frame spans
-          // less than 2^31 bytes, checked at submission), the four neighbours are loaded before the first is used
-          const double x = (int)(px + 1) * .5, y = (int)(py + 1) * .5;
-          const int ix = (int)((px + 1) >> 1), iy = (int)((py + 1) >> 1);
-          if (((unsigned)(ix - 1) < (unsigned)(W - 2)) & ((unsigned)(iy - 1) < (unsigned)(H - 2))) {
-            const uint32_t o = __umul24((uint32_t)iy, (uint32_t)gpitch) + (uint32_t)ix;   // (rows below 2^14, pitches below 2^24: check_images)
-            const int g_r = ggray[o + 1], g_l = ggray[o - 1], g_d = ggray[o + (uint32_t)gpitch], g_u = ggray[o - (uint32_t)gpitch];
-            const int grad_x = g_r - g_l, grad_y = g_d - g_u;
-            G = (uint32_t)(grad_x * grad_x + grad_y * grad_y);
-          }
-          const double Wt = sqrt_u18(G) + 1;
-          const double tt[6] = {Wt * x, Wt * y, Wt * x * x, Wt * x * y, Wt * y * y, Wt};
-#pragma unroll
-          for (int j = 0; j < 6; j++) {
-            const D2 t = split_term(tt[j]);
-            acc[j].hi += t.hi; acc[j].lo += t.lo;
-          }
+          G = fit_grad2(ggray, gpitch, px, py, W, H);
+          fit_terms_add(acc, G, px, py);
           kept++;
         }
         const unsigned long long stash = ((unsigned long long)(keep ? 1u : 0u) << 63) | ((unsigned long long)G << 28) |
@@ -1101,13 +1101,7 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       }
       // lane totals onto the grid (|lo| <= 2^-7), then the inclusive scans
       D2 incl[6];
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        const double c = (acc[j].lo + AT_SPLIT_C) - AT_SPLIT_C;
-        acc[j].hi += c; acc[j].lo -= c;
-        incl[j].hi = wave_scan_f64(acc[j].hi);
-        incl[j].lo = wave_scan_f64(acc[j].lo);
-      }
+      fit_scan_totals(acc, incl);
       int kincl = kept;
 #define OP(C, M) kincl += __builtin_amdgcn_update_dpp(0, kincl, C, M, 0xF, true);
       AT_DPP_STEPS(OP)
@@ -1168,15 +1162,9 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       for (int i = i0; i < i1; i++) {
         const unsigned long long st = in_lds ? skeys[FQ_KP(i)] : gkeys[i];
         if (st >> 63) {
-          const double x = (int)(((uint32_t)st & 0x3FFFu) + 1u) * .5, y = (int)(((uint32_t)(st >> 14) & 0x3FFFu) + 1u) * .5;
-          const double Wt = sqrt_u18((uint32_t)(st >> 28) & 0x3FFFFu) + 1;
-          const double tt[6] = {Wt * x, Wt * y, Wt * x * x, Wt * x * y, Wt * y * y, Wt};
+          fit_terms_add(off, (uint32_t)(st >> 28) & 0x3FFFFu, (uint32_t)st & 0x3FFFu, (uint32_t)(st >> 14) & 0x3FFFu);
 #pragma unroll
-          for (int j = 0; j < 6; j++) {
-            const D2 t = split_term(tt[j]);
-            off[j].hi += t.hi; off[j].lo += t.lo;
-            o[j] = off[j].hi + off[j].lo;
-          }
+          for (int j = 0; j < 6; j++) o[j] = off[j].hi + off[j].lo;
           o += 6;
         }
       }
@@ -1218,15 +1206,12 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
                 const int grad_y = (int)gray[(size_t)(iy + 1) * gpitch + ix] - (int)gray[(size_t)(iy - 1) * gpitch + ix];
                 Wt = __dsqrt_rn((double)(grad_x * grad_x + grad_y * grad_y)) + 1;
               }
+              double tt[6];
+              fit_moment_terms(Wt, x, y, tt);
               U96 t[6];
-              t[0] = u96_of(exact_to_fixed(Wt * x));
-              t[1] = u96_of(exact_to_fixed(Wt * y));
-              t[2] = u96_of(exact_to_fixed(Wt * x * x));
-              t[3] = u96_of(exact_to_fixed(Wt * x * y));
-              t[4] = u96_of(exact_to_fixed(Wt * y * y));
-              t[5] = u96_of(exact_to_fixed(Wt));
 #pragma unroll
               for (int j = 0; j < 6; j++) {
+                t[j] = u96_of(exact_to_fixed(tt[j]));
                 v[j] = u96_add(v[j], t[j]);
                 if (e == 1) t1[j] = t[j];
               }
@@ -1286,12 +1271,8 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
 #pragma unroll
           for (int j = 0; j < 6; j++) {
             w[j] = u128_add(u128_of(v[j]), carry[j]);
-            U128 t;
-            t.lo = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w[j].lo, 63) |
-                   ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w[j].lo >> 32), 63) << 32);
-            t.hi = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w[j].hi, 63) |
-                   ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w[j].hi >> 32), 63) << 32);
-            carry[j] = t;
+            carry[j].lo = readlane_u64(w[j].lo, 63);
+            carry[j].hi = readlane_u64(w[j].hi, 63);
           }
           cnt_carry += wcount;
         }
@@ -1339,8 +1320,7 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
 #pragma unroll
       for (int j = 0; j < 6; j++) tot[j] = lf[(size_t)(szd - 1) * 6 + j];
       for (int i = tid; i < szd; i += NT) {
-        const int i0 = (i >= ksz) ? i - ksz : i - ksz + szd;
-        const int i1 = (i + ksz < szd) ? i + ksz : i + ksz - szd;
+        const int i0 = fit_window_i0(i, ksz, szd), i1 = fit_window_i1(i, ksz, szd);
         const double2* pb = reinterpret_cast<const double2*>(lf + (size_t)i1 * 6);
         const double2 b0 = pb[0], b1 = pb[1], b2 = pb[2];
         const double b[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y};
@@ -1361,9 +1341,6 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
     }
     if (tid == 0) { s_ncand = 0; s_nkept = 0; }
     __syncthreads();
-    const float f0 = 0x1.6c0504p-7f, f1 = 0x1.152aaap-3f, f2 = 0x1.368b3p-1f;
-    const double F0 = (double)f0, F1 = (double)f1, F2 = (double)f2;
-    auto wrap = [szd](int k) { return k < 0 ? k + szd : (k >= szd ? k - szd : k); };
     double* cand_val = in_lds ? reinterpret_cast<double*>(skeys) : ea;
     int* cand_idx = in_lds ? reinterpret_cast<int*>(skeys + (sort_cap >> 1)) : reinterpret_cast<int*>(ea + (szd >> 1) + 1);
     constexpr int FQ_SMOOTH_REGS = FQ_SMOOTH_REGS_OF(NT);
@@ -1381,17 +1358,9 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
       for (int it = 0; it < FQ_SMOOTH_REGS; it++) {
         const int i = tid + it * NT;
         acc[it] = 0;
-        if (i < szd) {
-          double a2 = 0;
-          a2 += le[wrap(i - 3)] * F0;
-          a2 += le[wrap(i - 2)] * F1;
-          a2 += le[wrap(i - 1)] * F2;
-          a2 += le[i] * 1.0;
-          a2 += le[wrap(i + 1)] * F2;
-          a2 += le[wrap(i + 2)] * F1;
-          a2 += le[wrap(i + 3)] * F0;
-          acc[it] = a2;
-        }
+        if (i < szd)
+          acc[it] = fit_smooth7(le[fit_wrap(i - 3, szd)], le[fit_wrap(i - 2, szd)], le[fit_wrap(i - 1, szd)], le[i],
+                                le[fit_wrap(i + 1, szd)], le[fit_wrap(i + 2, szd)], le[fit_wrap(i + 3, szd)]);
       }
       __syncthreads();
 #pragma unroll
@@ -1404,41 +1373,19 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
 #pragma unroll
       for (int it = 0; it < FQ_SMOOTH_REGS; it++) {
         const int i = tid + it * NT;
-        if (i < szd) {
-          const double e = acc[it];
-          if (e > le[i + 1 < szd ? i + 1 : 0] && e > le[i > 0 ? i - 1 : szd - 1]) mx |= 1u << it;
-        }
+        if (i < szd && fit_is_max(acc[it], le[fit_next(i, szd)], le[fit_prev(i, szd)])) mx |= 1u << it;
       }
       __syncthreads();
 #pragma unroll
       for (int it = 0; it < FQ_SMOOTH_REGS; it++) {
         if (it * NT >= szd) break;
-        const bool is_max = (mx >> it) & 1u;
-        const unsigned long long mm = __ballot(is_max);
-        if (mm) {
-          int kbase = 0;
-          if (lane_id() == 0) kbase = atomicAdd(&s_ncand, (int)__popcll(mm));
-          kbase = __builtin_amdgcn_readfirstlane(kbase);
-          if (is_max) {
-            const int k = kbase + (int)__popcll(mm & ((1ull << lane_id()) - 1ull));
-            lcv[k] = acc[it];
-            lci[k] = tid + it * NT;
-          }
-        }
+        fq_push_maxima((mx >> it) & 1u, acc[it], tid + it * NT, &s_ncand, lcv, lci);
       }
     } else {
       double* eb = gerrs_b;
-      for (int i = tid; i < szd; i += NT) {
-        double acc = 0;
-        acc += ea[wrap(i - 3)] * F0;
-        acc += ea[wrap(i - 2)] * F1;
-        acc += ea[wrap(i - 1)] * F2;
-        acc += ea[i] * 1.0;
-        acc += ea[wrap(i + 1)] * F2;
-        acc += ea[wrap(i + 2)] * F1;
-        acc += ea[wrap(i + 3)] * F0;
-        eb[i] = acc;
-      }
+      for (int i = tid; i < szd; i += NT)
+        eb[i] = fit_smooth7(ea[fit_wrap(i - 3, szd)], ea[fit_wrap(i - 2, szd)], ea[fit_wrap(i - 1, szd)], ea[i],
+                            ea[fit_wrap(i + 1, szd)], ea[fit_wrap(i + 2, szd)], ea[fit_wrap(i + 3, szd)]);
       __syncthreads();
       for (int base = 0; base < szd; base += NT) {
         const int i = base + tid;
@@ -1446,19 +1393,9 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
         bool is_max = false;
         if (i < szd) {
           e = eb[i];
-          is_max = e > eb[i + 1 < szd ? i + 1 : 0] && e > eb[i > 0 ? i - 1 : szd - 1];
+          is_max = fit_is_max(e, eb[fit_next(i, szd)], eb[fit_prev(i, szd)]);
         }
-        const unsigned long long mm = __ballot(is_max);
-        if (mm) {
-          int kbase = 0;
-          if (lane_id() == 0) kbase = atomicAdd(&s_ncand, (int)__popcll(mm));
-          kbase = __builtin_amdgcn_readfirstlane(kbase);
-          if (is_max) {
-            const int k = kbase + (int)__popcll(mm & ((1ull << lane_id()) - 1ull));
-            cand_val[k] = e;
-            cand_idx[k] = i;
-          }
-        }
+        fq_push_maxima(is_max, e, i, &s_ncand, cand_val, cand_idx);
       }
     }
     FQ_TICK(5)
@@ -1479,15 +1416,12 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
         const int myi = have ? cand_idx[lane] : -1;
         int rank = 0;
         for (int l = 0; l < nmaxima; l++) {
-          const unsigned long long ok =
-              (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)myk, l) |
-              ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(myk >> 32), l) << 32);
+          const unsigned long long ok = readlane_u64(myk, l);
           rank += (ok > myk || (ok == myk && l < lane)) ? 1 : 0;
         }
         const unsigned long long tmask = __ballot(have && rank == P.max_nmaxima);
         const int tl = (int)__ffsll((long long)tmask) - 1;
-        const unsigned long long tk = (unsigned long long)(uint32_t)__shfl((int)(uint32_t)myk, tl, 64) |
-                                      ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(myk >> 32), tl, 64) << 32);
+        const unsigned long long tk = shfl_u64(myk, tl);
         const bool kept = have && rank < P.max_nmaxima && myk > tk;
         const unsigned long long kmask = __ballot(kept);
         if (kept) s_maxidx[__popcll(kmask & ((1ull << lane) - 1ull))] = myi;
@@ -1521,8 +1455,7 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
           if (lane == round) { rem_key = mk; rem_k = src + 64 * wr; }
         }
         // threshold = key of the last round; keep the earlier winners that are strictly larger
-        const unsigned long long tk = (unsigned long long)(uint32_t)__shfl((int)(uint32_t)rem_key, P.max_nmaxima, 64) |
-                                      ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(rem_key >> 32), P.max_nmaxima, 64) << 32);
+        const unsigned long long tk = shfl_u64(rem_key, P.max_nmaxima);
         const bool kept = lane < P.max_nmaxima && rem_key > tk;
         const unsigned long long kmask = __ballot(kept);
         if (kept) s_maxidx[__popcll(kmask & ((1ull << lane) - 1ull))] = cand_idx[rem_k];
@@ -1581,7 +1514,7 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
     // loads, round after round: the phase is ~15 us of the ~40 us every cluster of the one-wave class costs, mostly waiting.)
     double* const s_rows = s_tab + FQT_ROWS;   // [2 m + 1][6]: rows 0 .. m-1 at the maxima, m .. 2m-1 before them, 2m the last row
     for (int r = tid; r < 2 * m + 1; r += NT) {
-      const int src = r < m ? s_maxidx[r] : r < 2 * m ? s_maxidx[r - m] - 1 : szd - 1;
+      const int src = fit_staged_row_src(r, m, s_maxidx, szd);
       double row[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (before point 0: nothing; the fit does not subtract it)
       if (src >= 0) {
         const double* g = lf + (size_t)src * 6;
@@ -1602,23 +1535,9 @@ __device__ __forceinline__ void fit_quads_body(const FrameDesc* __restrict__ fra
     }
     __syncthreads();
     // wave 0 alone, without workgroup barriers (the other waves go on to the barrier at the top of the cluster loop)
-    if (tid < 64) fq_corner_search(s_tab, s_cpairs, m, szd, tid, P, cands_all, counters, frame, cl.key, q_reversed);
+    if (tid < 64) fq_corner_search(s_tab, s_cpairs, m, szd, tid, P, cands_all, counters, frame, fi.cl.key, q_reversed);
     FQ_TICK(7)
   }
-}
-
-// second launch-bound argument = minimum waves per SIMD the register allocation must allow
-template <int NT, bool SPLIT>
-__global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 : NT == 256 ? FQ_WPE_256 : 4)) void k_fit_quads(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
-                                                   const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
-                                                   const uint32_t* __restrict__ work, const uint32_t* __restrict__ work_n, uint32_t work_cap,
-                                                   uint32_t* __restrict__ work_cursor, double* __restrict__ lf_scratch,
-                                                   unsigned long long* __restrict__ keys_scratch, double* __restrict__ errs_scratch,
-                                                   FitCand* __restrict__ cands_all, FrameCounters* __restrict__ counters,
-                                                   unsigned long long* __restrict__ prof, int sort_cap, int slot_cap,
-                                                   int pop, DetParams P) {
-  fit_quads_body<NT, SPLIT>(frames, gray_all, pts_all, clusters_all, work, work_n, work_cap, work_cursor, lf_scratch, keys_scratch, errs_scratch,
-                            cands_all, counters, prof, sort_cap, slot_cap, pop, P);
 }
 
 // ---- k_fit_prefilter: the cheap exits of the quad fit for the clusters of the large classes, ahead of k_fit_quads ---------
@@ -1683,62 +1602,47 @@ __global__ __launch_bounds__(FQ_PF_NT) void k_fit_prefilter(const FrameDesc* __r
       }
     }
     const uint32_t wi = (uint32_t)__builtin_amdgcn_readfirstlane((int)work[widx]);
-    const int frame = (int)(wi >> P.wshift);
-    const FrameDesc fd = frames[frame];
-    const uint8_t* gray = (P.decimate > 1) ? gray_all + (size_t)frame * P.H * P.WS : fd.img;
-    const int gpitch = (P.decimate > 1) ? P.WS : (int)fd.pitch;
-    const __attribute__((address_space(1))) uint8_t* const ggray = (const __attribute__((address_space(1))) uint8_t*)gray;
-    const ClusterRec cl = clusters_all[(size_t)frame * P.ccap + (wi & ((1u << P.wshift) - 1u))];
-    const int sz = (int)cl.count;
-    const uint32_t* pts = pts_all + (size_t)frame * P.pcap + cl.start;
+    const FqItem item = fq_decode_item(wi, frames, gray_all, pts_all, clusters_all, P);
+    const int gpitch = item.gpitch, sz = (int)item.cl.count;
+    const fit_gray_ptr ggray = item.ggray;
+    const uint32_t* const pts = item.pts;
 
-    // bounding box and exact gradient dot: the statements of k_fit_quads
-    int xmin = 1 << 30, xmax = -1, ymin = 1 << 30, ymax = -1;
+    // bounding box and exact gradient dot
+    FitBox box;
     long long sxg = 0, sgx = 0, sgy = 0;
     for (int i = tid; i < sz; i += 8 * FQ_PF_NT) {   // (eight independent loads per trip)
       uint32_t pq[8];
 #pragma unroll
       for (int u = 0; u < 8; u++) pq[u] = pts[min(i + u * FQ_PF_NT, sz - 1)];
       // gradient signs (-1, 0, 1) summed in 32 bits per trip (8 x 2^14 at most), scaled by 255 once per trip
-      int t_xg = 0, t_gx = 0, t_gy = 0;
+      FitDotPart t;
 #pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const uint32_t p = (i + u * FQ_PF_NT < sz) ? pq[u] : ((pq[0] & ~15u) | 5u);
-        const int x = (int)(p >> 18), y = (int)((p >> 4) & 0x3FFF);
-        const int gx = (int)((p >> 2) & 3) - 1, gy = (int)(p & 3) - 1;
-        xmin = min(xmin, x); xmax = max(xmax, x); ymin = min(ymin, y); ymax = max(ymax, y);
-        t_xg += __mul24(x, gx) + __mul24(y, gy);
-        t_gx += gx; t_gy += gy;
-      }
-      sxg += (long long)(t_xg * 255); sgx += t_gx * 255; sgy += t_gy * 255;
+      for (int u = 0; u < 8; u++) fit_box_add(box, t, i + u * FQ_PF_NT < sz, pq[u], pq[0]);
+      sxg += (long long)(t.xg * 255); sgx += t.gx * 255; sgy += t.gy * 255;
     }
-    xmin = wave_min_i(xmin); xmax = wave_max_i(xmax); ymin = wave_min_i(ymin); ymax = wave_max_i(ymax);
+    box.xmin = wave_min_i(box.xmin); box.xmax = wave_max_i(box.xmax); box.ymin = wave_min_i(box.ymin); box.ymax = wave_max_i(box.ymax);
     sxg = wave_sum_ll(sxg); sgx = wave_sum_ll(sgx); sgy = wave_sum_ll(sgy);
     {
       const int wv = tid >> 6;
       if (lane_id() == 0) {
-        s_box[wv][0] = xmin; s_box[wv][1] = xmax; s_box[wv][2] = ymin; s_box[wv][3] = ymax;
+        s_box[wv][0] = box.xmin; s_box[wv][1] = box.xmax; s_box[wv][2] = box.ymin; s_box[wv][3] = box.ymax;
         s_dot[wv][0] = sxg; s_dot[wv][1] = sgx; s_dot[wv][2] = sgy;
       }
       for (int t = tid; t < (64 + 1) * 7; t += FQ_PF_NT) sB[t] = 0.0;
       __syncthreads();
-      xmin = s_box[0][0]; xmax = s_box[0][1]; ymin = s_box[0][2]; ymax = s_box[0][3];
+      box.xmin = s_box[0][0]; box.xmax = s_box[0][1]; box.ymin = s_box[0][2]; box.ymax = s_box[0][3];
       sxg = s_dot[0][0]; sgx = s_dot[0][1]; sgy = s_dot[0][2];
 #pragma unroll
       for (int w = 1; w < FQ_PF_NT / 64; w++) {
-        xmin = min(xmin, s_box[w][0]); xmax = max(xmax, s_box[w][1]); ymin = min(ymin, s_box[w][2]); ymax = max(ymax, s_box[w][3]);
+        box.xmin = min(box.xmin, s_box[w][0]); box.xmax = max(box.xmax, s_box[w][1]); box.ymin = min(box.ymin, s_box[w][2]); box.ymax = max(box.ymax, s_box[w][3]);
         sxg += s_dot[w][0]; sgx += s_dot[w][1]; sgy += s_dot[w][2];
       }
     }
     PF_TICK(60)
-    bool reject = (xmax - xmin) * (ymax - ymin) < P.min_tag_width;
-    const double cxd = (xmin + xmax) * 0.5 + 0.05118, cyd = (ymin + ymax) * 0.5 + -0.028581;
-    const double dot = (double)sxg - cxd * (double)sgx - cyd * (double)sgy;
-    const int q_reversed = dot < 0;
-    if (!P.reversed_border && q_reversed) reject = true;
-    if (!P.normal_border && !q_reversed) reject = true;
+    const FitCentre ctr = fit_centre(box);
+    bool reject = fit_box_too_small(box, P) || fit_border_unwanted(fit_border_reversed(ctr, (double)sxg, (double)sgx, (double)sgy), P);
     if (!reject && P.split_moments) {   // (the sector sums assume the fast path's coordinate range; larger images skip the test)
-      const float cx = (float)cxd, cy = (float)cyd;
+      const float cx = (float)ctr.x, cy = (float)ctr.y;
       double a[7];
       int cur = -1;
       auto flush = [&]() {
@@ -1761,35 +1665,15 @@ __global__ __launch_bounds__(FQ_PF_NT) void k_fit_prefilter(const FrameDesc* __r
         // squared gradients of the eight points first (32 independent byte gathers in flight)
         uint32_t GG[8];
 #pragma unroll
-        for (int e = 0; e < 8; e++) {
-          const uint32_t p = pp[e];
-          const uint32_t px = p >> 18, py = (p >> 4) & 0x3FFFu;
-          const int ix = (int)((px + 1) >> 1), iy = (int)((py + 1) >> 1);
-          GG[e] = 0;
-          if ((base + tid * 8 + e < sz) & ((unsigned)(ix - 1) < (unsigned)(W - 2)) & ((unsigned)(iy - 1) < (unsigned)(H - 2))) {
-            const uint32_t o = __umul24((uint32_t)iy, (uint32_t)gpitch) + (uint32_t)ix;   // (rows below 2^14, pitches below 2^24: check_images)
-            const int g_r = ggray[o + 1], g_l = ggray[o - 1], g_d = ggray[o + (uint32_t)gpitch], g_u = ggray[o - (uint32_t)gpitch];
-            const int grad_x = g_r - g_l, grad_y = g_d - g_u;
-            GG[e] = (uint32_t)(grad_x * grad_x + grad_y * grad_y);
-          }
-        }
+        for (int e = 0; e < 8; e++)
+          GG[e] = fit_grad2(ggray, gpitch, (uint32_t)fit_point_x(pp[e]), (uint32_t)fit_point_y(pp[e]), W, H, base + tid * 8 + e < sz);
 #pragma unroll
         for (int e = 0; e < 8; e++) {
           if (base + tid * 8 + e >= sz) break;
-          const uint32_t p = pp[e];
-          const int xi = (int)(p >> 18), yi = (int)((p >> 4) & 0x3FFF);
-          // slope key of k_fit_quads (same float statements)
-          float dx = (float)xi - cx, dy = (float)yi - cy;
-          float quadrant;
-          if (dy > 0) quadrant = (dx > 0) ? 65536.0f : 131072.0f;
-          else quadrant = (dx > 0) ? 0.0f : -65536.0f;
-          if (dy < 0) { dy = -dy; dx = -dx; }
-          if (dx < 0) { float tmp = dx; dx = dy; dy = -tmp; }
-          const float slope = quadrant + __fdiv_rn(dy, dx);
-          const int sec = fq_sector64(slope);
-          const uint32_t px = (uint32_t)xi, py = (uint32_t)yi;
-          const double x = (int)(px + 1) * .5, y = (int)(py + 1) * .5;
-          const double Wt = sqrt_u18(GG[e]) + 1;
+          const int sec = fq_sector64(fit_slope(pp[e], cx, cy));
+          const uint32_t px = (uint32_t)fit_point_x(pp[e]), py = (uint32_t)fit_point_y(pp[e]);
+          const double x = fit_coord(px), y = fit_coord(py);
+          const double Wt = fit_weight(GG[e]);
           const double wl = (px & py & 1u) ? 0.5 * Wt : Wt;
           if (sec != cur) {
             if (cur >= 0) flush();

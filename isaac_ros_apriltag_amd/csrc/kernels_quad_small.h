@@ -1,6 +1,7 @@
 // kernels_quad_small.h -- S5 quad fitting for the SMALL clusters (at most 64 K boundary points, K = 2 or 4), the bulk of a
 // noisy frame's clusters (inside cuAprilTagsDetect, reference src/apriltag_node.cpp:491-493).
-// Same statements and the same results, bit for bit, as k_fit_quads (kernels_quad.h); what differs is where the data lives:
+// The statements of fit_statements.h and so the same results, bit for bit, as k_fit_quads (kernels_quad.h); what differs is where
+// the data lives:
 //   * a lane loads its K points ONCE and keeps them in registers through bounding box, border direction and slope keys;
 //   * the keys never touch LDS: the bitonic network runs on the registers (partner keys over ds_bpermute), and after it
 //     lane l holds the sorted positions l K .. l K + K - 1 -- exactly the lane-contiguous runs the moment sweep walks;
@@ -28,18 +29,16 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   return __builtin_amdgcn_readlane(v, 63);
 }
 
-#ifndef FS_WPE
 #define FS_WPE 4   // waves per SIMD the register allocation must allow
-#endif
 #define FS_TAB_BYTES (FQT_DOUBLES * 8)   // pair tables + staged moment rows
 // LDS of a workgroup: moments [64 K][6] | errors [64 K], the tables over the moments once they are dead
 #define FS_LDS_BYTES(K) ((64 * (K) * 56) > FS_TAB_BYTES ? (64 * (K) * 56) : FS_TAB_BYTES)
 
 template <int K>
-__device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
+__global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
                                                           const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
                                                           const uint32_t* __restrict__ work, const uint32_t* __restrict__ work_n, uint32_t work_cap,
-                                                          uint32_t* __restrict__ work_cursor, double* __restrict__ lf_scratch, FitCand* __restrict__ cands_all,
+                                                          uint32_t* __restrict__ work_cursor, FitCand* __restrict__ cands_all,
                                                           FrameCounters* __restrict__ counters, int pop, DetParams P) {
   constexpr int CAP = 64 * K;
   extern __shared__ __attribute__((aligned(16))) unsigned char fs_smem[];
@@ -122,7 +121,7 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
                                            : reinterpret_cast<const uint8_t*>(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.img_v[1]) << 32) |
                                                                               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.img_v[0]));
     const int gpitch = (P.decimate > 1) ? P.WS : __builtin_amdgcn_readfirstlane((int)cur.img_v[2]);
-    const __attribute__((address_space(1))) uint8_t* const ggray = (const __attribute__((address_space(1))) uint8_t*)gray;
+    const fit_gray_ptr ggray = (fit_gray_ptr)gray;
     const unsigned long long cl_key = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.rec_v[1]) << 32) |
                                       (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.rec_v[0]);
     const int sz = __builtin_amdgcn_readfirstlane((int)cur.rec_v[3]);
@@ -134,47 +133,35 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
     uint32_t pp[K];
 #pragma unroll
     for (int j = 0; j < K; j++) pp[j] = cur.pp[j];
-    int xmin = 1 << 30, xmax = -1, ymin = 1 << 30, ymax = -1;
+    FitBox box;
     int sxg = 0, sg = 0;   // sums of x sgn(gx) + y sgn(gy) and of the packed signs (sgn(gx) << 16) + sgn(gy): |sums| < 2^24, 2^9
 #pragma unroll
     for (int j = 0; j < K; j++) {
       // a lane without a point in this slot repeats a point of the cluster with a zero gradient (neither box nor sums change)
-      const uint32_t p = (lane + 64 * j < sz) ? pp[j] : ((pp[0] & ~15u) | 5u);
-      const int x = (int)(p >> 18), y = (int)((p >> 4) & 0x3FFF);
-      const int gx = (int)((p >> 2) & 3) - 1, gy = (int)(p & 3) - 1;
-      xmin = min(xmin, x); xmax = max(xmax, x); ymin = min(ymin, y); ymax = max(ymax, y);
+      const uint32_t p = (lane + 64 * j < sz) ? pp[j] : fit_pad_point(pp[0]);
+      const int x = fit_point_x(p), y = fit_point_y(p);
+      const int gx = fit_point_sgx(p), gy = fit_point_sgy(p);
+      box.xmin = min(box.xmin, x); box.xmax = max(box.xmax, x); box.ymin = min(box.ymin, y); box.ymax = max(box.ymax, y);
       sxg += __mul24(x, gx) + __mul24(y, gy);
       sg += gx * 65536 + gy;
     }
-    xmin = wave_min_i(xmin); xmax = wave_max_i(xmax); ymin = wave_min_i(ymin); ymax = wave_max_i(ymax);
+    box.xmin = wave_min_i(box.xmin); box.xmax = wave_max_i(box.xmax); box.ymin = wave_min_i(box.ymin); box.ymax = wave_max_i(box.ymax);
     sxg = wave_sum_i(sxg); sg = wave_sum_i(sg);
-    if ((xmax - xmin) * (ymax - ymin) < P.min_tag_width) break;
+    if (fit_box_too_small(box, P)) break;
     const int sgy_s = (int)(short)(sg & 0xFFFF), sgx_s = (sg - sgy_s) >> 16;
-    const double cxd = (xmin + xmax) * 0.5 + 0.05118, cyd = (ymin + ymax) * 0.5 + -0.028581;
     // (the gradients are +-255: the integer sums of k_fit_quads are 255 times these, exactly)
-    const double dot = (double)(255LL * sxg) - cxd * (double)(255 * sgx_s) - cyd * (double)(255 * sgy_s);
-    const int q_reversed = dot < 0;
-    if (!P.reversed_border && q_reversed) break;
-    if (!P.normal_border && !q_reversed) break;
+    const FitCentre ctr = fit_centre(box);
+    const int q_reversed = fit_border_reversed(ctr, (double)(255LL * sxg), (double)(255 * sgx_s), (double)(255 * sgy_s));
+    if (fit_border_unwanted(q_reversed, P)) break;
 
     stage2(nxt); pf = 2;
     AT_MARK("keys")
-    // ---- slope keys (the statements of k_fit_quads) and the sort, in registers ---------------------------------------
-    const float cx = (float)cxd, cy = (float)cyd;
+    // ---- slope keys and the sort, in registers -----------------------------------------------------------------------
+    const float cx = (float)ctr.x, cy = (float)ctr.y;
     unsigned long long v[K];
 #pragma unroll
     for (int j = 0; j < K; j++) {
-      const uint32_t p = pp[j];
-      const int x = (int)(p >> 18), y = (int)((p >> 4) & 0x3FFF);
-      float dx = (float)x - cx, dy = (float)y - cy;
-      float quadrant;
-      if (dy > 0) quadrant = (dx > 0) ? 65536.0f : 131072.0f;
-      else quadrant = (dx > 0) ? 0.0f : -65536.0f;
-      if (dy < 0) { dy = -dy; dx = -dx; }
-      if (dx < 0) { float tmp = dx; dx = dy; dy = -tmp; }
-      const float slope = quadrant + __fdiv_rn(dy, dx);
-      const unsigned long long key = key_enc(((unsigned long long)float_sortable(slope) << 32) | ((unsigned long long)y << 18) |
-                                             ((unsigned long long)x << 4) | (unsigned long long)(p & 15u));
+      const unsigned long long key = fit_sort_key(fit_slope(pp[j], cx, cy), pp[j]);
       v[j] = (lane + 64 * j < sz) ? key : AT_KEY_PAD;
     }
     AT_MARK("sort")
@@ -199,26 +186,13 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
     for (int j = 0; j < K; j++) {
       const int i = lane * K + j;
       const unsigned long long key = key_dec(v[j]);
-      const bool keep = (i < sz) && ((i == 0) || ((key >> 4) != (prev >> 4)));
+      const bool keep = (i < sz) && ((i == 0) || fit_key_moved(key, prev));
       prev = key;
-      const uint32_t px = (uint32_t)((key >> 4) & 0x3FFF), py = (uint32_t)((key >> 18) & 0x3FFF);
+      const uint32_t px = fit_key_px(key), py = fit_key_py(key);
       uint32_t G = 0;
       if (keep) {
-        const double x = (int)(px + 1) * .5, y = (int)(py + 1) * .5;
-        const int ix = (int)((px + 1) >> 1), iy = (int)((py + 1) >> 1);
-        if (((unsigned)(ix - 1) < (unsigned)(W - 2)) & ((unsigned)(iy - 1) < (unsigned)(H - 2))) {
-          const uint32_t o = __umul24((uint32_t)iy, (uint32_t)gpitch) + (uint32_t)ix;   // (rows below 2^14, pitches below 2^24: check_images)
-          const int g_r = ggray[o + 1], g_l = ggray[o - 1], g_d = ggray[o + (uint32_t)gpitch], g_u = ggray[o - (uint32_t)gpitch];
-          const int grad_x = g_r - g_l, grad_y = g_d - g_u;
-          G = (uint32_t)(grad_x * grad_x + grad_y * grad_y);
-        }
-        const double Wt = sqrt_u18(G) + 1;
-        const double tt[6] = {Wt * x, Wt * y, Wt * x * x, Wt * x * y, Wt * y * y, Wt};
-#pragma unroll
-        for (int m = 0; m < 6; m++) {
-          const D2 t = split_term(tt[m]);
-          acc[m].hi += t.hi; acc[m].lo += t.lo;
-        }
+        G = fit_grad2(ggray, gpitch, px, py, W, H);
+        fit_terms_add(acc, G, px, py);
         kept++;
       }
       st_xy[j] = ((keep ? 1u : 0u) << 31) | (py << 14) | px;
@@ -226,13 +200,9 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
     }
     AT_MARK("scan")
     D2 off[6];
+    fit_scan_totals(acc, off);
 #pragma unroll
-    for (int j = 0; j < 6; j++) {
-      const double c = (acc[j].lo + AT_SPLIT_C) - AT_SPLIT_C;
-      acc[j].hi += c; acc[j].lo -= c;
-      off[j].hi = wave_scan_f64(acc[j].hi) - acc[j].hi;
-      off[j].lo = wave_scan_f64(acc[j].lo) - acc[j].lo;
-    }
+    for (int j = 0; j < 6; j++) { off[j].hi -= acc[j].hi; off[j].lo -= acc[j].lo; }   // exclusive
     int kincl = kept;
 #define OP(C, M) kincl += __builtin_amdgcn_update_dpp(0, kincl, C, M, 0xF, true);
     AT_DPP_STEPS(OP)
@@ -244,16 +214,10 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
 #pragma unroll
     for (int j = 0; j < K; j++) {
       if (st_xy[j] >> 31) {
-        const double x = (int)((st_xy[j] & 0x3FFFu) + 1u) * .5, y = (int)(((st_xy[j] >> 14) & 0x3FFFu) + 1u) * .5;
-        const double Wt = sqrt_u18(st_g[j]) + 1;
-        const double tt[6] = {Wt * x, Wt * y, Wt * x * x, Wt * x * y, Wt * y * y, Wt};
+        fit_terms_add(off, st_g[j], st_xy[j] & 0x3FFFu, (st_xy[j] >> 14) & 0x3FFFu);
         double r[6];
 #pragma unroll
-        for (int m = 0; m < 6; m++) {
-          const D2 t = split_term(tt[m]);
-          off[m].hi += t.hi; off[m].lo += t.lo;
-          r[m] = off[m].hi + off[m].lo;
-        }
+        for (int m = 0; m < 6; m++) r[m] = off[m].hi + off[m].lo;
         double2* const o = reinterpret_cast<double2*>(rows + pos * 6);
         o[0] = make_double2(r[0], r[1]); o[1] = make_double2(r[2], r[3]); o[2] = make_double2(r[4], r[5]);
         pos++;
@@ -271,32 +235,19 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
       const int i = lane + it * 64;
       if (i < szd) {
         double e;
-        const int i0 = (i >= ksz) ? i - ksz : i - ksz + szd;
-        const int i1 = (i + ksz < szd) ? i + ksz : i + ksz - szd;
-        fit_line_dev(rows, szd, i0, i1, nullptr, &e, nullptr);
+        fit_line_dev(rows, szd, fit_window_i0(i, ksz, szd), fit_window_i1(i, ksz, szd), nullptr, &e, nullptr);
         errs[i] = e;
       }
     }
     __syncthreads();
     AT_MARK("smooth")
-    const float f0 = 0x1.6c0504p-7f, f1 = 0x1.152aaap-3f, f2 = 0x1.368b3p-1f;
-    const double F0 = (double)f0, F1 = (double)f1, F2 = (double)f2;
-    auto wrap = [szd](int k) { return k < 0 ? k + szd : (k >= szd ? k - szd : k); };
 #pragma unroll
     for (int it = 0; it < K; it++) {
       const int i = lane + it * 64;
       sm[it] = 0;
-      if (i < szd) {
-        double a2 = 0;
-        a2 += errs[wrap(i - 3)] * F0;
-        a2 += errs[wrap(i - 2)] * F1;
-        a2 += errs[wrap(i - 1)] * F2;
-        a2 += errs[i] * 1.0;
-        a2 += errs[wrap(i + 1)] * F2;
-        a2 += errs[wrap(i + 2)] * F1;
-        a2 += errs[wrap(i + 3)] * F0;
-        sm[it] = a2;
-      }
+      if (i < szd)
+        sm[it] = fit_smooth7(errs[fit_wrap(i - 3, szd)], errs[fit_wrap(i - 2, szd)], errs[fit_wrap(i - 1, szd)], errs[i],
+                             errs[fit_wrap(i + 1, szd)], errs[fit_wrap(i + 2, szd)], errs[fit_wrap(i + 3, szd)]);
     }
     __syncthreads();
 #pragma unroll
@@ -309,10 +260,7 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
 #pragma unroll
     for (int it = 0; it < K; it++) {
       const int i = lane + it * 64;
-      if (i < szd) {
-        const double e = sm[it];
-        if (e > errs[i + 1 < szd ? i + 1 : 0] && e > errs[i > 0 ? i - 1 : szd - 1]) mx |= 1u << it;
-      }
+      if (i < szd && fit_is_max(sm[it], errs[fit_next(i, szd)], errs[fit_prev(i, szd)])) mx |= 1u << it;
     }
     __syncthreads();
     // the maxima, in ascending index order: values in errs[0 ..), indices behind them
@@ -353,9 +301,7 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
       for (int r2 = 0; r2 < KR; r2++) {
         const int n2 = min(64, nmaxima - 64 * r2);
         for (int l = 0; l < n2; l++) {
-          const unsigned long long ok =
-              (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)myk[r2], l) |
-              ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(myk[r2] >> 32), l) << 32);
+          const unsigned long long ok = readlane_u64(myk[r2], l);
 #pragma unroll
           for (int r = 0; r < KR; r++) rank[r] += (ok > myk[r] || (ok == myk[r] && (r2 < r || (r2 == r && l < lane)))) ? 1 : 0;
         }
@@ -367,8 +313,7 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
         const unsigned long long tmask = __ballot(myk[r] != 0ull && rank[r] == P.max_nmaxima);
         if (tmask) {
           const int tl = (int)__ffsll((long long)tmask) - 1;
-          tk = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)myk[r], tl) |
-               ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(myk[r] >> 32), tl) << 32);
+          tk = readlane_u64(myk[r], tl);
         }
       }
       m = 0;
@@ -391,7 +336,7 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
     {
       double row[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       if (lane < 2 * m + 1) {
-        const int src = lane < m ? s_maxidx[lane] : lane < 2 * m ? s_maxidx[lane - m] - 1 : szd - 1;
+        const int src = fit_staged_row_src(lane, m, s_maxidx, szd);
         if (src >= 0) {
 #pragma unroll
           for (int j = 0; j < 6; j++) row[j] = rows[src * 6 + j];
@@ -416,14 +361,4 @@ __device__ __forceinline__ void fit_small_body(const FrameDesc* __restrict__ fra
     if (pf < 3) stage3(nxt);
     cur = nxt;
   }
-}
-
-// (lf_scratch: unused)
-template <int K>
-__global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __restrict__ frames, const uint8_t* __restrict__ gray_all,
-                                                          const uint32_t* __restrict__ pts_all, const ClusterRec* __restrict__ clusters_all,
-                                                          const uint32_t* __restrict__ work, const uint32_t* __restrict__ work_n, uint32_t work_cap,
-                                                          uint32_t* __restrict__ work_cursor, double* __restrict__ lf_scratch, FitCand* __restrict__ cands_all,
-                                                          FrameCounters* __restrict__ counters, int pop, DetParams P) {
-  fit_small_body<K>(frames, gray_all, pts_all, clusters_all, work, work_n, work_cap, work_cursor, lf_scratch, cands_all, counters, pop, P);
 }

@@ -215,3 +215,14 @@ def test_packed_gradient_sign_sums():
         sgy = low - 65536 if low >= 32768 else low                  # (int)(short)
         sgx = (sg32 - sgy) >> 16
         assert (sgx, sgy) == (sum(gx), sum(gy))
+
+
+def test_fit_constants_are_stated_once():
+    """The quad fit's arithmetic is stated once, in csrc/fit_statements.h, for the three kernels that need it (k_fit_quads,
+    k_fit_prefilter, k_fit_small): the constants that mark a retyped copy -- the two centre offsets, the first Gaussian tap,
+    the last quadrant band of the slope and the third moment term -- each occur in exactly one file under csrc/, once."""
+    csrc = os.path.join(os.path.dirname(HERE), "isaac_ros_apriltag_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".c", ".cpp"))}
+    for lit in ("0.05118", "0.028581", "0x1.6c0504p-7f", "131072.0f", "Wt * x * x"):
+        hits = {f: t.count(lit) for f, t in texts.items() if lit in t}
+        assert sum(hits.values()) == 1, (lit, hits)
