@@ -274,6 +274,21 @@ int amdAprilTagsSetFrameSkews(amdAprilTagsHandle handle, uint32_t n, const float
  * (amdAprilTagsDebugGraphReplay reports it).  Set it once after create, or rarely. */
 int amdAprilTagsSetQuadSigma(amdAprilTagsHandle handle, float quad_sigma);
 
+/* Per-frame image sizes: mixed camera rigs and windows (regions of interest) in one submission.  Off (the default), every image of a
+ * submission must have exactly the handle's width x height (AMDAT_SIZE_MISMATCH otherwise).  On, frame i is images[i].width x
+ * images[i].height, any size with 1 <= width <= cfg.width, 1 <= height <= cfg.height whose working image (1 + (size - 1) / decimate
+ * in each direction) has at least tile_size pixels both ways; a frame outside that range returns AMDAT_SIZE_MISMATCH with nothing
+ * enqueued, and the pitch checks apply to every frame's own width.  The records of every frame are those of a handle of that
+ * frame's size given that frame alone: everything the algorithm derives from the image size (tiles, bounds, the cluster-size cap,
+ * quad_sigma's edge rules, the order of the records) follows the frame; memory, capacities and the launch schedule stay those of the
+ * handle's size (DESIGN.md sections 3 and 4).  A window is a frame whose dev_ptr points at its first pixel inside a larger image and
+ * whose pitch is that image's ("mixed rigs and windows").  Applies to every submitting call: Detect[Color],
+ * DetectBatch[Color][Ex], SubmitBatch[Color] / WaitBatch[Ex], ThresholdOnly[Color].
+ * Callable whenever no submission is in flight; AMDAT_INVALID_ARGUMENT: null handle, a submission in flight.  A call that changes
+ * the mode retires the handle's captured launch graphs (the two modes differ in one launch), against the same budget of 24 retired
+ * graphs as amdAprilTagsSetQuadSigma: set it once after create. */
+int amdAprilTagsSetPerFrameSizes(amdAprilTagsHandle handle, int enable);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

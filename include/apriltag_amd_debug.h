@@ -69,7 +69,8 @@ typedef enum {
   AMDAT_DBG_COUNTS = 7,    /* u32[8]: npoints_raw, nclusters, npoints_kept, nquads, ndets, flags, w, h */
   AMDAT_DBG_FQPROF = 8     /* u64[64]: shader-cycle totals, 8 phases x up to 8 size classes of the quad-fit kernel (profiling on) */
 } amdAprilTagsDebugBuffer;
-/* Copies an intermediate buffer of frame `frame` of the last submission to host memory.
+/* Copies an intermediate buffer of frame `frame` of the last submission to host memory.  w, h: the FRAME's own working size (with
+ * amdAprilTagsSetPerFrameSizes on, the size that frame was submitted with; the planes are dense w x h whatever the handle's size).
  * Returns the number of bytes the buffer holds through *bytes (copy truncated to capacity). */
 int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsDebugBuffer what,
                           void* host_dst, size_t capacity, size_t* bytes);

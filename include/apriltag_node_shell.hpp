@@ -76,6 +76,10 @@ struct NodeOptions {
   // a superset: mono8 is what north_star feeds the detector, and the library's colour entry point reads rgba8 / bgra8 as well.
   // true: cuAprilTags mode refuses everything but rgb8 / bgr8 with the reference's own text.
   bool strict_cuapriltags_encodings = false;
+  // AprilTagMultiCameraNode only (AprilTagNode, the single-camera shape of the reference, ignores them): the largest frame of a mixed
+  // rig.  Both set: the handle is created at max_width x max_height with per-frame image sizes on (amdAprilTagsSetPerFrameSizes), and
+  // streams of every admissible size are batched together.  0 (the default): one size, the first frame's; other sizes are dropped.
+  uint32_t max_width = 0, max_height = 0;
 };
 
 class AprilTagNode {
@@ -104,7 +108,8 @@ class AprilTagNode {
   std::unique_ptr<Impl> impl_;
 };
 
-// Batching front end: S camera streams of one image size on ONE GPU, one detector submission per round.
+// Batching front end: S camera streams on ONE GPU, one detector submission per round -- streams of one image size, or (NodeOptions::
+// max_width / max_height) of any size up to that one.
 //
 // The reference node -- and AprilTagNode above -- hands the detector one frame per call (src/apriltag_node.cpp:491-493);
 // S cameras then mean S nodes and S one-frame submissions, each a chain of ~20 dependent kernels that leaves the GPU
@@ -126,7 +131,8 @@ class AprilTagMultiCameraNode {
   void set_transforms_callback(TransformsCallback cb);
 
   // Stages one synchronised pair of `stream` (a newer pair replaces an unsubmitted older one: "latest frame").  Returns
-  // false when the stamps differ (ExactTime would not fire) or the frame is dropped (size mismatch, as AprilTagNode).
+  // false when the stamps differ (ExactTime would not fire) or the frame is dropped (size mismatch, as AprilTagNode; with max_width /
+  // max_height set: a frame larger than that, or too small for one threshold tile).
   // With auto_flush (default) the round is submitted as soon as every stream has a staged frame.
   bool CameraImageCallback(uint32_t stream, const Image& image, const CameraInfo& camera_info);
   // Submits the staged frames of all streams that have one; publishes per stream; returns the number of streams served.

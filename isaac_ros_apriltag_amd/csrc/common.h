@@ -15,17 +15,27 @@
 #define AT_INVALID_SLOT 0xFFFFFFFFu
 #define AT_MAX_FAMILIES 4
 
-// Per-frame descriptor (device copy of amdAprilTagsImageInput_t + intrinsics), one per batch slot.
+// Per-frame descriptor (device copy of amdAprilTagsImageInput_t + intrinsics), one per batch slot.  k_prologue rewrites the block on
+// every submission, so everything here may change between two replays of a captured launch graph -- which is why the frame's
+// EXTENTS live here and not in DetParams (a by-value kernel argument, baked into the graph).  With per-frame sizes off
+// (amdAprilTagsSetPerFrameSizes) fill_frames writes the handle's size into every descriptor: one code path.
+// What follows the frame: every quantity the algorithm derives from the image size (bounds, full tiles, the label index y * W + x,
+// the cluster cap).  What stays the handle's (DetParams): slot strides, pitches of the working planes, capacities, grids.
 struct FrameDesc {
   const uint8_t* img;  // mono8, full resolution -- of a colour submission: the handle's gray plane, which the threshold pass (or the
                        // conversion launch ahead of it) fills from `src`; every later stage reads `img` and never sees the colour frame
   uint32_t pitch;
-  uint32_t seq;        // number of the launch this descriptor was written for (the handle's counter): comes back in FrameCounters::seq
+  uint32_t wh;         // W | H << 16 (both below 2^14): the working extents in one word, behind img and pitch for k_fit_small's raw loads
   double fx, fy, cx, cy;
   double skew;
   const uint8_t* src;  // colour submissions (amdAprilTagsEncoding != mono8): the caller's interleaved frame; null otherwise
   uint32_t src_pitch;
   uint32_t fmt;        // amdAprilTagsEncoding of `src`
+  uint32_t seq;        // number of the launch this descriptor was written for (the handle's counter): comes back in FrameCounters::seq
+  int32_t W0, H0;      // the frame's input size
+  int32_t W, H;        // its working (decimated) size: 1 + (W0 - 1) / decimate
+  int32_t tw, th;      // its full threshold tiles: W / tile, H / tile
+  int32_t max_cluster_points;   // its cluster-size cap: 3 (2 W + 2 H)
 };
 
 struct ClusterRec {
@@ -76,6 +86,8 @@ struct FamilyDev {
 // Geometry + algorithm parameters shared by all kernels of a handle.
 struct DetParams {
   int frame0;        // first batch slot of this launch (a submission may be split into concurrent halves)
+  // W0 .. th and max_cluster_points are the HANDLE's size: storage and schedule (slot strides, grids, capacities).  A kernel takes
+  // the extents the algorithm sees from its frame's FrameDesc, never from here.
   int W0, H0;        // input size
   int W, H;          // working (decimated) size
   int WS;            // pitch of the working u8 images (multiple of 16)

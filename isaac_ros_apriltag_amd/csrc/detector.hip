@@ -247,6 +247,8 @@ struct amdAprilTagsDetector_st {
   uint32_t qs_ksz = 1;
   int qs_kh = 0;
   QsTaps qs = {};
+  // amdAprilTagsSetPerFrameSizes: every frame of a submission brings its own size, up to the handle's (check_images, fill_frames)
+  bool per_frame_sizes = false;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -281,9 +283,11 @@ __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ sr
 
 // The same conversion for the frames of a colour submission that does not take the fused loader of k_threshold (decimate > 1,
 // tile_size 8): source and destination of frame blockIdx.z come from its descriptor (src -> img), one launch per submission.
+// (the grid is the handle's size; w x h is the frame's own)
 template <int NCH, int RIDX, int BIDX>
-__global__ __launch_bounds__(256) void k_to_mono8_frames(const FrameDesc* __restrict__ frames, uint32_t w, uint32_t h) {
+__global__ __launch_bounds__(256) void k_to_mono8_frames(const FrameDesc* __restrict__ frames) {
   const FrameDesc fd = frames[blockIdx.z];
+  const uint32_t w = (uint32_t)fd.W0, h = (uint32_t)fd.H0;
   const uint32_t x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
   const uint32_t y = blockIdx.y;
   if (x4 >= w || y >= h) return;
@@ -871,6 +875,17 @@ int amdAprilTagsSetQuadSigma(amdAprilTagsHandle handle, float quad_sigma) {
   return AMDAT_SUCCESS;
 }
 
+int amdAprilTagsSetPerFrameSizes(amdAprilTagsHandle handle, int enable) {
+  if (!handle || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  const bool on = enable != 0;
+  if (on == handle->per_frame_sizes) return AMDAT_SUCCESS;
+  DeviceGuard guard(handle->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  drop_graphs(handle);   // captured with the other mode's launch set (the leftover kernel of the one-pass threshold: launch_threshold)
+  handle->per_frame_sizes = on;
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
   if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
   if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
@@ -910,7 +925,13 @@ static int check_images(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
   if (n > D->cfg.max_batch) return AMDAT_BATCH_TOO_LARGE;
   for (uint32_t i = 0; i < n; i++) {
     if (!images[i].dev_ptr) return AMDAT_INVALID_ARGUMENT;
-    if (images[i].width != D->cfg.width || images[i].height != D->cfg.height) return AMDAT_SIZE_MISMATCH;
+    if (!D->per_frame_sizes) {
+      if (images[i].width != D->cfg.width || images[i].height != D->cfg.height) return AMDAT_SIZE_MISMATCH;
+    } else {   // any size up to the handle's whose working image has a full threshold tile in both directions
+      if (images[i].width < 1 || images[i].width > D->cfg.width || images[i].height < 1 || images[i].height > D->cfg.height) return AMDAT_SIZE_MISMATCH;
+      const uint32_t w = 1 + (images[i].width - 1) / D->cfg.decimate, h = 1 + (images[i].height - 1) / D->cfg.decimate;
+      if (w < D->cfg.tile_size || h < D->cfg.tile_size) return AMDAT_SIZE_MISMATCH;
+    }
     if (images[i].pitch < (size_t)images[i].width * enc_channels(fmt)) return AMDAT_INVALID_ARGUMENT;
     if ((uint64_t)images[i].pitch * images[i].height > 0x7FFFFFFFull) return AMDAT_INVALID_ARGUMENT;   // 32-bit pixel offsets on the device
     if (images[i].pitch >= (1u << 24)) return AMDAT_INVALID_ARGUMENT;   // (row offsets are formed with 24-bit multiplies: a 16 MB row is no image)
@@ -968,6 +989,14 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
     }
     D->h_frames[i].fmt = fmt;
     D->h_frames[i].seq = D->seq;
+    {   // the frame's extents and what the algorithm derives from them (check_images: the handle's own size unless per_frame_sizes)
+      FrameDesc& fd = D->h_frames[i];
+      fd.W0 = (int32_t)images[i].width; fd.H0 = (int32_t)images[i].height;
+      fd.W = 1 + (fd.W0 - 1) / D->P.decimate; fd.H = 1 + (fd.H0 - 1) / D->P.decimate;
+      fd.wh = (uint32_t)fd.W | ((uint32_t)fd.H << 16);
+      fd.tw = fd.W / D->P.tile; fd.th = fd.H / D->P.tile;
+      fd.max_cluster_points = 3 * (2 * fd.W + 2 * fd.H);
+    }
     D->h_frames[i].fx = (double)k.fx; D->h_frames[i].fy = (double)k.fy;
     D->h_frames[i].cx = (double)k.cx; D->h_frames[i].cy = (double)k.cy;
     D->h_frames[i].skew = (double)(i < D->frame_skew.size() ? D->frame_skew[i] : D->cfg.skew);
@@ -982,7 +1011,7 @@ static void launch_quad_sigma(amdAprilTagsDetector_st* D, const DetParams& P, ui
   const int gx = (P.W + QS_TW - 1) / QS_TW, gy = (P.H + QS_TH - 1) / QS_TH;
   const unsigned ntiles = (unsigned)gx * gy * n;
   const dim3 grid(8u * ((ntiles + 7u) / 8u));
-  switch (D->qs_kh) {
+  switch (D->qs_kh) {   // (the kernel takes every extent from the frame's descriptor; P carries strides)
     case 1: hipLaunchKernelGGL(k_quad_sigma<1>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
     case 2: hipLaunchKernelGGL(k_quad_sigma<2>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
     case 4: hipLaunchKernelGGL(k_quad_sigma<4>, grid, dim3(256), 0, s, D->d_frames, D->d_gray, gx, gy, (int)n, T, P); break;
@@ -999,23 +1028,19 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
   if (fmt != AMDAT_ENC_MONO8 && (filt ? P.decimate > 1 : !colour_fused(D, fmt))) {
     const dim3 g((P.W0 + 1023) / 1024, (unsigned)P.H0, n);
     switch (fmt) {
-      case AMDAT_ENC_RGB8: hipLaunchKernelGGL((k_to_mono8_frames<3, 0, 2>), g, dim3(256), 0, s, D->d_frames, (uint32_t)P.W0, (uint32_t)P.H0); break;
-      case AMDAT_ENC_BGR8: hipLaunchKernelGGL((k_to_mono8_frames<3, 2, 0>), g, dim3(256), 0, s, D->d_frames, (uint32_t)P.W0, (uint32_t)P.H0); break;
-      case AMDAT_ENC_RGBA8: hipLaunchKernelGGL((k_to_mono8_frames<4, 0, 2>), g, dim3(256), 0, s, D->d_frames, (uint32_t)P.W0, (uint32_t)P.H0); break;
-      default: hipLaunchKernelGGL((k_to_mono8_frames<4, 2, 0>), g, dim3(256), 0, s, D->d_frames, (uint32_t)P.W0, (uint32_t)P.H0); break;
+      case AMDAT_ENC_RGB8: hipLaunchKernelGGL((k_to_mono8_frames<3, 0, 2>), g, dim3(256), 0, s, D->d_frames); break;
+      case AMDAT_ENC_BGR8: hipLaunchKernelGGL((k_to_mono8_frames<3, 2, 0>), g, dim3(256), 0, s, D->d_frames); break;
+      case AMDAT_ENC_RGBA8: hipLaunchKernelGGL((k_to_mono8_frames<4, 0, 2>), g, dim3(256), 0, s, D->d_frames); break;
+      default: hipLaunchKernelGGL((k_to_mono8_frames<4, 2, 0>), g, dim3(256), 0, s, D->d_frames); break;
     }
     fmt = AMDAT_ENC_MONO8;
   }
-  DetParams Pp = P;   // (PLANE: the source is W x H)
-  if (filt) {
-    launch_quad_sigma(D, P, n, s, fmt);
-    Pp.W0 = P.W; Pp.H0 = P.H;
-  }
+  if (filt) launch_quad_sigma(D, P, n, s, fmt);
   if (P.tile != 4) {   // the two-pass statement (kernels_threshold.h); 4 keeps the one-pass kernel below
     const dim3 g1((unsigned)((P.tw * P.th + 255) / 256), 1, n), g2((unsigned)((P.W + 255) / 256), (unsigned)P.H, n);
 #define TH_ANY(DEC, PLANE)                                                                                                       \
-    hipLaunchKernelGGL((k_tile_minmax<DEC, PLANE>), g1, dim3(256), 0, s, D->d_frames, D->d_tmin, D->d_tmax, P.tile, Pp, D->d_gray);  \
-    hipLaunchKernelGGL((k_threshold_any_tile<DEC, PLANE>), g2, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, D->d_tmin, D->d_tmax, P.tile, Pp);
+    hipLaunchKernelGGL((k_tile_minmax<DEC, PLANE>), g1, dim3(256), 0, s, D->d_frames, D->d_tmin, D->d_tmax, P.tile, P, D->d_gray);  \
+    hipLaunchKernelGGL((k_threshold_any_tile<DEC, PLANE>), g2, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, D->d_tmin, D->d_tmax, P.tile, P);
     if (filt) { TH_ANY(1, true) }
     else switch (P.decimate) {
       case 1: TH_ANY(1, false) break;
@@ -1029,12 +1054,14 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
   const int gx = ((P.W + 3) / 4 + TH_BTX - 1) / TH_BTX, gy = ((P.H + 3) / 4 + TH_BTY - 1) / TH_BTY;
   const unsigned ntiles = (unsigned)gx * gy * n;
   dim3 grid(8u * ((ntiles + 7u) / 8u));
-  const bool leftover = (P.W % 4) || (P.H % 4);
-  const int nleft = (P.W - P.tw * 4) * (P.th * 4) + (P.H - P.th * 4) * P.W;
+  // the pixels right of / below the last full tile: the handle's own remainder, or -- per-frame sizes -- what any admissible frame
+  // can have, up to three columns and three rows (threads beyond a frame's own count return)
+  const bool leftover = D->per_frame_sizes || (P.W % 4) || (P.H % 4);
+  const int nleft = D->per_frame_sizes ? 3 * (P.W + P.H) : (P.W - P.tw * 4) * (P.th * 4) + (P.H - P.th * 4) * P.W;
   dim3 lgrid((unsigned)((nleft + 255) / 256), 1, n);
 #define TH_LAUNCH(DEC, FMT, PLANE)                                                                                                  \
-  hipLaunchKernelGGL((k_threshold<DEC, FMT, PLANE>), grid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, gx, gy, (int)n, Pp);    \
-  if (leftover) hipLaunchKernelGGL((k_threshold_leftover<DEC, FMT, PLANE>), lgrid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, Pp);
+  hipLaunchKernelGGL((k_threshold<DEC, FMT, PLANE>), grid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, gx, gy, (int)n, P);    \
+  if (leftover) hipLaunchKernelGGL((k_threshold_leftover<DEC, FMT, PLANE>), lgrid, dim3(256), 0, s, D->d_frames, D->d_gray, D->d_thr, P);
   if (filt) {
     TH_LAUNCH(1, 0, true)
     return;
@@ -1082,9 +1109,9 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   {
     const dim3 grid((P.W + CC_T - 1) / CC_T, (P.H + CC_T - 1) / CC_T, n);
     if (plan.cc_waves == 16)
-      hipLaunchKernelGGL((k_cc_local<16>), grid, dim3(1024), 0, s, D->d_thr, D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, P);
+      hipLaunchKernelGGL((k_cc_local<16>), grid, dim3(1024), 0, s, D->d_thr, D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, D->d_frames, P);
     else
-      hipLaunchKernelGGL((k_cc_local<4>), grid, dim3(256), 0, s, D->d_thr, D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, P);
+      hipLaunchKernelGGL((k_cc_local<4>), grid, dim3(256), 0, s, D->d_thr, D->d_label, D->d_csize, D->d_roots, D->d_perim, D->d_counters, D->d_frames, P);
   }
   mark();
   {
@@ -1092,7 +1119,7 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
     const long total = (long)nrows * P.W + (long)ncols * P.H;
     if (total > 0) {
 #define BORDER_ARGS dim3((unsigned)((total + 255) / 256) * n), dim3(256), 0, s, D->d_perim, D->d_label, D->d_roots, D->d_counters,   \
-                    (uint32_t)((total + 255) / 256), n, P
+                    (uint32_t)((total + 255) / 256), n, D->d_frames, P
       if (plan.border_per_wave) hipLaunchKernelGGL((k_cc_border<true>), BORDER_ARGS);
       else hipLaunchKernelGGL((k_cc_border<false>), BORDER_ARGS);
 #undef BORDER_ARGS
@@ -1104,11 +1131,11 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   mark();
   const uint32_t gxt = (uint32_t)((P.W + PT_TW - 1) / PT_TW), gyt = (uint32_t)((P.H + PT_TH - 1) / PT_TH);
   hipLaunchKernelGGL(k_points, dim3(gxt * gyt * n), dim3(256), 0, s, D->d_thr, D->d_label, D->d_hkeys, D->d_hcnt,
-                     D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_counters, (D->fq_counters ? D->d_ptprof : nullptr), gxt, gyt, n, P);
+                     D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_counters, (D->fq_counters ? D->d_ptprof : nullptr), gxt, gyt, n, D->d_frames, P);
   mark();
   const FqWorkLayout& L = D->work_layout.all;
   hipLaunchKernelGGL(k_cluster_select, dim3(plan.select_grid, 1, n), dim3(256), 0, s, D->d_hkeys, D->d_hcnt, D->d_hoff, D->d_clusters,
-                     D->d_counters, D->d_work, D->d_workctl, plan.latency ? D->work_layout.latency : L, plan.select_chunks, P);
+                     D->d_counters, D->d_work, D->d_workctl, plan.latency ? D->work_layout.latency : L, plan.select_chunks, D->d_frames, P);
   mark();
   hipLaunchKernelGGL(k_scatter, dim3((gxt * gyt + 3) / 4, 1, n), dim3(256), 0, s, D->d_stage, D->d_bhdr, D->d_btab, D->d_long, D->d_hoff, D->d_pts,
                      D->d_counters, gxt, gyt, P);
@@ -1734,7 +1761,9 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
   if (!guard.ok) return AMDAT_HIP_ERROR;
   HIP_TRY(hipDeviceSynchronize());
   const FrameCounters& fc = handle->h_counters[frame];
-  const size_t npx = (size_t)P.W * P.H;
+  // the frame's own working size (the descriptor block still holds the last submission): dense fW x fH planes; slots are the handle's
+  const int fW = handle->h_frames[frame].W, fH = handle->h_frames[frame].H;
+  const size_t npx = (size_t)fW * fH, slot_px = (size_t)P.W * P.H;
   const void* src = nullptr;
   size_t sz = 0;
   std::vector<uint8_t> tmp;
@@ -1748,7 +1777,7 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       else if (P.decimate > 1) base = handle->d_gray + (size_t)frame * P.H * P.WS;
       else { base = handle->h_frames[frame].img; pitch = handle->h_frames[frame].pitch; }
       tmp.resize(npx);
-      HIP_TRY(hipMemcpy2D(tmp.data(), P.W, base, pitch, P.W, P.H, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy2D(tmp.data(), fW, base, pitch, fW, fH, hipMemcpyDeviceToHost));
       *bytes = npx;
       if (host_dst) memcpy(host_dst, tmp.data(), npx < capacity ? npx : capacity);
       return AMDAT_SUCCESS;
@@ -1756,12 +1785,12 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
     case AMDAT_DBG_LABEL: {
       DetParams Pf = P;
       Pf.frame0 = (int)frame;
-      hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)((npx + 255) / 256), 1, 1), dim3(256), 0, 0, handle->d_label, Pf);
+      hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)((npx + 255) / 256), 1, 1), dim3(256), 0, 0, handle->d_label, npx, Pf);
       HIP_TRY(hipDeviceSynchronize());
-      src = handle->d_label + (size_t)frame * npx; sz = npx * 4;
+      src = handle->d_label + (size_t)frame * slot_px; sz = npx * 4;
       break;
     }
-    case AMDAT_DBG_CSIZE: src = handle->d_csize + (size_t)frame * npx; sz = npx * 4; break;
+    case AMDAT_DBG_CSIZE: src = handle->d_csize + (size_t)frame * slot_px; sz = npx * 4; break;
     case AMDAT_DBG_CLUSTERS:
       src = handle->d_clusters + (size_t)frame * P.ccap;
       sz = (size_t)(fc.nclusters < P.ccap ? fc.nclusters : P.ccap) * sizeof(ClusterRec);
@@ -1778,7 +1807,7 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       src = handle->d_fqprof; sz = (64 + 8) * 8;
       break;
     case AMDAT_DBG_COUNTS: {
-      uint32_t c[8] = {fc.npoints_raw, fc.nclusters, fc.npoints_kept, fc.nquads, fc.ndets, fc.flags, (uint32_t)P.W, (uint32_t)P.H};
+      uint32_t c[8] = {fc.npoints_raw, fc.nclusters, fc.npoints_kept, fc.nquads, fc.ndets, fc.flags, (uint32_t)fW, (uint32_t)fH};
       *bytes = sizeof(c);
       if (host_dst) memcpy(host_dst, c, sizeof(c) < capacity ? sizeof(c) : capacity);
       return AMDAT_SUCCESS;

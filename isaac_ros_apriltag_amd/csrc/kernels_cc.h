@@ -133,7 +133,8 @@ __host__ __device__ inline CcPerim cc_perim_layout(int W, int H) {
 template <int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(CC_LOCAL_MIN_WAVES, 8))) void k_cc_local(const uint8_t* __restrict__ thr_all, uint32_t* __restrict__ label_all,
                                                   uint32_t* __restrict__ csize_all, uint32_t* __restrict__ roots_all,
-                                                  uint32_t* __restrict__ perim_all, FrameCounters* __restrict__ counters, DetParams P) {
+                                                  uint32_t* __restrict__ perim_all, FrameCounters* __restrict__ counters,
+                                                  const FrameDesc* __restrict__ frames, DetParams P) {
   // (the threshold tile is only read into registers right after the load; the link-request lists of the union pass take
   // over its space -- a barrier lies between)
   constexpr int ROWS = CC_T / NW;                                   // rows of a wave's strip
@@ -146,8 +147,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(CC_LOCA
   // (with 4 waves the block is 20 KB of LDS to the byte -- eight blocks per CU, and eight waves per SIMD)
   const int frame = (int)blockIdx.z + P.frame0;
   const int X0 = blockIdx.x * CC_T, Y0 = blockIdx.y * CC_T;
-  const int W = P.W, H = P.H;
-  const uint8_t* thr = thr_all + (size_t)frame * H * P.WS;
+  // W, H: the FRAME's working extents (bounds, link-source columns, the label index y * W + x); slot strides and the perimeter
+  // layout are the handle's (P).  The grid is the handle's too: a tile outside a smaller frame has nothing to do.
+  const int W = frames[frame].W, H = frames[frame].H;
+  if (X0 >= W || Y0 >= H) return;
+  const uint8_t* thr = thr_all + (size_t)frame * P.H * P.WS;
   const int tid = threadIdx.x;
 
   if (tid < 256) {  // load the tile: 16 bytes per thread, out-of-image pixels become 127
@@ -335,8 +339,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(CC_LOCA
 
   CC_STOP_AT(3)
   // ---- 4. write global labels (index of the local root), local sizes at the roots, root list -------
-  uint32_t* label = label_all + (size_t)frame * W * H;
-  uint32_t* csize = csize_all + (size_t)frame * W * H;
+  uint32_t* label = label_all + (size_t)frame * P.W * P.H;
+  uint32_t* csize = csize_all + (size_t)frame * P.W * P.H;
   // No root list any more (round 6): a root keeps the size bit of its LOCAL pixel count whether or not its component touches the
   // tile's perimeter -- the count only grows when the border pass joins it to another tile's component, so the bit is final when
   // set -- and the passes behind the border pass (k_cc_sizes, k_cc_resolve) run over the roots that LOST a union there, which
@@ -353,7 +357,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(CC_LOCA
     const uint32_t* const sl4 = lds_at(sl, me4);
     // the tile's perimeter for k_cc_border (CcPerim): the first / last row go out as one 256-byte store each, the first / last
     // column as one two-lane store per row (lane 0 to `left`, lane 63 to `right`)
-    const CcPerim PL = cc_perim_layout(W, H);
+    const CcPerim PL = cc_perim_layout(P.W, P.H);
     uint32_t* const perim = perim_all + (size_t)frame * PL.words;
     uint32_t* const pcol = perim + (lane == 0 ? PL.left + blockIdx.x * (uint32_t)PL.HP : PL.right + blockIdx.x * (uint32_t)PL.HP) + (uint32_t)gyw;
     const bool col_lane = lane == 0 || lane == 63;
@@ -428,14 +432,14 @@ __device__ __forceinline__ void cc_column_requests(int W, int gx, bool upward, u
 template <bool PER_WAVE>
 __global__ __launch_bounds__(256) void k_cc_border(const uint32_t* __restrict__ perim_all, uint32_t* __restrict__ label_all,
                                                    uint32_t* __restrict__ roots_all, FrameCounters* __restrict__ counters,
-                                                   uint32_t bpf, uint32_t nframes, DetParams P) {
+                                                   uint32_t bpf, uint32_t nframes, const FrameDesc* __restrict__ frames, DetParams P) {
   uint32_t fr_, blk_;
   at_frame_block(blockIdx.x, bpf, nframes, CC_ILEAVE, &fr_, &blk_);
   const int frame = (int)fr_ + P.frame0;
-  const int W = P.W, H = P.H;
-  const CcPerim PL = cc_perim_layout(W, H);
+  const int W = frames[frame].W, H = frames[frame].H;   // the frame's extents: its own borders, fewer than the grid covers in a smaller frame
+  const CcPerim PL = cc_perim_layout(P.W, P.H);
   const uint32_t* perim = perim_all + (size_t)frame * PL.words;
-  uint32_t* label = label_all + (size_t)frame * W * H;
+  uint32_t* label = label_all + (size_t)frame * P.W * P.H;
   const int nrows = (H - 1) / CC_T;  // tile-top rows at y = 64, 128, ...
   const int ncols = (W - 1) / CC_T;  // tile-left columns at x = 64, 128, ...
   int i = (int)blk_ * 256 + threadIdx.x;
@@ -588,12 +592,12 @@ __global__ __launch_bounds__(256) void k_cc_resolve(uint32_t* __restrict__ label
 }
 
 // Stage inspection only: representative per pixel (label[label[p]] after k_cc_sizes; idempotent).
-__global__ __launch_bounds__(256) void k_cc_flatten(uint32_t* __restrict__ label_all, DetParams P) {
+// (npx: the pixels of the frame in the slot, at most P.W * P.H -- entries behind them are an earlier submission's)
+__global__ __launch_bounds__(256) void k_cc_flatten(uint32_t* __restrict__ label_all, size_t npx, DetParams P) {
   const int frame = (int)blockIdx.z + P.frame0;
-  const size_t n = (size_t)P.W * P.H;
-  uint32_t* label = label_all + (size_t)frame * n;
+  uint32_t* label = label_all + (size_t)frame * P.W * P.H;
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+  if (i >= npx) return;
   const uint32_t l = label[i];
   if (l == AT_NO_LABEL) return;
   // (idempotent under concurrent execution: every entry on a chain keeps pointing at an ancestor, with or without the bit)

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
                                                 uint2* __restrict__ bhdr_all, uint2* __restrict__ btab_all, uint4* __restrict__ long_all,
                                                 FrameCounters* __restrict__ counters,
                                                 unsigned long long* __restrict__ prof, uint32_t gx_tiles, uint32_t gy_tiles, uint32_t nframes,
-                                                DetParams P) {
+                                                const FrameDesc* __restrict__ frames, DetParams P) {
   PT_HOOKS_DECL   // (tools_hooks.h: measurement hooks, nothing in the product build)
   // tile + halo, one word per pixel: representative of the pixel's component if it is large enough, with the pixel's class in
   // the two top bits -- white 10, black 01 -- and 0 = no component that counts (value 127, or too small).  Two pixels lie on
@@ -143,12 +143,15 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
   at_frame_block(blockIdx.x, gx_tiles * gy_tiles, nframes, PT_ILEAVE, &fr_, &blk_);
   const int frame = (int)fr_ + P.frame0;
   const int bx_ = (int)(blk_ % gx_tiles), by_ = (int)(blk_ / gx_tiles);
-  const int W = P.W, H = P.H;
-  const size_t npx = (size_t)W * H;
-  const uint8_t* thr = thr_all + (size_t)frame * H * P.WS;
-  const uint32_t* label = label_all + (size_t)frame * npx;
+  const int W = frames[frame].W, H = frames[frame].H;   // the frame's working extents; strides and the tile grid are the handle's
+  const uint8_t* thr = thr_all + (size_t)frame * P.H * P.WS;
+  const uint32_t* label = label_all + (size_t)frame * P.W * P.H;
   const int X0 = bx_ * PT_TW, Y0 = by_ * PT_TH;
   const int tid = threadIdx.x;
+  if (X0 >= W || Y0 >= H) {   // a tile outside a smaller frame: no points (k_scatter reads every tile's header)
+    if (tid == 0) bhdr_all[(size_t)frame * (gx_tiles * gy_tiles) + blk_] = make_uint2(0u, 0u);
+    return;
+  }
 
   // An INTERIOR tile -- all of its 17 x 66 entries inside the image, every pixel of it a valid emission source whose left
   // neighbour is one too (nine tiles in ten at 1080p) -- takes the straight-line forms of the tile load and of the emission tests
@@ -440,7 +443,8 @@ __global__ __launch_bounds__(256) void k_cluster_select(unsigned long long* __re
                                                         uint32_t* __restrict__ hcnt_all, uint32_t* __restrict__ hoff_all,
                                                         ClusterRec* __restrict__ clusters_all,
                                                         FrameCounters* __restrict__ counters, uint32_t* __restrict__ work,
-                                                        uint32_t* __restrict__ work_n, FqWorkLayout L, int nchunks, DetParams P) {
+                                                        uint32_t* __restrict__ work_n, FqWorkLayout L, int nchunks,
+                                                        const FrameDesc* __restrict__ frames, DetParams P) {
   // 1024 table slots per chunk, four consecutive ones per thread (16-byte loads and stores; hcap is a power of two >= 256)
   __shared__ uint32_t wsum[4], wcnt[4];
   __shared__ uint32_t s_pbase, s_cbase;
@@ -450,6 +454,7 @@ __global__ __launch_bounds__(256) void k_cluster_select(unsigned long long* __re
   // a frame whose point staging overflowed has pair counts that exceed what was staged: it yields no
   // clusters at all (the overflow bit is reported), never an out-of-range range
   const bool frame_ok = (counters[frame].flags & 0x1u) == 0;
+  const int max_cluster_points = SEL_CLUSTER_CAP(frames[frame], P);   // (tools_hooks.h: the frame's own cap, 3 (2 W + 2 H) of ITS extents)
   const int lane = lane_id(), wv = threadIdx.x >> 6;
   // work item of a kept cluster: size class, rank among the block's items of the class, cluster index
   int wcls[SEL_CHUNKS][4];
@@ -476,7 +481,7 @@ __global__ __launch_bounds__(256) void k_cluster_select(unsigned long long* __re
     for (int j = 0; j < 4; j++) {
       key[j] = c[j] ? hkeys_all[hi + j] : AT_EMPTY_KEY;
       if (c[j]) hkeys_all[hi + j] = AT_EMPTY_KEY;   // this kernel is the table's last reader: it leaves it empty for the next submission
-      keep[j] = frame_ok && key[j] != AT_EMPTY_KEY && (int)c[j] >= P.min_cluster_points && (int)c[j] <= P.max_cluster_points;
+      keep[j] = frame_ok && key[j] != AT_EMPTY_KEY && (int)c[j] >= P.min_cluster_points && (int)c[j] <= max_cluster_points;
       if (keep[j]) { tsum += c[j]; tcnt++; }
     }
     const uint32_t inc = wave_incl_scan(tsum), cinc = wave_incl_scan(tcnt);

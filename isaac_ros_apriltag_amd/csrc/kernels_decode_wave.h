@@ -42,7 +42,7 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
   const FrameDesc fd = frames[frame];
   // the caller's image pointer is global by contract; out of the descriptor the compiler would have to assume generic
   const __attribute__((address_space(1))) uint8_t* im = (const __attribute__((address_space(1))) uint8_t*)fd.img;
-  const int w = P.W0, h = P.H0, pitch = (int)fd.pitch;
+  const int w = fd.W0, h = fd.H0, pitch = (int)fd.pitch;   // the frame's own input size
 
   for (uint32_t qi = blockIdx.x; qi < nq; qi += gridDim.x) {
     __syncthreads();

@@ -62,6 +62,8 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
   const int frame = lframe + P.frame0;
   const int x0 = (trem % gx) * QS_TW, y0 = (trem / gx) * QS_TH;
   const FrameDesc fd = frames[frame];
+  const int fW = fd.W, fH = fd.H;   // the frame's own working extents (the identity and edge-copy rules follow them); the grid is the handle's
+  if (x0 >= fW || y0 >= fH) return;
   const th_gimg_t simg = (th_gimg_t)(T.kind < 5 ? fd.src : fd.img);
   const uint32_t spitch = T.kind < 5 ? fd.src_pitch : fd.pitch;
   const bool aligned = ((((uintptr_t)simg) | (uintptr_t)spitch) & 15) == 0;
@@ -72,14 +74,14 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
     const int r = u / 10, c = u - r * 10;
     const int y = y0 - KH + r, x = x0 - 16 + 16 * c;
     uint32_t v[4] = {0u, 0u, 0u, 0u};
-    if (y >= 0 && y < P.H && x >= 0 && x < P.W) qs_load16(T.kind, simg, spitch, P.W0, P.H0, aligned, x, y, v);
+    if (y >= 0 && y < fH && x >= 0 && x < fW) qs_load16(T.kind, simg, spitch, fd.W0, fd.H0, aligned, x, y, v);
     th_u32x4 w; w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3];
     *reinterpret_cast<th_u32x4*>(sg + r * QS_IW + 16 * c) = w;
   }
   __syncthreads();
 
   // ---- row pass: IH rows x 8 units of 16 pixels ------------------------------------------------------------------------------
-  const bool rows_filter = P.W > T.ksz, cols_filter = P.H > T.ksz;
+  const bool rows_filter = fW > T.ksz, cols_filter = fH > T.ksz;
   for (int u = tid; u < IH * 8; u += 256) {
     const int r = u >> 3, c = u & 7;
     const int x = x0 + 16 * c;
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
     uint32_t d[10];
 #pragma unroll
     for (int q = 0; q < 5; q++) { const uint2 t = src[q]; d[2 * q] = t.x; d[2 * q + 1] = t.y; }
-    const bool interior = rows_filter && x >= T.h && x + 15 <= P.W - QS_FAR_EDGE_H(KH, T.h) - 2;   // (tools_hooks.h: T.h)
+    const bool interior = rows_filter && x >= T.h && x + 15 <= fW - QS_FAR_EDGE_H(KH, T.h) - 2;   // (tools_hooks.h: T.h)
     uint32_t o[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int p = 0; p < 16; p++) {
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
       uint32_t t = acc >> 8;
       if (!interior) {
         const int xp = x + p;
-        if (!(rows_filter && xp >= T.h && xp <= P.W - QS_FAR_EDGE_H(KH, T.h) - 2)) t = (d[(8 + p) / 4] >> (8 * ((8 + p) & 3))) & 0xFFu;
+        if (!(rows_filter && xp >= T.h && xp <= fW - QS_FAR_EDGE_H(KH, T.h) - 2)) t = (d[(8 + p) / 4] >> (8 * ((8 + p) & 3))) & 0xFFu;
       }
       o[p >> 2] |= t << (8 * (p & 3));
     }
@@ -113,9 +115,9 @@ __global__ __launch_bounds__(256) void k_quad_sigma(const FrameDesc* __restrict_
   // ---- column pass: 32 rows x 8 units, one per thread ---------------------------------------------------------------------------
   const int r = tid >> 3, c = tid & 7;
   const int y = y0 + r, x = x0 + 16 * c;
-  if (y >= P.H || x >= P.WS) return;
+  if (y >= fH || x >= P.WS) return;
   uint32_t o[4];
-  if (cols_filter && y >= T.h && y <= P.H - QS_FAR_EDGE_H(KH, T.h) - 2) {
+  if (cols_filter && y >= T.h && y <= fH - QS_FAR_EDGE_H(KH, T.h) - 2) {
     qs_u16x2 lo[4], hi[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) { lo[q] = (qs_u16x2)(0); hi[q] = (qs_u16x2)(0); }

@@ -858,6 +858,7 @@ __device__ __forceinline__ void fq_corner_search(const double* s_tab, const uint
 struct FqItem {
   int frame;
   int gpitch;
+  int W, H;             // the frame's working extents (FrameDesc): the image bounds of the fit
   const uint8_t* gray;
   fit_gray_ptr ggray;   // gray in the global address space
   ClusterRec cl;
@@ -871,6 +872,7 @@ __device__ __forceinline__ FqItem fq_decode_item(uint32_t wi, const FrameDesc* _
   const FrameDesc fd = frames[it.frame];
   it.gray = (P.decimate > 1) ? gray_all + (size_t)it.frame * P.H * P.WS : fd.img;
   it.gpitch = (P.decimate > 1) ? P.WS : (int)fd.pitch;
+  it.W = (int)(fd.wh & 0xFFFFu); it.H = (int)(fd.wh >> 16);
   it.ggray = (fit_gray_ptr)it.gray;
   it.cl = clusters_all[(size_t)it.frame * P.ccap + (wi & ((1u << P.wshift) - 1u))];
   it.pts = pts_all + (size_t)it.frame * P.pcap + it.cl.start;
@@ -928,7 +930,6 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
   __shared__ int s_feasible;
 
   const int tid = threadIdx.x;
-  const int W = P.W, H = P.H;
   const uint32_t nwork = min(*work_n, work_cap);
   // scratch slot of this workgroup: cumulative moments of the cluster in flight (and, for clusters that do
   // not fit the LDS key array, their sort keys and two error arrays)
@@ -964,6 +965,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
     if (item >= nwork) break;
     const FqItem fi = fq_decode_item((uint32_t)__builtin_amdgcn_readfirstlane((int)work[item]), frames, gray_all, pts_all, clusters_all, P);
     const int frame = fi.frame, gpitch = fi.gpitch, sz = (int)fi.cl.count;
+    const int W = fi.W, H = fi.H;
     const uint8_t* const gray = fi.gray;
     const fit_gray_ptr ggray = fi.ggray;
     const uint32_t* const pts = fi.pts;
@@ -1571,7 +1573,6 @@ __global__ __launch_bounds__(FQ_PF_NT) void k_fit_prefilter(const FrameDesc* __r
   __shared__ uint32_t s_okf[FQ_XG], s_okw[FQ_XG];
   __shared__ int s_feasible;
   const int tid = threadIdx.x;
-  const int W = P.W, H = P.H;
   PF_HOOKS_DECL   // (tools_hooks.h)
   TL_MARK_MIN(0)
   // items of the classes first_class .. FQ_NCLS - 1, largest class first
@@ -1604,6 +1605,7 @@ __global__ __launch_bounds__(FQ_PF_NT) void k_fit_prefilter(const FrameDesc* __r
     const uint32_t wi = (uint32_t)__builtin_amdgcn_readfirstlane((int)work[widx]);
     const FqItem item = fq_decode_item(wi, frames, gray_all, pts_all, clusters_all, P);
     const int gpitch = item.gpitch, sz = (int)item.cl.count;
+    const int W = item.W, H = item.H;
     const fit_gray_ptr ggray = item.ggray;
     const uint32_t* const pts = item.pts;
 

@@ -55,7 +55,6 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
   __shared__ int s_maxidx[16];
 
   const int lane = (int)threadIdx.x;
-  const int W = P.W, H = P.H;
   const uint32_t nwork = min(*work_n, work_cap);
   for (int t = lane; t < 210; t += 64) s_cpairs[t] = g_combo_pairs.v[t];
 
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
     uint32_t item;      // uniform; >= nwork: none
     uint32_t wi_v;      // stage 1: work item (the same word in every lane)
     uint32_t rec_v[4];  // stage 2: cluster record {key lo, key hi, start, count}
-    uint32_t img_v[3];  //          frame: image pointer lo / hi, pitch
+    uint32_t img_v[4];  //          frame: image pointer lo / hi, pitch, working extents (W | H << 16)
     uint32_t pp[K];     // stage 3: the lane's points
   };
   auto stage1 = [&](Pending& n) {
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
     const gptr32 fdp = (gptr32)(frames + frame);
 #pragma unroll
     for (int j = 0; j < 4; j++) n.rec_v[j] = rec[j];
-    n.img_v[0] = fdp[0]; n.img_v[1] = fdp[1]; n.img_v[2] = fdp[2];   // FrameDesc: img (8 bytes), pitch
+    n.img_v[0] = fdp[0]; n.img_v[1] = fdp[1]; n.img_v[2] = fdp[2]; n.img_v[3] = fdp[3];   // FrameDesc: img (8 bytes), pitch, wh
   };
   auto stage3 = [&](Pending& n) {
     if (n.item >= nwork) return;
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
 #pragma unroll
     for (int j = 0; j < K; j++) n.pp[j] = pts[min(lane + 64 * j, max(sz, 1) - 1)];
   };
-  static_assert(offsetof(FrameDesc, img) == 0 && offsetof(FrameDesc, pitch) == 8 && sizeof(ClusterRec) == 16, "stage 2 reads raw words");
+  static_assert(offsetof(FrameDesc, img) == 0 && offsetof(FrameDesc, pitch) == 8 && offsetof(FrameDesc, wh) == 12 && sizeof(ClusterRec) == 16, "stage 2 reads raw words");
   Pending cur, nxt;
   stage1(cur); stage2(cur); stage3(cur);
   while (cur.item < nwork) {
@@ -122,6 +121,8 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
                                                                               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.img_v[0]));
     const int gpitch = (P.decimate > 1) ? P.WS : __builtin_amdgcn_readfirstlane((int)cur.img_v[2]);
     const fit_gray_ptr ggray = (fit_gray_ptr)gray;
+    const int wh = __builtin_amdgcn_readfirstlane((int)cur.img_v[3]);
+    const int W = wh & 0xFFFF, H = (int)((uint32_t)wh >> 16);   // the frame's working extents: the image bounds of the fit
     const unsigned long long cl_key = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.rec_v[1]) << 32) |
                                       (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)cur.rec_v[0]);
     const int sz = __builtin_amdgcn_readfirstlane((int)cur.rec_v[3]);

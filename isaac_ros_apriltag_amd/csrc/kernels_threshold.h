@@ -148,7 +148,7 @@ __device__ __forceinline__ void th_minmax_word(uint32_t w, uint32_t& mn, uint32_
 // (the colour instances take 117 registers -- all loads of both units in flight -- and run at four waves per SIMD against the mono8
 // instance's seven; a budget of 96 or 80 registers makes the compiler spill 12 / 28 of them instead of issuing the loads later, and
 // a scheduling fence between the two units changes nothing: measured 63 - 66 % of 8 TB/s on 5 N bytes as it stands)
-// PLANE: the source is the frame's slot of gray_all (pitch P.WS, W x H; the host passes W0 = W, H0 = H), which the quad_sigma filter
+// PLANE: the source is the frame's slot of gray_all (pitch P.WS, the frame's W x H), which the quad_sigma filter
 // (kernels_filter.h) has written, and gray_all is not written.
 template <int DEC, int FMT = 0, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__ frames, uint8_t* __restrict__ gray_all,
@@ -167,6 +167,10 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
   const int frame = lframe + P.frame0;
   const int bx = trem % gx, by = trem / gx;
   const FrameDesc fd = frames[frame];
+  // the frame's own extents (common.h: FrameDesc); the grid is the handle's, a block outside a smaller frame has nothing to do
+  const int fW = fd.W, fH = fd.H, ftw = fd.tw, fth = fd.th;
+  if (bx * (TH_BTX * 4) >= fW || by * (TH_BTY * 4) >= fH) return;
+  const int sW0 = PLANE ? fW : fd.W0, sH0 = PLANE ? fH : fd.H0;   // extents of the source
   // (a colour submission: the loader reads the caller's interleaved frame, fd.img is the handle's gray plane of pitch WS)
   const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_all + (size_t)frame * P.H * P.WS) : (th_gimg_t)(FMT ? fd.src : fd.img);
   const uint32_t spitch = PLANE ? (uint32_t)P.WS : (FMT ? fd.src_pitch : fd.pitch);
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
   for (int v = 0; v < 2; v++) {
     const int uy = (TY0 + 2 * ty4 + v) * 4;
 #pragma unroll
-    for (int r = 0; r < 4; r++) th_load16<DEC, FMT>(simg, spitch, P.W0, P.H0, aligned, ux, uy + r, u[v][r]);
+    for (int r = 0; r < 4; r++) th_load16<DEC, FMT>(simg, spitch, sW0, sH0, aligned, ux, uy + r, u[v][r]);
   }
 #pragma unroll
   for (int v = 0; v < 2; v++) {
@@ -193,14 +197,14 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
     if (DEC > 1 || FMT) {
 #pragma unroll
       for (int r = 0; r < 4; r++)
-        if (uy + r < P.H && ux < P.WS)
+        if (uy + r < fH && ux < P.WS)
           *reinterpret_cast<uint4*>(gray + (size_t)(uy + r) * P.WS + ux) = make_uint4(u[v][r][0], u[v][r][1], u[v][r][2], u[v][r][3]);
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int tX = TX0 + 4 * tx64 + j;
       uint32_t mn = 255, mx = 0;
-      if (tX < P.tw && tY < P.th) {
+      if (tX < ftw && tY < fth) {
 #pragma unroll
         for (int r = 0; r < 4; r++) th_minmax_word(u[v][r][j], mn, mx);
       }
@@ -214,16 +218,16 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
     const int tY = side ? TY0 + TH_BTY : TY0 - 1;
     const int lrow = side ? 9 : 0;
     uint32_t h[4][4];
-    const bool rowok = tY >= 0 && tY < P.th;
+    const bool rowok = tY >= 0 && tY < fth;
     if (rowok) {
 #pragma unroll
-      for (int r = 0; r < 4; r++) th_load16<DEC, FMT>(simg, spitch, P.W0, P.H0, aligned, (TX0 + 4 * c) * 4, tY * 4 + r, h[r]);
+      for (int r = 0; r < 4; r++) th_load16<DEC, FMT>(simg, spitch, sW0, sH0, aligned, (TX0 + 4 * c) * 4, tY * 4 + r, h[r]);
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int tX = TX0 + 4 * c + j;
       uint32_t mn = 255, mx = 0;
-      if (rowok && tX < P.tw) {
+      if (rowok && tX < ftw) {
 #pragma unroll
         for (int r = 0; r < 4; r++) th_minmax_word(h[r][j], mn, mx);
       }
@@ -236,10 +240,10 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
     const int tX = side ? TX0 + TH_BTX : TX0 - 1;
     const int tY = TY0 - 1 + lrow;
     uint32_t mn = 255, mx = 0;
-    if (tX >= 0 && tX < P.tw && tY >= 0 && tY < P.th) {
+    if (tX >= 0 && tX < ftw && tY >= 0 && tY < fth) {
       for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) {
-          uint32_t v = th_px<DEC, FMT>(simg, spitch, P.W0, P.H0, tX * 4 + c, tY * 4 + r);
+          uint32_t v = th_px<DEC, FMT>(simg, spitch, sW0, sH0, tX * 4 + c, tY * 4 + r);
           mn = min(mn, v);
           mx = max(mx, v);
         }
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
   for (int v = 0; v < 2; v++) {
     const int lty = 2 * ty4 + v;
     const int tY = TY0 + lty, uy = tY * 4;
-    if (tY >= P.th) continue;
+    if (tY >= fth) continue;
     uint32_t cmin[6], cmax[6];
 #pragma unroll
     for (int c = 0; c < 6; c++) { cmin[c] = 255; cmax[c] = 0; }
@@ -281,7 +285,7 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int tX = TX0 + 4 * tx64 + j;
-      valid[j] = tX < P.tw;
+      valid[j] = tX < ftw;
       const uint32_t mn = min(min(cmin[j], cmin[j + 1]), cmin[j + 2]);
       const uint32_t mx = max(max(cmax[j], cmax[j + 1]), cmax[j + 2]);
       if ((int)(mx - mn) < P.min_white_black_diff) {
@@ -328,29 +332,31 @@ __global__ __launch_bounds__(256) void k_threshold_leftover(const FrameDesc* __r
                                                             uint8_t* __restrict__ thr_all, DetParams P) {
   const int frame = (int)blockIdx.z + P.frame0;
   const FrameDesc fd = frames[frame];
+  const int fW = fd.W, fH = fd.H, ftw = fd.tw, fth = fd.th;   // the frame's own extents; the grid is the handle's
+  const int sW0 = PLANE ? fW : fd.W0, sH0 = PLANE ? fH : fd.H0;
   const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_all + (size_t)frame * P.H * P.WS) : (th_gimg_t)(FMT ? fd.src : fd.img);
   const uint32_t spitch = PLANE ? (uint32_t)P.WS : (FMT ? fd.src_pitch : fd.pitch);
-  const int nright = P.W - P.tw * 4;  // columns per row in the right strip
-  const int nbot = P.H - P.th * 4;    // rows in the bottom strip
-  const int right_cnt = nright * (P.th * 4);
-  const int total = right_cnt + nbot * P.W;
+  const int nright = fW - ftw * 4;  // columns per row in the right strip
+  const int nbot = fH - fth * 4;    // rows in the bottom strip
+  const int right_cnt = nright * (fth * 4);
+  const int total = right_cnt + nbot * fW;
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   int x, y;
-  if (i < right_cnt) { y = i / nright; x = P.tw * 4 + i % nright; }
-  else { int k = i - right_cnt; y = P.th * 4 + k / P.W; x = k % P.W; }
-  int tX = min(x / 4, P.tw - 1), tY = min(y / 4, P.th - 1);
+  if (i < right_cnt) { y = i / nright; x = ftw * 4 + i % nright; }
+  else { int k = i - right_cnt; y = fth * 4 + k / fW; x = k % fW; }
+  int tX = min(x / 4, ftw - 1), tY = min(y / 4, fth - 1);
   uint32_t mn = 255, mx = 0;
-  for (int ty = max(tY - 1, 0); ty <= min(tY + 1, P.th - 1); ty++)
-    for (int tx = max(tX - 1, 0); tx <= min(tX + 1, P.tw - 1); tx++)
+  for (int ty = max(tY - 1, 0); ty <= min(tY + 1, fth - 1); ty++)
+    for (int tx = max(tX - 1, 0); tx <= min(tX + 1, ftw - 1); tx++)
       for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) {
-          uint32_t v = th_px<DEC, FMT>(simg, spitch, P.W0, P.H0, tx * 4 + c, ty * 4 + r);
+          uint32_t v = th_px<DEC, FMT>(simg, spitch, sW0, sH0, tx * 4 + c, ty * 4 + r);
           mn = min(mn, v);
           mx = max(mx, v);
         }
   uint32_t thresh = mn + (mx - mn) / 2;
-  uint32_t v = th_px<DEC, FMT>(simg, spitch, P.W0, P.H0, x, y);
+  uint32_t v = th_px<DEC, FMT>(simg, spitch, sW0, sH0, x, y);
   thr_all[(size_t)frame * P.H * P.WS + (size_t)y * P.WS + x] = v > thresh ? 255 : 0;
   if (DEC > 1) gray_all[(size_t)frame * P.H * P.WS + (size_t)y * P.WS + x] = (uint8_t)v;
   // (FMT: the one-pass kernel's units cover these pixels too and have written their gray values)
@@ -367,15 +373,17 @@ __global__ __launch_bounds__(256) void k_tile_minmax(const FrameDesc* __restrict
                                                      uint8_t* __restrict__ tmax_all, int ts, DetParams P, const uint8_t* __restrict__ gray_plane) {
   const int frame = (int)blockIdx.z + P.frame0;
   const FrameDesc fd = frames[frame];
+  const int fW = fd.W, fH = fd.H, ftw = fd.tw, fth = fd.th;   // the frame's own extents; the grid is the handle's
+  const int sW0 = PLANE ? fW : fd.W0, sH0 = PLANE ? fH : fd.H0;
   const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_plane + (size_t)frame * P.H * P.WS) : (th_gimg_t)fd.img;
   const uint32_t spitch = PLANE ? (uint32_t)P.WS : fd.pitch;
   const int t = (int)(blockIdx.x * 256 + threadIdx.x);
-  if (t >= P.tw * P.th) return;
-  const int tx = t % P.tw, ty = t / P.tw;
+  if (t >= ftw * fth) return;
+  const int tx = t % ftw, ty = t / ftw;
   uint32_t mn = 255, mx = 0;
   for (int r = 0; r < ts; r++)
     for (int c = 0; c < ts; c++) {
-      const uint32_t v = th_px<DEC>(simg, spitch, P.W0, P.H0, tx * ts + c, ty * ts + r);
+      const uint32_t v = th_px<DEC>(simg, spitch, sW0, sH0, tx * ts + c, ty * ts + r);
       mn = min(mn, v);
       mx = max(mx, v);
     }
@@ -390,21 +398,23 @@ __global__ __launch_bounds__(256) void k_threshold_any_tile(const FrameDesc* __r
   static_assert(!PLANE || DEC == 1, "the filtered plane is a working-size image");
   const int frame = (int)blockIdx.z + P.frame0;
   const FrameDesc fd = frames[frame];
+  const int fW = fd.W, fH = fd.H, ftw = fd.tw, fth = fd.th;   // the frame's own extents; the grid is the handle's
+  const int sW0 = PLANE ? fW : fd.W0, sH0 = PLANE ? fH : fd.H0;
   const th_gimg_t simg = PLANE ? (th_gimg_t)(gray_all + (size_t)frame * P.H * P.WS) : (th_gimg_t)fd.img;
   const uint32_t spitch = PLANE ? (uint32_t)P.WS : fd.pitch;
   const int x = (int)(blockIdx.x * 256 + threadIdx.x), y = (int)blockIdx.y;
-  if (x >= P.W) return;
+  if (x >= fW || y >= fH) return;
   const uint8_t* tmin = tmin_all + (size_t)frame * P.tw * P.th;
   const uint8_t* tmax = tmax_all + (size_t)frame * P.tw * P.th;
-  const int tX = min(x / ts, P.tw - 1), tY = min(y / ts, P.th - 1);
+  const int tX = min(x / ts, ftw - 1), tY = min(y / ts, fth - 1);
   uint32_t mn = 255, mx = 0;
-  for (int ty = max(tY - 1, 0); ty <= min(tY + 1, P.th - 1); ty++)
-    for (int tx = max(tX - 1, 0); tx <= min(tX + 1, P.tw - 1); tx++) {
-      mn = min(mn, (uint32_t)tmin[ty * P.tw + tx]);
-      mx = max(mx, (uint32_t)tmax[ty * P.tw + tx]);
+  for (int ty = max(tY - 1, 0); ty <= min(tY + 1, fth - 1); ty++)
+    for (int tx = max(tX - 1, 0); tx <= min(tX + 1, ftw - 1); tx++) {
+      mn = min(mn, (uint32_t)tmin[ty * ftw + tx]);
+      mx = max(mx, (uint32_t)tmax[ty * ftw + tx]);
     }
-  const uint32_t v = th_px<DEC>(simg, spitch, P.W0, P.H0, x, y);
-  const bool in_full_tile = x < P.tw * ts && y < P.th * ts;   // (no low-contrast rule right of / below the last full tile)
+  const uint32_t v = th_px<DEC>(simg, spitch, sW0, sH0, x, y);
+  const bool in_full_tile = x < ftw * ts && y < fth * ts;   // (no low-contrast rule right of / below the last full tile)
   uint8_t o;
   if (in_full_tile && (int)(mx - mn) < P.min_white_black_diff) o = 127;
   else o = v > mn + (mx - mn) / 2 ? 255 : 0;

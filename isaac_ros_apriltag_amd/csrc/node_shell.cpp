@@ -43,6 +43,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsStreamCreate) stream_create = nullptr;
   decltype(&amdAprilTagsStreamDestroy) stream_destroy = nullptr;
   decltype(&amdAprilTagsSetQuadSigma) set_quad_sigma = nullptr;
+  decltype(&amdAprilTagsSetPerFrameSizes) set_per_frame_sizes = nullptr;
 };
 
 DetectorApi& api() {
@@ -78,6 +79,7 @@ DetectorApi& api() {
   BIND(stream_create, "amdAprilTagsStreamCreate")
   BIND(stream_destroy, "amdAprilTagsStreamDestroy")
   BIND(set_quad_sigma, "amdAprilTagsSetQuadSigma")
+  BIND(set_per_frame_sizes, "amdAprilTagsSetPerFrameSizes")
 #undef BIND
   return a;
 }
@@ -366,12 +368,13 @@ struct AprilTagMultiCameraNode::Impl {
   bool cuapriltags_mode = false, auto_flush = true, initialized = false;
   int family_enum = -1;
   amdAprilTagsHandle detector = nullptr;
-  uint32_t width = 0, height = 0;
+  uint32_t width = 0, height = 0;  // the handle's size: the first frame's, or NodeOptions::max_width x max_height
+  bool mixed = false;              // max_width and max_height set: streams of any admissible size, batched together (per-frame sizes)
   uint8_t* d_mono = nullptr;       // S mono8 slots
   size_t pitch = 0, slot_bytes = 0;
   void* d_input = nullptr;         // staging for host / colour frames
   size_t d_input_bytes = 0;
-  struct Slot { bool pending = false; Header info_header; std::array<double, 9> k{}; };
+  struct Slot { bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; };
   std::vector<Slot> slots;
 
 
@@ -381,7 +384,8 @@ struct AprilTagMultiCameraNode::Impl {
     if (detector) { api().destroy(detector); detector = nullptr; }
     if (d_mono) { api().dev_free(d_mono); d_mono = nullptr; }
     amdAprilTagsConfig_t cfg;
-    api().default_config(&cfg, info.width, info.height);
+    mixed = opt.max_width != 0 && opt.max_height != 0;
+    api().default_config(&cfg, mixed ? opt.max_width : info.width, mixed ? opt.max_height : info.height);
     cfg.tile_size = opt.tile_size;
     cfg.decimate = opt.decimate;
     cfg.num_families = 1;
@@ -397,8 +401,9 @@ struct AprilTagMultiCameraNode::Impl {
     const int error = api().create_ex(&detector, &cfg);
     if (error != 0) throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
     apply_quad_sigma(detector, opt.quad_sigma);
-    width = info.width;
-    height = info.height;
+    if (mixed && api().set_per_frame_sizes(detector, 1) != 0) throw std::runtime_error("per-frame image sizes refused");
+    width = cfg.width;
+    height = cfg.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
     slot_bytes = pitch * height;
     void* p = nullptr;
@@ -414,12 +419,20 @@ struct AprilTagMultiCameraNode::Impl {
       std::fprintf(stderr, "[apriltag_node] Unsupported image encoding: %s\n", image.encoding.c_str());
       throw std::runtime_error("AprilTags detector only supports 'mono8', 'rgb8', 'bgr8', 'rgba8' or 'bgra8' image input");
     }
-    if (image.width != width || image.height != height || info.width != width || info.height != height ||
+    // one size (the first frame's), or -- max_width x max_height set -- every size the handle admits (include/apriltag_amd.h,
+    // amdAprilTagsSetPerFrameSizes: up to the handle's, a full threshold tile of the working image in both directions)
+    const auto working = [&](uint32_t v) { return 1 + (v - 1) / opt.decimate; };
+    const bool size_ok = mixed ? image.width >= 1 && image.width <= width && image.height >= 1 && image.height <= height &&
+                                     working(image.width) >= opt.tile_size && working(image.height) >= opt.tile_size
+                               : image.width == width && image.height == height;
+    if (!size_ok || info.width != image.width || info.height != image.height ||
         static_cast<size_t>(image.step) < static_cast<size_t>(image.width) * bpp || image.data == nullptr) {
-      std::fprintf(stderr, "[apriltag_node] stream %u: image %ux%u (step %u) does not match the initialised size %ux%u: frame dropped\n",
-                   stream, image.width, image.height, image.step, width, height);
+      std::fprintf(stderr, "[apriltag_node] stream %u: image %ux%u (step %u) does not match the initialised size %s%ux%u: frame dropped\n",
+                   stream, image.width, image.height, image.step, mixed ? "up to " : "", width, height);
       return false;
     }
+    slots[stream].width = image.width;
+    slots[stream].height = image.height;
     const uint8_t* dev_src = image.data;
     uint8_t* slot = d_mono + slot_bytes * stream;
     if (!image.is_device) {
@@ -495,7 +508,7 @@ uint32_t AprilTagMultiCameraNode::Flush() {
   std::vector<amdAprilTagsCameraIntrinsics_t> intr(n);
   for (uint32_t i = 0; i < n; i++) {
     const Impl::Slot& sl = I.slots[who[i]];
-    imgs[i].width = I.width; imgs[i].height = I.height; imgs[i].dev_ptr = I.d_mono + I.slot_bytes * who[i]; imgs[i].pitch = I.pitch;
+    imgs[i].width = sl.width; imgs[i].height = sl.height; imgs[i].dev_ptr = I.d_mono + I.slot_bytes * who[i]; imgs[i].pitch = I.pitch;
     // K of the stream's own CameraInfo, double -> float as the reference does (src/apriltag_node.cpp:442-447)
     intr[i].fx = static_cast<float>(sl.k[0]); intr[i].fy = static_cast<float>(sl.k[4]);
     intr[i].cx = static_cast<float>(sl.k[2]); intr[i].cy = static_cast<float>(sl.k[5]);
@@ -642,14 +655,16 @@ struct MultiShellHarness {
   std::vector<int> publishes;
 };
 
-MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
-                                              const char* backends, int decimate, int auto_flush, double quad_sigma, char* err,
-                                              size_t err_len) {
+// max_width, max_height: NodeOptions of the same names (0, 0: one size, the first frame's)
+MultiShellHarness* node_shell_multi_create_sized(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                 const char* backends, int decimate, int auto_flush, double quad_sigma,
+                                                 uint32_t max_width, uint32_t max_height, char* err, size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     o.quad_sigma = quad_sigma;
+    o.max_width = max_width; o.max_height = max_height;
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
     h->node->set_auto_flush(auto_flush != 0);
@@ -661,6 +676,13 @@ MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, dou
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+
+MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                              const char* backends, int decimate, int auto_flush, double quad_sigma, char* err,
+                                              size_t err_len) {
+  return node_shell_multi_create_sized(num_streams, max_tags, size, tile_size, tag_family, backends, decimate, auto_flush, quad_sigma, 0, 0,
+                                       err, err_len);
 }
 
 MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,

@@ -17,9 +17,12 @@
 //                           4 = k_quad_sigma's copy rule takes the instance's padded half width KH for the tap half width h on the right
 //                               and bottom edges: wrong values in the last KH - h filtered columns / rows, for h < KH only (h = 3, 5, 6, 7)
 //                           5 = with the quad_sigma filter on at decimate > 1 the decode launch runs as if refine_edges were 0
-//                           (4 and 5 change values only: no address, index bound or launch size)
-//                           the GPU suite ships all five (build.py: build_mutants) and asserts that its stage tests FAIL on each
-//                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds)
+//                           6 = k_cluster_select takes the cluster-size cap from the handle instead of the frame: a smaller frame of a
+//                               per-frame-sizes submission keeps clusters above its own cap (the scratch slots are sized by the handle's cap)
+//                           (4, 5 and 6 change values only: no address, index bound or launch size)
+//                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
+//                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
+//                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -63,6 +66,13 @@
 #define PT_STOP_AT(n, keep_live) if (AMDAT_PT_STOP == (n) && P.max_nmaxima == 10) { keep_live; return; }
 #else
 #define PT_STOP_AT(n, keep_live)
+#endif
+
+// ---- k_cluster_select: the cluster-size cap of a frame (fd: its FrameDesc) ----------------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 6
+#define SEL_CLUSTER_CAP(fd, P) ((void)(fd), (P).max_cluster_points)
+#else
+#define SEL_CLUSTER_CAP(fd, P) ((fd).max_cluster_points)
 #endif
 
 // ---- k_fit_quads --------------------------------------------------------------------------------------------------------

@@ -11,9 +11,12 @@ import numpy as np
 from . import capi
 
 
-def _as_images(frames, width, height, channels=1):
+def _as_images(frames, width, height, channels=1, per_frame=False):
     """frames: torch uint8 CUDA tensor [n,H,W] / [H,W] (colour: [n,H,W,C] / [H,W,C], interleaved), or a list of such tensors,
-    or a list of (dev_ptr, pitch) pairs.  Returns (ctypes array, keepalive)."""
+    or a list of (dev_ptr, pitch) pairs or (dev_ptr, pitch, width, height) tuples.  width, height: the handle's size, which a
+    two-element pair means; with per_frame (the handle's per-frame sizes mode) a tensor brings its own size, from its shape.
+    A four-element tuple always names its own size -- a window is (pointer to its first pixel, the full image's pitch, its
+    width, its height).  Returns (ctypes array, keepalive)."""
     items = []
     if hasattr(frames, "data_ptr"):
         t = frames
@@ -23,8 +26,9 @@ def _as_images(frames, width, height, channels=1):
             assert t.dim() == 3 and t.stride(2) == 1, "expected [n,H,W] mono8 with unit pixel stride"
         else:
             assert t.dim() == 4 and t.shape[3] == channels and t.stride(3) == 1 and t.stride(2) == channels, "expected [n,H,W,C] interleaved"
+        w, h = (int(t.shape[2]), int(t.shape[1])) if per_frame else (width, height)
         for i in range(t.shape[0]):
-            items.append((t[i].data_ptr(), t.stride(1)))
+            items.append((t[i].data_ptr(), t.stride(1), w, h))
     else:
         for f in frames:
             if hasattr(f, "data_ptr"):
@@ -32,18 +36,21 @@ def _as_images(frames, width, height, channels=1):
                     assert f.dim() == 2 and f.stride(1) == 1
                 else:
                     assert f.dim() == 3 and f.shape[2] == channels and f.stride(2) == 1 and f.stride(1) == channels
-                items.append((f.data_ptr(), f.stride(0)))
+                w, h = (int(f.shape[1]), int(f.shape[0])) if per_frame else (width, height)
+                items.append((f.data_ptr(), f.stride(0), w, h))
+            elif len(f) == 4:
+                items.append((int(f[0]), int(f[1]), int(f[2]), int(f[3])))
             else:
-                items.append((int(f[0]), int(f[1])))
+                items.append((int(f[0]), int(f[1]), width, height))
     arr = (capi.ImageInput * len(items))()
-    for i, (ptr, pitch) in enumerate(items):
-        arr[i].width, arr[i].height, arr[i].dev_ptr, arr[i].pitch = width, height, ptr, pitch
+    for i, (ptr, pitch, w, h) in enumerate(items):
+        arr[i].width, arr[i].height, arr[i].dev_ptr, arr[i].pitch = w, h, ptr, pitch
     return arr, frames
 
 
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
-                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, **caps):
+                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -70,16 +77,25 @@ class AprilTagDetector:
         self._h = C.c_void_p()
         capi._check("amdCreateAprilTagsDetectorEx", L.amdCreateAprilTagsDetectorEx(C.byref(self._h), C.byref(cfg)))
         self._L = L
-        if quad_sigma:
-            try:
+        self.per_frame_sizes = False
+        try:
+            if quad_sigma:
                 self.set_quad_sigma(quad_sigma)
-            except Exception:
-                self.close()
-                raise
+            if per_frame_sizes:
+                self.set_per_frame_sizes(True)
+        except Exception:
+            self.close()
+            raise
 
     def set_quad_sigma(self, sigma):
         """quad_sigma (amdAprilTagsSetQuadSigma): blur (> 0) or sharpen (< 0) of the working image; takes effect with the next submission."""
         capi._check("amdAprilTagsSetQuadSigma", self._L.amdAprilTagsSetQuadSigma(self._h, float(sigma)))
+
+    def set_per_frame_sizes(self, enable=True):
+        """amdAprilTagsSetPerFrameSizes: every frame of a submission brings its own size, up to the handle's (width, height are then
+        the largest frame); tensors are taken at their shape, (dev_ptr, pitch, width, height) tuples as they say."""
+        capi._check("amdAprilTagsSetPerFrameSizes", self._L.amdAprilTagsSetPerFrameSizes(self._h, 1 if enable else 0))
+        self.per_frame_sizes = bool(enable)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -95,7 +111,7 @@ class AprilTagDetector:
     # ---- detection --------------------------------------------------------------------------------
     def detect_batch_ex(self, frames, max_dets=64, intrinsics=None, stream=None, encoding="mono8"):
         """encoding != "mono8": frames are interleaved colour ([n,H,W,C]) and go through amdAprilTagsDetectBatchColorEx."""
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding])
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes)
         n = len(imgs)
         out = (capi.DetectionEx * (n * max_dets))()
         cnt = (C.c_uint32 * n)()
@@ -123,7 +139,7 @@ class AprilTagDetector:
 
     # ---- prepared submissions: argument marshalling done once, the timed call is only the C ABI call ----
     def prepare(self, frames, max_dets=64, intrinsics=None, encoding="mono8"):
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding])
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes)
         n = len(imgs)
         intr = None
         if intrinsics is not None:
@@ -172,7 +188,7 @@ class AprilTagDetector:
 
     def detect_batch_raw(self, frames, max_tags=64, intrinsics=None, stream=None):
         """Returns (TagID ctypes array of n*max_tags, counts) -- the cuAprilTagsID_t-shaped records."""
-        imgs, keep = _as_images(frames, self.width, self.height)
+        imgs, keep = _as_images(frames, self.width, self.height, 1, self.per_frame_sizes)
         n = len(imgs)
         out = (capi.TagID * (n * max_tags))()
         cnt = (C.c_uint32 * n)()
@@ -184,7 +200,7 @@ class AprilTagDetector:
         return out, [int(c) for c in cnt]
 
     def threshold_only(self, frames, stream=None, encoding="mono8"):
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding])
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes)
         if encoding == "mono8":
             capi._check("amdAprilTagsThresholdOnly", self._L.amdAprilTagsThresholdOnly(self._h, len(imgs), imgs, stream))
         else:

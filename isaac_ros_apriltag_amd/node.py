@@ -42,6 +42,9 @@ def lib():
         L.node_shell_multi_create_ex.restype = C.c_void_p
         L.node_shell_multi_create_ex.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                                  C.c_double, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_sized.restype = C.c_void_p
+        L.node_shell_multi_create_sized.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                    C.c_double, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
         L.node_shell_multi_destroy.argtypes = [C.c_void_p]
         L.node_shell_multi_on_frame.restype = C.c_int
         L.node_shell_multi_on_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -72,11 +75,14 @@ class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True, quad_sigma=0.0):
+                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0):
+        """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
+        sizes); 0: one size, the first frame's, and frames of another size are dropped."""
         err = C.create_string_buffer(1024)
         self._L = lib()
-        self._h = self._L.node_shell_multi_create_ex(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
-                                                     decimate, 1 if auto_flush else 0, float(quad_sigma), err, 1024)
+        self._h = self._L.node_shell_multi_create_sized(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
+                                                        decimate, 1 if auto_flush else 0, float(quad_sigma), int(max_width),
+                                                        int(max_height), err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags, self.num_streams = max_tags, num_streams
