@@ -1151,7 +1151,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
             for (int j = 0; j < 6; j++) sP[(g + 1) * 6 + j] = (off[j].hi + acc[j].hi) + (off[j].lo + acc[j].lo);
           }
           __syncthreads();
-          if (!fq_feasible<NT, 6, 5>(sP, P.max_line_fit_mse, W, H, s_okf, s_okw, &s_feasible)) { FQ_COUNT(2, sz) continue; }
+          if (!fq_feasible<NT, 6, 5>(sP, FQ_GROUP_TEST_MSE(NT, P.max_line_fit_mse), W, H, s_okf, s_okw, &s_feasible)) { FQ_COUNT(2, sz) continue; }
         }
       } else {
 #pragma unroll
@@ -1256,7 +1256,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
             U128 run = s_carry[par * 6 + j];
             for (int w2 = 0; w2 < ww; w2++) run = u128_add(run, s_wtot[w2 * 6 + j]);
             s_woff[tid] = run;
-            if (ww == NW - 1) s_carry[(par ^ 1) * 6 + j] = u128_add(run, s_wtot[ww * 6 + j]);
+            if (ww == NW - 1) s_carry[(par ^ 1) * 6 + j] = u128_add(run, FQ_CARRY_LAST_WAVE(s_wtot[ww * 6 + j]));   // (tools_hooks.h: the totals themselves in the product build)
           } else if (tid < NW * 7) {
             const int ww = tid - NW * 6;
             int run = 0;

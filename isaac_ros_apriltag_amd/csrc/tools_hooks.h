@@ -19,10 +19,20 @@
 //                           5 = with the quad_sigma filter on at decimate > 1 the decode launch runs as if refine_edges were 0
 //                           6 = k_cluster_select takes the cluster-size cap from the handle instead of the frame: a smaller frame of a
 //                               per-frame-sizes submission keeps clusters above its own cap (the scratch slots are sized by the handle's cap)
-//                           (4, 5 and 6 change values only: no address, index bound or launch size)
+//                           7 = the group test after the first walk of the two-double sweep (fq_feasible, k_fit_quads<256, true> and
+//                               <1024, true> only) is handed a quarter of max_line_fit_mse: it then "proves" quads impossible whose sides
+//                               fit a line at a mean square error between a quarter of the limit and the limit, and drops them
+//                           8 = the general sweep of k_fit_quads<NT, false>, NT >= 128 (working images above 2048 pixels a side): the last
+//                               wave's totals enter the running carry from chunk to chunk twice, so every prefix behind a chunk's end is
+//                               too large by them.  (Twice, not once too few or with the wrong sign: the prefixes stay the increasing,
+//                               positive moments of a point set -- the cluster with some points counted double -- so no window has a
+//                               weight of zero or below, nothing downstream meets a NaN or an infinity it does not meet in the product
+//                               build, and the wrong build can only give wrong quads.)
+//                           (4 .. 8 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
-//                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6)
+//                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
+//                           tests/test_fit_classes_gpu.py::test_fit_class_tests_fail_on_the_wrong_builds for 7 and 8)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -152,6 +162,18 @@
 #define PF_MUT_EXTRA_SECTOR(nt) ((nt) == 64 ? 1 : 0)
 #else
 #define PF_MUT_EXTRA_SECTOR(nt) 0
+#endif
+// the line-fit limit the group test after the first walk is handed (NT: the instance's threads)
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 7
+#define FQ_GROUP_TEST_MSE(NT, mse) (((NT) == 256 || (NT) == 1024) ? 0.25 * (mse) : (mse))
+#else
+#define FQ_GROUP_TEST_MSE(NT, mse) (mse)
+#endif
+// what the last wave of a chunk adds to the general sweep's running carry (t: its totals, a U128)
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 8
+#define FQ_CARRY_LAST_WAVE(t) u128_add((t), (t))
+#else
+#define FQ_CARRY_LAST_WAVE(t) (t)
 #endif
 #ifdef AMDAT_FQ_NO_EARLY_EXIT
 #define FQ_SOUND_EXIT_AFTER_WALK1 0

@@ -1648,10 +1648,12 @@ def test_long_staging_records_with_a_short_tile_list(built):
 
 def _big_quads_frame(amp, w=1920, h=1080):
     """Three large dark quadrilaterals on a bright ground -- a 760 x 640 rectangle, a rotated 460-px square and a tilted 920 x 340
-    one -- whose edges ripple with amplitude `amp` pixels, under sigma-1 noise: boundaries of 5 000 .. 8 000 points each, i.e.
-    clusters of the size classes above 2048 points, which go through k_fit_prefilter before their fit.  amp = 0: three clean
-    quads; amp = 3.2: the line fits of the sides come out at a mean square error of about 5 of the 10 a side may have, so the
-    sound sector test has to pass them on a margin a wrong test does not leave."""
+    one -- whose edges ripple with amplitude `amp` pixels, under sigma-1 noise: boundaries of 5 000 .. 8 000 points each, which
+    go through k_fit_prefilter before their fit.  amp = 0: three clean quads; amp = 3.2: the line fits of the sides come out at a
+    mean square error of about 5 of the 10 a side may have, so the sound sector test has to pass them on a margin a wrong test
+    does not leave.  All of these quads sit in ONE size class, 4097 .. 8192 points (512 threads): clusters of 4984, 5592 and 5600
+    points at amp 0, of 5144 and 7716 at amp 3.2.  The frame's other clusters above 2048 points are noise blobs that neither side
+    keeps, so the 256- and the 1024-thread class are not under test here (tests/test_fit_classes_gpu.py has quads in both)."""
     rng = np.random.default_rng(606)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
     img = np.full((h, w), 215.0)
@@ -1671,9 +1673,10 @@ def _big_quads_frame(amp, w=1920, h=1080):
 @pytest.mark.parametrize("path", PATHS)
 @pytest.mark.parametrize("amp,nbig", [(0.0, 3), (3.2, 2)])
 def test_large_quads_survive_the_prefilter(built, path, amp, nbig):
-    """Clusters above 2048 points that ARE quads: the sound sector test of k_fit_prefilter (one wave per cluster on the throughput
-    set, a CU-wide workgroup on the latency set) must let every one of them through to its fit -- clean ones and ones whose sides
-    fit a line only just; quads equal the oracle's, and the large ones are among them."""
+    """Clusters of 4097 .. 8192 points that ARE quads: the sound sector test of k_fit_prefilter (one wave per cluster on the
+    throughput set, a CU-wide workgroup on the latency set) must let every one of them through to its fit -- clean ones and ones
+    whose sides fit a line only just; quads equal the oracle's, and the large ones are among them.  (One size class only, see
+    _big_quads_frame; the others: tests/test_fit_classes_gpu.py.)"""
     img = _big_quads_frame(amp)
     K = synth.default_K(1920, 1080)
     det, g = _run(img, K, path=path)
