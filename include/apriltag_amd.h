@@ -289,6 +289,30 @@ int amdAprilTagsSetQuadSigma(amdAprilTagsHandle handle, float quad_sigma);
  * graphs as amdAprilTagsSetQuadSigma: set it once after create. */
 int amdAprilTagsSetPerFrameSizes(amdAprilTagsHandle handle, int enable);
 
+/* Rectification inside the submission: per-camera plumb_bob undistortion of every frame, batched, ahead of detection.
+ * K, Knew: row-major 3x3; D = k1, k2, p1, p2, k3 (sensor_msgs/CameraInfo, distortion_model "plumb_bob"). */
+typedef struct { double K[9]; double D[5]; double Knew[9]; } amdAprilTagsCameraModel_t;  /* row-major 3x3; plumb_bob */
+/* ncams = 0 turns rectification off (the default: nothing changes).  Otherwise frame i of every following submission is first
+ * undistorted with cams[i % ncams] -- one camera for every slot with ncams = 1, a camera per slot with ncams = n -- into a plane
+ * the handle owns, and detected there: its records are exactly those of the same handle given the rectified frame R as a mono8 frame,
+ * at every decimate, tile_size and quad_sigma.  R has the frame's own size w x h and R(x, y) is what amdAprilTagsRectifyMono8 computes
+ * (the same double-precision projection, 1/32-pixel position, integer bilinear sum, 0 outside the source); a colour frame is first
+ * turned into gray tap by tap with the fixed-point BT.601 weights of amdAprilTagsConvertToMono8, so R = rectify(convert(frame))
+ * (DESIGN.md section 7b).  One launch per submission covers all frames; the caller's buffers are never written.
+ * The library does NOT touch the pose intrinsics: the rectified image's camera is Knew, so pass {Knew[0], Knew[4], Knew[2], Knew[5]}
+ * as per_frame_intrinsics (or in the handle's configuration), and Knew[1] through amdAprilTagsSetFrameSkews where it matters.
+ * The models are host state of the handle, as the frame skews are, and travel to the device with each submission's descriptors: the
+ * call makes no device synchronisation and a front end may call it before every flush.  The first call that turns rectification on
+ * allocates the rectified plane (max_batch full-size mono8 frames).  Applies to every submitting call of this header -- Detect[Color],
+ * DetectBatch[Color][Ex], SubmitBatch[Color] / WaitBatch[Ex] -- on both launch sets, and with amdAprilTagsSetPerFrameSizes on (each
+ * frame's own width x height bounds its model; a window is rectified as the cropped array).  amdAprilTagsThresholdOnly[Color] of the
+ * debug header never rectifies.
+ * Callable whenever no submission is in flight.  AMDAT_INVALID_ARGUMENT: null handle, null cams with ncams > 0, ncams > max_batch, a
+ * non-finite entry, Knew[0] == 0 or Knew[4] == 0, a submission in flight; AMDAT_OUT_OF_MEMORY: the plane could not be allocated.  A
+ * refused call leaves the previous setting in force.  Turning the mode on or off retires the handle's captured launch graphs, against
+ * the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the models does not. */
+int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModel_t* cams);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 
@@ -310,7 +334,8 @@ int amdAprilTagsResizeMono8(const uint8_t* src_dev, size_t src_pitch, uint32_t s
 /* Undistortion of a plumb_bob image (sensor_msgs/CameraInfo K and D = k1,k2,p1,p2,k3) onto the pinhole
  * camera K_new (row-major 3x3 each): every destination pixel is projected through the distortion model
  * in double precision, the source position is quantised to 1/32 pixel and sampled bilinearly in integer
- * arithmetic; pixels that map outside the source are 0 (oracle: ato_rectify_mono8). */
+ * arithmetic; pixels that map outside the source are 0 (oracle: ato_rectify_mono8).  One frame per call on the
+ * caller's stream; amdAprilTagsSetRectification does the same inside the submission, for every frame at once. */
 int amdAprilTagsRectifyMono8(const uint8_t* src_dev, size_t src_pitch, uint8_t* dst_dev, size_t dst_pitch, uint32_t width,
                              uint32_t height, const double* K9, const double* D5, const double* Knew9,
                              amdAprilTagsStream stream);

@@ -40,7 +40,21 @@ struct CameraInfo {
   Header header;
   uint32_t height = 0, width = 0;
   std::array<double, 9> k{};  // the node reads K (k[0],k[4],k[2],k[5]), src/apriltag_node.cpp:442-446
+  // read only with NodeOptions::rectify (RectificationModel below)
+  std::vector<double> d;            // distortion coefficients: k1, k2, p1, p2, k3 of "plumb_bob" (fewer: zero-padded)
+  std::string distortion_model;     // "plumb_bob" or empty
+  std::array<double, 12> p{};       // projection matrix: its left 3x3 is the rectified image's camera when p[0] != 0
 };
+
+// The camera model NodeOptions::rectify hands the detector (amdAprilTagsCameraModel_t): K and D of the distorted image, and the
+// pinhole camera Knew of the rectified one -- the left 3x3 of P when p[0] != 0, K otherwise.
+struct CameraModel {
+  std::array<double, 9> k{};
+  std::array<double, 5> d{};
+  std::array<double, 9> knew{};
+};
+// Throws std::runtime_error for a distortion_model other than "plumb_bob" / empty and for more than five coefficients.
+CameraModel RectificationModel(const CameraInfo& camera_info);
 
 struct Point { double x = 0, y = 0, z = 0; };
 struct Quaternion { double x = 0, y = 0, z = 0, w = 1; };
@@ -80,6 +94,11 @@ struct NodeOptions {
   // rig.  Both set: the handle is created at max_width x max_height with per-frame image sizes on (amdAprilTagsSetPerFrameSizes), and
   // streams of every admissible size are batched together.  0 (the default): one size, the first frame's; other sizes are dropped.
   uint32_t max_width = 0, max_height = 0;
+  // Extension: the frames come from a distorted camera and are undistorted INSIDE the detector's submission (amdAprilTagsSetRectification;
+  // the reference puts a RectifyNode in front, launch/isaac_ros_apriltag_usb_cam.launch.py:43-63).  The model is RectificationModel of the
+  // stream's CameraInfo (AprilTagNode: of the first frame's, like K; AprilTagMultiCameraNode: of every staged frame's, set before each
+  // flush in slot order), and the pose is computed with Knew -- fx, fy, cx, cy, and its [0][1] as the skew in VPI mode -- in place of K.
+  bool rectify = false;
 };
 
 class AprilTagNode {

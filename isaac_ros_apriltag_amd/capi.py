@@ -15,6 +15,7 @@ NUM_STAGES = 12
 FAMILY_ENUM = {"tag36h11": 0, "tag25h9": 1, "tag16h5": 2}
 SLOT_TAG36H10, SLOT_CUSTOM0 = 3, 4   # registrable slots: 3 (tag36h10: no built-in table) and 4..8
 (DBG_GRAY, DBG_THRESH, DBG_LABEL, DBG_CSIZE, DBG_CLUSTERS, DBG_POINTS, DBG_QUADS, DBG_COUNTS) = range(8)
+DBG_RECTIFIED = 9   # u8 W0 x H0: the frame's rectified plane (amdAprilTagsSetRectification)
 
 STATUS = {0: "AMDAT_SUCCESS", 1: "AMDAT_INVALID_ARGUMENT", 2: "AMDAT_UNSUPPORTED", 3: "AMDAT_HIP_ERROR",
           4: "AMDAT_SIZE_MISMATCH", 5: "AMDAT_OUT_OF_MEMORY", 6: "AMDAT_BATCH_TOO_LARGE"}
@@ -26,6 +27,11 @@ class Intrinsics(C.Structure):
 
 class ImageInput(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("dev_ptr", C.c_void_p), ("pitch", C.c_size_t)]
+
+
+class CameraModel(C.Structure):
+    """amdAprilTagsCameraModel_t: row-major 3x3 K and Knew, plumb_bob D = k1, k2, p1, p2, k3."""
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 5), ("Knew", C.c_double * 9)]
 
 
 class Float2(C.Structure):
@@ -68,7 +74,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsEncodingFromName", "amdAprilTagsDetectColor", "amdAprilTagsDetectBatchColor", "amdAprilTagsDetectBatchColorEx",
            "amdAprilTagsSubmitBatchColor", "amdAprilTagsThresholdOnlyColor", "amdAprilTagsCopyToDeviceAsync", "amdAprilTagsStreamCreate",
            "amdAprilTagsStreamDestroy", "amdAprilTagsDebugGraphReplay", "amdAprilTagsConfigLayoutVersion",
-           "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes"]
+           "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes",
+           "amdAprilTagsSetRectification"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 ENC_CHANNELS = {"mono8": 1, "rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4}
@@ -143,6 +150,7 @@ def lib():
     L.amdAprilTagsDebugMath.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.amdAprilTagsSetQuadSigma.argtypes = [H, C.c_float]
     L.amdAprilTagsSetPerFrameSizes.argtypes = [H, C.c_int]
+    L.amdAprilTagsSetRectification.argtypes = [H, C.c_uint32, C.POINTER(CameraModel)]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -203,6 +211,22 @@ def debug_math(op, a, b):
     out = np.empty_like(a)
     _check("amdAprilTagsDebugMath", lib().amdAprilTagsDebugMath(op, a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data))
     return out
+
+
+def camera_models(models):
+    """[(K, D, Knew)] -> a ctypes array of amdAprilTagsCameraModel_t (None for an empty list).  K, Knew: 3x3 or 9 values; D: up to five
+    plumb_bob coefficients, zero-padded."""
+    models = list(models or [])
+    if not models:
+        return None
+    arr = (CameraModel * len(models))()
+    for m, (K, D, Knew) in zip(arr, models):
+        k, d, kn = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (K, D, Knew))
+        if k.size != 9 or kn.size != 9 or d.size > 5:
+            raise ValueError("a camera model is (K[3x3], D[<= 5], Knew[3x3])")
+        m.K[:], m.Knew[:] = list(k), list(kn)
+        m.D[:] = list(d) + [0.0] * (5 - d.size)
+    return arr
 
 
 def quad_sigma_taps(sigma):

@@ -249,6 +249,13 @@ struct amdAprilTagsDetector_st {
   QsTaps qs = {};
   // amdAprilTagsSetPerFrameSizes: every frame of a submission brings its own size, up to the handle's (check_images, fill_frames)
   bool per_frame_sizes = false;
+  // amdAprilTagsSetRectification: frame i of a submission is undistorted with rect_models[i % size] into slot i of the rectified plane
+  // (d_conv: a rectified submission never takes the conversion launch) by k_rectify_frames, and the pipeline sees that slot as a mono8 frame
+  std::vector<amdAprilTagsCameraModel_t> rect_models;   // empty: off
+  RectDesc* h_rdesc = nullptr;                          // pinned, one per batch slot: k_prologue uploads them with the frame descriptors
+  DevBuf<RectDesc> d_rdesc;
+  std::vector<amdAprilTagsImageInput_t> rect_imgs;      // the plane's slots as the mono8 images of the submission (fill_rect)
+  bool last_rectified = false;                          // the last submission rectified (AMDAT_DBG_RECTIFIED)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -481,6 +488,7 @@ static void free_all(amdAprilTagsDetector_st* D) {
   if (D->h_frames) hipHostFree(D->h_frames);
   if (D->h_counters) hipHostFree(D->h_counters);
   if (D->h_out) hipHostFree(D->h_out);
+  if (D->h_rdesc) hipHostFree(D->h_rdesc);
   for (auto& e : D->ev) if (e) hipEventDestroy(e);
   if (D->own_stream) hipStreamDestroy(D->own_stream);
   for (auto& a : D->aux_stream) if (a) hipStreamDestroy(a);
@@ -886,6 +894,46 @@ int amdAprilTagsSetPerFrameSizes(amdAprilTagsHandle handle, int enable) {
   return AMDAT_SUCCESS;
 }
 
+// What the first call that turns rectification on allocates: the rectified plane (max_batch full-size mono8 frames: d_conv, with its
+// pitch) and the descriptor blocks of k_rectify_frames.
+static int ensure_rect_buffers(amdAprilTagsDetector_st* D) {
+  const size_t B = D->cfg.max_batch;
+  if (!D->d_conv) {
+    D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
+    if (!dev_alloc(D, D->d_conv, B * D->conv_pitch * D->cfg.height)) return AMDAT_OUT_OF_MEMORY;
+  }
+  if (!D->d_rdesc && !dev_alloc(D, D->d_rdesc, B * sizeof(RectDesc))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->h_rdesc) {
+    if (hipHostMalloc((void**)&D->h_rdesc, B * sizeof(RectDesc), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+      D->h_rdesc = nullptr;
+      (void)hipGetLastError();
+      return AMDAT_OUT_OF_MEMORY;
+    }
+    memset(D->h_rdesc, 0, B * sizeof(RectDesc));
+  }
+  D->rect_imgs.resize(B);
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModel_t* cams) {
+  if (!handle || handle->inflight.active || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  for (uint32_t c = 0; c < ncams; c++) {
+    for (double v : cams[c].K) if (!std::isfinite(v)) return AMDAT_INVALID_ARGUMENT;
+    for (double v : cams[c].D) if (!std::isfinite(v)) return AMDAT_INVALID_ARGUMENT;
+    for (double v : cams[c].Knew) if (!std::isfinite(v)) return AMDAT_INVALID_ARGUMENT;
+    if (cams[c].Knew[0] == 0.0 || cams[c].Knew[4] == 0.0) return AMDAT_INVALID_ARGUMENT;
+  }
+  const bool on = ncams > 0;
+  if (on != !handle->rect_models.empty()) {
+    DeviceGuard guard(handle->device);
+    if (!guard.ok) return AMDAT_HIP_ERROR;
+    if (on) { const int rc = ensure_rect_buffers(handle); if (rc) return rc; }
+    drop_graphs(handle);   // captured with or without the rectification launch; the models themselves travel through the descriptors
+  }
+  handle->rect_models.assign(cams, cams + ncams);
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
   if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
   if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
@@ -1003,6 +1051,27 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
   }
 }
 
+// Rectification on: the descriptors of k_rectify_frames for the caller's frames (encoding fmt), and the plane's slots as the mono8
+// images the rest of the submission is filled from.
+static const amdAprilTagsImageInput_t* fill_rect(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
+  const uint32_t ncams = (uint32_t)D->rect_models.size();
+  for (uint32_t i = 0; i < n; i++) {
+    const amdAprilTagsCameraModel_t& m = D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)];   // (tools_hooks.h: i % ncams)
+    RectDesc& r = D->h_rdesc[i];
+    r.src = images[i].dev_ptr;
+    r.src_pitch = (uint32_t)images[i].pitch;
+    r.dst = D->d_conv + (size_t)i * D->conv_pitch * D->cfg.height;
+    r.dst_pitch = (uint32_t)D->conv_pitch;
+    r.fmt = fmt;
+    r.W0 = (int32_t)images[i].width; r.H0 = (int32_t)images[i].height;
+    r.model = {m.K[0], m.K[4], m.K[2], m.K[5], m.D[0], m.D[1], m.D[2], m.D[3], m.D[4], m.Knew[0], m.Knew[4], m.Knew[2], m.Knew[5]};
+    D->rect_imgs[i] = images[i];
+    D->rect_imgs[i].dev_ptr = r.dst;
+    D->rect_imgs[i].pitch = D->conv_pitch;
+  }
+  return D->rect_imgs.data();
+}
+
 // The quad_sigma filter of a submission: each frame's working image (decimate 1: `src`, mono8 or colour; otherwise `img` sampled at the
 // decimation) filtered into its slot of d_gray.
 static void launch_quad_sigma(amdAprilTagsDetector_st* D, const DetParams& P, uint32_t n, hipStream_t s, uint32_t fmt) {
@@ -1087,9 +1156,11 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
 // first launch of a submission: frame descriptors from the pinned host block to device memory, work-list control words
 // and frame counters to zero (one block per frame)
 __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ host_frames, uint32_t* __restrict__ frames,
-                                                 uint32_t* __restrict__ workctl, uint32_t* __restrict__ counters, int fd_words, int fc_words) {
+                                                 uint32_t* __restrict__ workctl, uint32_t* __restrict__ counters, int fd_words, int fc_words,
+                                                 const uint32_t* __restrict__ host_rdesc, uint32_t* __restrict__ rdesc, int rd_words) {
   const int frame = (int)blockIdx.x, t = (int)threadIdx.x;
   for (int i = t; i < fd_words; i += 64) frames[frame * fd_words + i] = host_frames[frame * fd_words + i];
+  for (int i = t; i < rd_words; i += 64) rdesc[frame * rd_words + i] = host_rdesc[frame * rd_words + i];   // (rectification off: no words)
   for (int i = t; i < fc_words; i += 64) counters[frame * fc_words + i] = 0u;
   if (frame == 0 && t < 32) workctl[t] = 0u;
 }
@@ -1205,14 +1276,21 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
 // Everything one submission enqueues on stream s (and the auxiliary streams forked from it): descriptor upload, clears,
 // the stage sequence, result download.  No host synchronisation inside, so the sequence can be stream-captured.
 static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride, hipStream_t s, uint32_t fmt, const std::function<void()>& mark) {
+  const bool rect = !D->rect_models.empty();   // (the setter refuses while a submission is in flight: a regrowth relaunch rectifies again)
   mark();
   // descriptor upload + clears in one small kernel (it reads the pinned descriptor block over the bus itself): a copy
   // command and a fill command ahead of the first kernel cost a one-frame call about 15 us, this launch 4
   static_assert(sizeof(FrameDesc) % 4 == 0 && sizeof(FrameDesc) <= 256 && sizeof(FrameCounters) % 4 == 0 && sizeof(FrameCounters) <= 256, "k_prologue: one word per thread");
   hipLaunchKernelGGL(k_prologue, dim3(n), dim3(64), 0, s, reinterpret_cast<const uint32_t*>(D->h_frames),
                      static_cast<uint32_t*>(D->d_frames.p), D->d_workctl, reinterpret_cast<uint32_t*>(D->d_counters),
-                     (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4));
+                     (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4), reinterpret_cast<const uint32_t*>(D->h_rdesc),
+                     static_cast<uint32_t*>(D->d_rdesc.p), rect ? (int)(sizeof(RectDesc) / 4) : 0);
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
+  // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
+  // (the grid is the handle's size; blocks beyond a frame's own extent return)
+  if (rect)
+    hipLaunchKernelGGL(k_rectify_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
+                       D->d_rdesc);
   mark();
   {
     const int rc = issue_pipeline(D, n, ostride, s, fmt, mark);
@@ -1444,6 +1522,11 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   if (!guard.ok) return AMDAT_HIP_ERROR;
   if (D->unusable) return AMDAT_OUT_OF_MEMORY;   // (never launch on the half-allocated buffers of a failed regrowth)
   const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
+  D->last_rectified = !D->rect_models.empty();
+  if (D->last_rectified) {   // from here on a mono8 submission of the rectified plane's slots
+    images = fill_rect(D, n, images, fmt);
+    fmt = AMDAT_ENC_MONO8;
+  }
   { const int crc = ensure_colour_plane(D, fmt, filt); if (crc) return crc; }
   fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
   D->last_n = n;
@@ -1655,6 +1738,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   if (rc) return rc;
   fill_frames(handle, n, images, nullptr, fmt);
   handle->last_n = n;
+  handle->last_rectified = false;   // (never rectifies)
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));
   if (handle->profiling) hipEventRecord(handle->ev[1], s);
   { DetParams P0 = handle->P; P0.frame0 = 0; launch_threshold(handle, P0, n, s, fmt); }
@@ -1780,6 +1864,16 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       HIP_TRY(hipMemcpy2D(tmp.data(), fW, base, pitch, fW, fH, hipMemcpyDeviceToHost));
       *bytes = npx;
       if (host_dst) memcpy(host_dst, tmp.data(), npx < capacity ? npx : capacity);
+      return AMDAT_SUCCESS;
+    }
+    case AMDAT_DBG_RECTIFIED: {   // W0 x H0 dense: the frame's slot of the rectified plane
+      if (handle->rect_models.empty() || !handle->last_rectified) return AMDAT_INVALID_ARGUMENT;
+      const RectDesc& r = handle->h_rdesc[frame];
+      const size_t n0 = (size_t)r.W0 * r.H0;
+      tmp.resize(n0);
+      HIP_TRY(hipMemcpy2D(tmp.data(), r.W0, r.dst, r.dst_pitch, r.W0, r.H0, hipMemcpyDeviceToHost));
+      *bytes = n0;
+      if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
       return AMDAT_SUCCESS;
     }
     case AMDAT_DBG_LABEL: {

@@ -34,29 +34,142 @@ struct RectifyParams {
   double nfx, nfy, ncx, ncy;    // destination (pinhole) camera
 };
 
+// ---- the rectification statement (oracle: ato_rectify_mono8), stated once for k_rectify_mono8 and k_rectify_frames.
+// The projection of destination pixel (x, y) is split where its operands allow: what depends on x alone, what on y alone, and the
+// rest.  Every operation below is the oracle's, on the oracle's operands, in the oracle's order (no re-association, and
+// -ffp-contract=off keeps every product and sum its own IEEE operation): a term formed once and used for many pixels has the value
+// it has when it is formed per pixel.
+struct RectCol { double xn, xx, txx, p1x, p2x; };   // xn = (x - ncx) / nfx, xn * xn, 2.0 * xn * xn, 2.0 * p1 * xn, 2.0 * p2 * xn
+struct RectRow { double yn, yy, tyy; };             // yn = (y - ncy) / nfy, yn * yn, 2.0 * yn * yn
+// one sample: the four source pixels of a destination pixel and their 1/32 weights
+struct RectTaps { int x0, y0, x1, y1, wx, wy; };
+
+__device__ __forceinline__ RectCol rect_col(int x, const RectifyParams& R) {
+  RectCol c;
+  c.xn = ((double)x - R.ncx) / R.nfx;
+  c.xx = c.xn * c.xn;
+  c.txx = 2.0 * c.xn * c.xn;
+  c.p1x = 2.0 * R.p1 * c.xn;
+  c.p2x = 2.0 * R.p2 * c.xn;
+  return c;
+}
+__device__ __forceinline__ RectRow rect_row(int y, const RectifyParams& R) {
+  RectRow r;
+  r.yn = ((double)y - R.ncy) / R.nfy;
+  r.yy = r.yn * r.yn;
+  r.tyy = 2.0 * r.yn * r.yn;
+  return r;
+}
+// false: the pixel maps outside the source (its value is 0)
+__device__ __forceinline__ bool rect_taps(const RectCol& c, const RectRow& r, const RectifyParams& R, int w, int h, RectTaps& t) {
+  // normalised pinhole ray of the destination pixel, then the plumb_bob model, then source pixels
+  const double xn = c.xn, yn = r.yn;
+  const double r2 = c.xx + r.yy;
+  const double radial = 1.0 + r2 * (R.k1 + r2 * (R.k2 + r2 * R.k3));
+  const double xd = xn * radial + (c.p1x * yn + R.p2 * (r2 + c.txx));
+  const double yd = yn * radial + (R.p1 * (r2 + r.tyy) + c.p2x * yn);
+  const double u = R.fx * xd + R.cx, v = R.fy * yd + R.cy;
+  if (!(u >= 0.0 && v >= 0.0 && u <= (double)(w - 1) && v <= (double)(h - 1))) return false;
+  const int fu = RECT_FIXED(u), fv = RECT_FIXED(v);  // 1/32 pixel (tools_hooks.h: (int)(u * 32.0 + 0.5))
+  t.x0 = fu >> 5; t.y0 = fv >> 5; t.wx = fu & 31; t.wy = fv & 31;
+  if (t.x0 >= w - 1) { t.x0 = w - 1; t.wx = 0; }
+  if (t.y0 >= h - 1) { t.y0 = h - 1; t.wy = 0; }
+  t.x1 = min(t.x0 + 1, w - 1); t.y1 = min(t.y0 + 1, h - 1);
+  return true;
+}
+__device__ __forceinline__ uint32_t rect_blend(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, const RectTaps& t) {
+  const uint32_t top = p00 * (32 - t.wx) + p01 * t.wx, bot = p10 * (32 - t.wx) + p11 * t.wx;
+  return (top * (32 - t.wy) + bot * t.wy + 512) >> 10;
+}
+
 __global__ __launch_bounds__(256) void k_rectify_mono8(const uint8_t* __restrict__ src, size_t spitch, uint8_t* __restrict__ dst,
                                                        size_t dpitch, int w, int h, RectifyParams R) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
-  // normalised pinhole ray of the destination pixel, then the plumb_bob model, then source pixels
-  const double xn = ((double)x - R.ncx) / R.nfx, yn = ((double)y - R.ncy) / R.nfy;
-  const double r2 = xn * xn + yn * yn;
-  const double radial = 1.0 + r2 * (R.k1 + r2 * (R.k2 + r2 * R.k3));
-  const double xd = xn * radial + (2.0 * R.p1 * xn * yn + R.p2 * (r2 + 2.0 * xn * xn));
-  const double yd = yn * radial + (R.p1 * (r2 + 2.0 * yn * yn) + 2.0 * R.p2 * xn * yn);
-  const double u = R.fx * xd + R.cx, v = R.fy * yd + R.cy;
   uint8_t out = 0;
-  if (u >= 0.0 && v >= 0.0 && u <= (double)(w - 1) && v <= (double)(h - 1)) {
-    const int fu = (int)(u * 32.0 + 0.5), fv = (int)(v * 32.0 + 0.5);  // 1/32 pixel
-    int x0 = fu >> 5, y0 = fv >> 5, wx = fu & 31, wy = fv & 31;
-    if (x0 >= w - 1) { x0 = w - 1; wx = 0; }
-    if (y0 >= h - 1) { y0 = h - 1; wy = 0; }
-    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
-    const uint32_t p00 = src[(size_t)y0 * spitch + x0], p01 = src[(size_t)y0 * spitch + x1];
-    const uint32_t p10 = src[(size_t)y1 * spitch + x0], p11 = src[(size_t)y1 * spitch + x1];
-    const uint32_t top = p00 * (32 - wx) + p01 * wx, bot = p10 * (32 - wx) + p11 * wx;
-    out = (uint8_t)((top * (32 - wy) + bot * wy + 512) >> 10);
+  RectTaps t;
+  if (rect_taps(rect_col(x, R), rect_row(y, R), R, w, h, t)) {
+    const uint8_t *r0 = src + (size_t)t.y0 * spitch, *r1 = src + (size_t)t.y1 * spitch;
+    out = (uint8_t)rect_blend(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t);
   }
   dst[(size_t)y * dpitch + x] = out;
+}
+
+// ---- rectification inside the submission (amdAprilTagsSetRectification) -----------------------------------------------------------------
+// One descriptor per batch slot, written by the host for every submission and uploaded by k_prologue beside the FrameDescs: the
+// caller's frame (mono8 or interleaved colour, any base address and pitch), its own size, its camera, and the slot of the handle's
+// rectified plane it becomes.  Everything behind this launch sees a mono8 submission whose images are those slots.
+struct RectDesc {
+  const uint8_t* src;
+  uint8_t* dst;          // 4-byte aligned, dst_pitch a multiple of 4 and >= W0 rounded up to 4: whole dwords are stored
+  uint32_t src_pitch, dst_pitch;
+  uint32_t fmt;          // amdAprilTagsEncoding of `src`
+  int32_t W0, H0;
+  uint32_t pad;
+  RectifyParams model;
+};
+static_assert(sizeof(RectDesc) % 4 == 0, "k_prologue copies RectDesc one word per thread");
+
+// The gray value of source pixel x of a row: mono8 as it stands, colour through the fixed-point BT.601 statement of
+// amdAprilTagsConvertToMono8 (k_to_mono8), so that R = rectify(convert(frame)).
+template <int NCH, int RIDX, int BIDX, class Row>
+__device__ __forceinline__ uint32_t rect_gray(Row row, int x) {
+  if (NCH == 1) return row[x];
+  const Row p = row + (size_t)x * NCH;
+  const uint32_t r = p[RIDX], g = p[1], b = p[BIDX];
+  return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
+}
+
+#define RF_PX 4     // adjacent output pixels of a thread per row: one dword store
+#define RF_ROWS 4   // rows of a thread: the column terms (one division each) serve all of them
+#define RF_BW (64 * RF_PX)
+#define RF_BH (4 * RF_ROWS)
+
+// A block of 256 threads covers RF_BW x RF_BH output pixels of frame blockIdx.z: a wave is 256 pixels wide, a thread RF_PX
+// columns by RF_ROWS rows.  The taps are gathered through the cache (neighbouring lanes read neighbouring source bytes).
+template <int NCH, int RIDX, int BIDX>
+__device__ __forceinline__ void rectify_frame_tile(const RectDesc& d) {
+  const int w = d.W0, h = d.H0;
+  const int x4 = (int)blockIdx.x * RF_BW + (int)(threadIdx.x & 63) * RF_PX;
+  const int ya = (int)blockIdx.y * RF_BH + (int)(threadIdx.x >> 6) * RF_ROWS;
+  if (x4 >= w || ya >= h) return;
+  const RectifyParams& R = d.model;
+  // (the descriptor's pointers are device memory: said so, the compiler addresses them as global, not flat)
+  typedef __attribute__((address_space(1))) const uint8_t* GlobalSrc;
+  typedef __attribute__((address_space(1))) uint32_t* GlobalDst;
+  const GlobalSrc src = (GlobalSrc)d.src;
+  RectCol col[RF_PX];
+#pragma unroll
+  for (int k = 0; k < RF_PX; k++) col[k] = rect_col(x4 + k, R);   // (columns at or beyond w: computed, never sampled)
+#pragma unroll
+  for (int j = 0; j < RF_ROWS; j++) {
+    const int y = ya + j;
+    if (y >= h) break;
+    const RectRow row = rect_row(y, R);
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < RF_PX; k++) {
+      RectTaps t;
+      if (x4 + k < w && rect_taps(col[k], row, R, w, h, t)) {
+        const GlobalSrc r0 = src + (size_t)t.y0 * d.src_pitch, r1 = src + (size_t)t.y1 * d.src_pitch;
+        const uint32_t g = rect_blend(rect_gray<NCH, RIDX, BIDX>(r0, t.x0), rect_gray<NCH, RIDX, BIDX>(r0, t.x1),
+                                      rect_gray<NCH, RIDX, BIDX>(r1, t.x0), rect_gray<NCH, RIDX, BIDX>(r1, t.x1), t);
+        word |= g << (8 * k);
+      }
+    }
+    *(GlobalDst)(d.dst + (size_t)y * d.dst_pitch + x4) = word;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_rectify_frames(const RectDesc* __restrict__ descs) {
+  const RectDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x * RF_BW >= d.W0 || (int)blockIdx.y * RF_BH >= d.H0) return;   // blocks beyond this frame's extent
+  switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
+    case 0: rectify_frame_tile<1, 0, 0>(d); break;
+    case 1: rectify_frame_tile<3, 0, 2>(d); break;
+    case 2: rectify_frame_tile<3, 2, 0>(d); break;
+    case 3: rectify_frame_tile<4, 0, 2>(d); break;
+    default: rectify_frame_tile<4, 2, 0>(d); break;
+  }
 }

@@ -44,6 +44,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsStreamDestroy) stream_destroy = nullptr;
   decltype(&amdAprilTagsSetQuadSigma) set_quad_sigma = nullptr;
   decltype(&amdAprilTagsSetPerFrameSizes) set_per_frame_sizes = nullptr;
+  decltype(&amdAprilTagsSetRectification) set_rectification = nullptr;
 };
 
 DetectorApi& api() {
@@ -80,6 +81,7 @@ DetectorApi& api() {
   BIND(stream_destroy, "amdAprilTagsStreamDestroy")
   BIND(set_quad_sigma, "amdAprilTagsSetQuadSigma")
   BIND(set_per_frame_sizes, "amdAprilTagsSetPerFrameSizes")
+  BIND(set_rectification, "amdAprilTagsSetRectification")
 #undef BIND
   return a;
 }
@@ -94,6 +96,18 @@ void apply_quad_sigma(amdAprilTagsHandle detector, double quad_sigma) {
   const int error = api().set_quad_sigma(detector, static_cast<float>(quad_sigma));
   if (error != 0)
     throw std::runtime_error("'quad_sigma' " + std::to_string(quad_sigma) + " refused (error code " + std::to_string(error) + ")");
+}
+
+amdAprilTagsCameraModel_t to_abi(const CameraModel& m) {
+  amdAprilTagsCameraModel_t o;
+  for (int i = 0; i < 9; i++) { o.K[i] = m.k[i]; o.Knew[i] = m.knew[i]; }
+  for (int i = 0; i < 5; i++) o.D[i] = m.d[i];
+  return o;
+}
+
+// The camera matrix the pose is computed with: Knew of the stream's model with NodeOptions::rectify, K otherwise.
+std::array<double, 9> pose_camera(const NodeOptions& opt, const CameraInfo& info) {
+  return opt.rectify ? RectificationModel(info).knew : info.k;
 }
 
 int bytes_per_pixel(const std::string& enc) {
@@ -219,6 +233,24 @@ int validate_family(const NodeOptions& options, bool* cuapriltags_mode) {
 
 }  // namespace
 
+CameraModel RectificationModel(const CameraInfo& info) {
+  if (!info.distortion_model.empty() && info.distortion_model != "plumb_bob")
+    throw std::runtime_error("'rectify' supports the distortion model 'plumb_bob' only, not '" + info.distortion_model + "'");
+  if (info.d.size() > 5)
+    throw std::runtime_error("'rectify': 'plumb_bob' has five coefficients (k1, k2, p1, p2, k3), camera_info carries " +
+                             std::to_string(info.d.size()));
+  CameraModel m;
+  m.k = info.k;
+  for (size_t i = 0; i < info.d.size(); i++) m.d[i] = info.d[i];
+  if (info.p[0] != 0.0) {
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) m.knew[r * 3 + c] = info.p[r * 4 + c];
+  } else {
+    m.knew = info.k;
+  }
+  return m;
+}
+
 struct AprilTagNode::Impl {
   NodeOptions opt;
   DetectionsCallback on_detections;
@@ -245,12 +277,13 @@ struct AprilTagNode::Impl {
     cfg.decimate = opt.decimate;
     cfg.num_families = 1;
     cfg.families[0] = static_cast<amdAprilTagsFamily>(family_enum);
-    cfg.intrinsics.fx = static_cast<float>(info.k[0]);
-    cfg.intrinsics.fy = static_cast<float>(info.k[4]);
-    cfg.intrinsics.cx = static_cast<float>(info.k[2]);
-    cfg.intrinsics.cy = static_cast<float>(info.k[5]);
+    const std::array<double, 9> k = pose_camera(opt, info);   // (rectify: Knew; throws on a model it cannot rectify)
+    cfg.intrinsics.fx = static_cast<float>(k[0]);
+    cfg.intrinsics.fy = static_cast<float>(k[4]);
+    cfg.intrinsics.cx = static_cast<float>(k[2]);
+    cfg.intrinsics.cy = static_cast<float>(k[5]);
     // the VPI path also passes the skew K[1] (src/apriltag_node.cpp:215-225); cuAprilTags has no such field
-    cfg.skew = cuapriltags_mode ? 0.0f : static_cast<float>(info.k[1]);
+    cfg.skew = cuapriltags_mode ? 0.0f : static_cast<float>(k[1]);
     cfg.tag_size = static_cast<float>(opt.size);
     cfg.max_batch = 1;
     const int error = api().create_ex(&detector, &cfg);
@@ -259,6 +292,11 @@ struct AprilTagNode::Impl {
       throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
     }
     apply_quad_sigma(detector, opt.quad_sigma);
+    if (opt.rectify) {
+      const amdAprilTagsCameraModel_t model = to_abi(RectificationModel(info));
+      const int rerr = api().set_rectification(detector, 1, &model);
+      if (rerr != 0) throw std::runtime_error("'rectify': camera model refused (error code " + std::to_string(rerr) + ")");
+    }
     width = info.width;
     height = info.height;
     if (!stream && api().stream_create(&stream) != 0) throw std::runtime_error("stream creation failed");
@@ -374,7 +412,8 @@ struct AprilTagMultiCameraNode::Impl {
   size_t pitch = 0, slot_bytes = 0;
   void* d_input = nullptr;         // staging for host / colour frames
   size_t d_input_bytes = 0;
-  struct Slot { bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; };
+  // k: the camera the pose is computed with (NodeOptions::rectify: Knew of `model`, the stream's camera model)
+  struct Slot { bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; CameraModel model; };
   std::vector<Slot> slots;
 
 
@@ -390,12 +429,13 @@ struct AprilTagMultiCameraNode::Impl {
     cfg.decimate = opt.decimate;
     cfg.num_families = 1;
     cfg.families[0] = static_cast<amdAprilTagsFamily>(family_enum);
-    cfg.intrinsics.fx = static_cast<float>(info.k[0]);
-    cfg.intrinsics.fy = static_cast<float>(info.k[4]);
-    cfg.intrinsics.cx = static_cast<float>(info.k[2]);
-    cfg.intrinsics.cy = static_cast<float>(info.k[5]);
+    const std::array<double, 9> k = pose_camera(opt, info);
+    cfg.intrinsics.fx = static_cast<float>(k[0]);
+    cfg.intrinsics.fy = static_cast<float>(k[4]);
+    cfg.intrinsics.cx = static_cast<float>(k[2]);
+    cfg.intrinsics.cy = static_cast<float>(k[5]);
     // (VPI mode passes every camera's own skew K[1], src/apriltag_node.cpp:215-225: set per frame at every flush)
-    cfg.skew = cuapriltags_mode ? 0.0f : static_cast<float>(info.k[1]);
+    cfg.skew = cuapriltags_mode ? 0.0f : static_cast<float>(k[1]);
     cfg.tag_size = static_cast<float>(opt.size);
     cfg.max_batch = S;
     const int error = api().create_ex(&detector, &cfg);
@@ -481,6 +521,8 @@ bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& 
   if (stream >= impl_->S) throw std::runtime_error("stream index out of range");
   if (image.header.stamp.sec != camera_info.header.stamp.sec || image.header.stamp.nanosec != camera_info.header.stamp.nanosec)
     return false;  // ExactTime synchroniser would not fire
+  CameraModel model;
+  if (impl_->opt.rectify) model = RectificationModel(camera_info);   // (throws before anything is staged)
   if (!impl_->initialized) impl_->Initialize(camera_info);
   Impl::Slot& sl = impl_->slots[stream];
   // the slot's device image is about to be overwritten: a frame staged earlier and not yet submitted is gone either way,
@@ -489,7 +531,8 @@ bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& 
   if (!impl_->Stage(stream, image, camera_info)) return false;
   sl.pending = true;
   sl.info_header = camera_info.header;
-  sl.k = camera_info.k;
+  sl.k = impl_->opt.rectify ? model.knew : camera_info.k;
+  sl.model = model;
   if (impl_->auto_flush) {
     bool all = true;
     for (const auto& x : impl_->slots) all &= x.pending;
@@ -521,6 +564,16 @@ uint32_t AprilTagMultiCameraNode::Flush() {
     for (uint32_t i = 0; i < n; i++) skews[i] = static_cast<float>(I.slots[who[i]].k[1]);
     if (api().set_frame_skews(I.detector, n, skews.data()) != 0) {   // (a round whose skews were refused must not run with stale ones)
       std::fprintf(stderr, "[apriltag_node] per-stream skews refused: round dropped\n");
+      for (uint32_t s : who) I.slots[s].pending = false;
+      return 0;
+    }
+  }
+  if (I.opt.rectify) {   // the models of the streams of this round, in slot order (host state of the handle: no device work)
+    std::vector<amdAprilTagsCameraModel_t> models(n);
+    for (uint32_t i = 0; i < n; i++) models[i] = to_abi(I.slots[who[i]].model);
+    const int rerr = api().set_rectification(I.detector, n, models.data());
+    if (rerr != 0) {   // (a round whose models were refused must not run with stale ones)
+      std::fprintf(stderr, "[apriltag_node] per-stream camera models refused (error code %d): round dropped\n", rerr);
       for (uint32_t s : who) I.slots[s].pending = false;
       return 0;
     }
@@ -573,15 +626,42 @@ struct NodeShellDetection {
 
 extern "C" {
 
-// Every NodeOptions field the flat view carries (node.py): the create calls below are this one with quad_sigma 0.
-NodeShellHarness* node_shell_create_ex(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
-                                       int decimate, int strict_cuapriltags_encodings, double quad_sigma, char* err, size_t err_len) {
+// sensor_msgs/CameraInfo's D, distortion_model and P through the flat view (null / 0: left empty)
+static void fill_camera_info_extras(CameraInfo* info, const double* d, int nd, const char* distortion_model, const double* p12) {
+  if (d && nd > 0) info->d.assign(d, d + nd);
+  if (distortion_model) info->distortion_model = distortion_model;
+  if (p12) for (int i = 0; i < 12; i++) info->p[i] = p12[i];
+}
+
+// RectificationModel of a CameraInfo with these fields: out23 = K[9], D[5], Knew[9].  0, or -2 with the exception's text in err.
+// (host only: loads no detector library)
+int node_shell_camera_model(const double* k9, const double* d, int nd, const char* distortion_model, const double* p12, double* out23,
+                            char* err, size_t err_len) {
+  try {
+    CameraInfo info;
+    for (int i = 0; i < 9; i++) info.k[i] = k9[i];
+    fill_camera_info_extras(&info, d, nd, distortion_model, p12);
+    const amd::isaac_ros::apriltag::CameraModel m = amd::isaac_ros::apriltag::RectificationModel(info);
+    for (int i = 0; i < 9; i++) { out23[i] = m.k[i]; out23[14 + i] = m.knew[i]; }
+    for (int i = 0; i < 5; i++) out23[9 + i] = m.d[i];
+    return 0;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return -2;
+  }
+}
+
+// Every NodeOptions field the flat view carries (node.py): the create calls below are this one with quad_sigma 0 and rectify off.
+NodeShellHarness* node_shell_create_opts(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                         int decimate, int strict_cuapriltags_encodings, double quad_sigma, int rectify, char* err,
+                                         size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     o.strict_cuapriltags_encodings = strict_cuapriltags_encodings != 0;
     o.quad_sigma = quad_sigma;
+    o.rectify = rectify != 0;
     auto* h = new NodeShellHarness();
     h->node.reset(new AprilTagNode(o));
     h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
@@ -591,6 +671,12 @@ NodeShellHarness* node_shell_create_ex(int max_tags, double size, int tile_size,
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+
+NodeShellHarness* node_shell_create_ex(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                       int decimate, int strict_cuapriltags_encodings, double quad_sigma, char* err, size_t err_len) {
+  return node_shell_create_opts(max_tags, size, tile_size, tag_family, backends, decimate, strict_cuapriltags_encodings, quad_sigma, 0,
+                                err, err_len);
 }
 
 // Returns nullptr and fills err on a constructor exception (mirrors test/apriltag_node_test.cpp).
@@ -609,10 +695,12 @@ void node_shell_destroy(NodeShellHarness* h) { delete h; }
 
 // Feeds one image + camera_info pair.  Returns the number of detections published, -1 if the stamps
 // differ (no callback), -2 on an exception (message in err).
-int node_shell_on_frame(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
-                        uint32_t height, uint32_t step, const double* k9, const char* frame_id, int32_t sec, uint32_t nanosec,
-                        int32_t info_sec, uint32_t info_nanosec, NodeShellDetection* out, int max_out, char* out_frame_id,
-                        size_t frame_id_len, char* err, size_t err_len) {
+// (d, nd, distortion_model, p12: the CameraInfo fields NodeOptions::rectify reads)
+int node_shell_on_frame_info(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
+                             uint32_t height, uint32_t step, const double* k9, const double* d, int nd, const char* distortion_model,
+                             const double* p12, const char* frame_id, int32_t sec, uint32_t nanosec, int32_t info_sec,
+                             uint32_t info_nanosec, NodeShellDetection* out, int max_out, char* out_frame_id, size_t frame_id_len,
+                             char* err, size_t err_len) {
   try {
     Image img;
     img.header.frame_id = "image_frame"; img.header.stamp.sec = sec; img.header.stamp.nanosec = nanosec;
@@ -621,6 +709,7 @@ int node_shell_on_frame(NodeShellHarness* h, const uint8_t* data, int is_device,
     info.header.frame_id = frame_id; info.header.stamp.sec = info_sec; info.header.stamp.nanosec = info_nanosec;
     info.width = width; info.height = height;
     for (int i = 0; i < 9; i++) info.k[i] = k9[i];
+    fill_camera_info_extras(&info, d, nd, distortion_model, p12);
     const int before = h->publishes;
     if (!h->node->CameraImageCallback(img, info)) return -1;
     if (h->publishes == before) return 0;  // frame dropped
@@ -647,6 +736,14 @@ int node_shell_on_frame(NodeShellHarness* h, const uint8_t* data, int is_device,
   }
 }
 
+int node_shell_on_frame(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
+                        uint32_t height, uint32_t step, const double* k9, const char* frame_id, int32_t sec, uint32_t nanosec,
+                        int32_t info_sec, uint32_t info_nanosec, NodeShellDetection* out, int max_out, char* out_frame_id,
+                        size_t frame_id_len, char* err, size_t err_len) {
+  return node_shell_on_frame_info(h, data, is_device, encoding, width, height, step, k9, nullptr, 0, nullptr, nullptr, frame_id, sec,
+                                  nanosec, info_sec, info_nanosec, out, max_out, out_frame_id, frame_id_len, err, err_len);
+}
+
 // ---- the multi-camera node through the same flat view ----
 struct MultiShellHarness {
   std::unique_ptr<amd::isaac_ros::apriltag::AprilTagMultiCameraNode> node;
@@ -655,16 +752,17 @@ struct MultiShellHarness {
   std::vector<int> publishes;
 };
 
-// max_width, max_height: NodeOptions of the same names (0, 0: one size, the first frame's)
-MultiShellHarness* node_shell_multi_create_sized(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
-                                                 const char* backends, int decimate, int auto_flush, double quad_sigma,
-                                                 uint32_t max_width, uint32_t max_height, char* err, size_t err_len) {
+// max_width, max_height, rectify: NodeOptions of the same names (0, 0: one size, the first frame's)
+MultiShellHarness* node_shell_multi_create_opts(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                const char* backends, int decimate, int auto_flush, double quad_sigma,
+                                                uint32_t max_width, uint32_t max_height, int rectify, char* err, size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     o.quad_sigma = quad_sigma;
     o.max_width = max_width; o.max_height = max_height;
+    o.rectify = rectify != 0;
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
     h->node->set_auto_flush(auto_flush != 0);
@@ -676,6 +774,13 @@ MultiShellHarness* node_shell_multi_create_sized(int num_streams, int max_tags, 
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+
+MultiShellHarness* node_shell_multi_create_sized(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                 const char* backends, int decimate, int auto_flush, double quad_sigma,
+                                                 uint32_t max_width, uint32_t max_height, char* err, size_t err_len) {
+  return node_shell_multi_create_opts(num_streams, max_tags, size, tile_size, tag_family, backends, decimate, auto_flush, quad_sigma,
+                                      max_width, max_height, 0, err, err_len);
 }
 
 MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
@@ -693,9 +798,10 @@ MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double
 void node_shell_multi_destroy(MultiShellHarness* h) { delete h; }
 
 // 1 staged, 0 not (stamps differ / dropped), -2 exception
-int node_shell_multi_on_frame(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
-                              uint32_t height, uint32_t step, const double* k9, const char* frame_id, int32_t sec, uint32_t nanosec,
-                              int32_t info_sec, uint32_t info_nanosec, char* err, size_t err_len) {
+int node_shell_multi_on_frame_info(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding,
+                                   uint32_t width, uint32_t height, uint32_t step, const double* k9, const double* d, int nd,
+                                   const char* distortion_model, const double* p12, const char* frame_id, int32_t sec, uint32_t nanosec,
+                                   int32_t info_sec, uint32_t info_nanosec, char* err, size_t err_len) {
   try {
     Image img;
     img.header.frame_id = "image_frame"; img.header.stamp.sec = sec; img.header.stamp.nanosec = nanosec;
@@ -704,11 +810,19 @@ int node_shell_multi_on_frame(MultiShellHarness* h, int stream, const uint8_t* d
     info.header.frame_id = frame_id; info.header.stamp.sec = info_sec; info.header.stamp.nanosec = info_nanosec;
     info.width = width; info.height = height;
     for (int i = 0; i < 9; i++) info.k[i] = k9[i];
+    fill_camera_info_extras(&info, d, nd, distortion_model, p12);
     return h->node->CameraImageCallback(static_cast<uint32_t>(stream), img, info) ? 1 : 0;
   } catch (const std::exception& e) {
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return -2;
   }
+}
+
+int node_shell_multi_on_frame(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
+                              uint32_t height, uint32_t step, const double* k9, const char* frame_id, int32_t sec, uint32_t nanosec,
+                              int32_t info_sec, uint32_t info_nanosec, char* err, size_t err_len) {
+  return node_shell_multi_on_frame_info(h, stream, data, is_device, encoding, width, height, step, k9, nullptr, 0, nullptr, nullptr,
+                                        frame_id, sec, nanosec, info_sec, info_nanosec, err, err_len);
 }
 
 int node_shell_multi_flush(MultiShellHarness* h) { return static_cast<int>(h->node->Flush()); }

@@ -28,11 +28,15 @@
 //                               positive moments of a point set -- the cluster with some points counted double -- so no window has a
 //                               weight of zero or below, nothing downstream meets a NaN or an infinity it does not meet in the product
 //                               build, and the wrong build can only give wrong quads.)
-//                           (4 .. 8 change values only: no address, index bound, launch size or loop count)
+//                           9 = the rectification statement (kernels_frontend.h: rect_taps) truncates the fixed-point source position,
+//                               (int)(u * 32.0) without the + 0.5: taps and weights one 1/32 step low wherever the fraction is a half or more
+//                           10 = amdAprilTagsSetRectification: every frame of a submission takes cams[0] instead of cams[i % ncams]
+//                           (4 .. 10 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
-//                           tests/test_fit_classes_gpu.py::test_fit_class_tests_fail_on_the_wrong_builds for 7 and 8)
+//                           tests/test_fit_classes_gpu.py::test_fit_class_tests_fail_on_the_wrong_builds for 7 and 8,
+//                           tests/test_rectify_submission_gpu.py::test_the_rectify_tests_fail_on_the_wrong_builds for 9 and 10)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -62,6 +66,18 @@
 #define QS_FAR_EDGE_H(KH, h) (KH)
 #else
 #define QS_FAR_EDGE_H(KH, h) (h)
+#endif
+
+// ---- rectification: the source position in 1/32 pixel, and the camera model of batch slot i ------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 9
+#define RECT_FIXED(u) ((int)((u) * 32.0))
+#else
+#define RECT_FIXED(u) ((int)((u) * 32.0 + 0.5))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 10
+#define RECT_MODEL_OF_SLOT(i, ncams) ((void)(i), (void)(ncams), 0u)
+#else
+#define RECT_MODEL_OF_SLOT(i, ncams) ((i) % (ncams))
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------

@@ -50,7 +50,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
-                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, **caps):
+                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -83,6 +83,8 @@ class AprilTagDetector:
                 self.set_quad_sigma(quad_sigma)
             if per_frame_sizes:
                 self.set_per_frame_sizes(True)
+            if rectification:
+                self.set_rectification(rectification)
         except Exception:
             self.close()
             raise
@@ -96,6 +98,13 @@ class AprilTagDetector:
         the largest frame); tensors are taken at their shape, (dev_ptr, pitch, width, height) tuples as they say."""
         capi._check("amdAprilTagsSetPerFrameSizes", self._L.amdAprilTagsSetPerFrameSizes(self._h, 1 if enable else 0))
         self.per_frame_sizes = bool(enable)
+
+    def set_rectification(self, models):
+        """amdAprilTagsSetRectification: models is a list of (K, D, Knew) -- frame i of every following submission is undistorted with
+        models[i % len(models)] inside the submission and detected there; None or [] turns it off.  The pose intrinsics stay the
+        caller's: pass Knew's fx, fy, cx, cy."""
+        arr = capi.camera_models(models)
+        capi._check("amdAprilTagsSetRectification", self._L.amdAprilTagsSetRectification(self._h, len(arr) if arr is not None else 0, arr))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -260,7 +269,7 @@ class AprilTagDetector:
         capi._check("amdAprilTagsDebugCopy",
                     self._L.amdAprilTagsDebugCopy(self._h, frame, what, buf.ctypes.data, buf.size, C.byref(nbytes)))
         buf = buf[:nbytes.value]
-        if what in (capi.DBG_GRAY, capi.DBG_THRESH):
+        if what in (capi.DBG_GRAY, capi.DBG_THRESH, capi.DBG_RECTIFIED):
             return buf
         if what in (capi.DBG_LABEL, capi.DBG_CSIZE, capi.DBG_POINTS, capi.DBG_COUNTS):
             return buf.view(np.uint32)

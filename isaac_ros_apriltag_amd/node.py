@@ -32,7 +32,26 @@ def lib():
         L.node_shell_create_ex.restype = C.c_void_p
         L.node_shell_create_ex.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double,
                                            C.c_char_p, C.c_size_t]
+        L.node_shell_create_opts.restype = C.c_void_p
+        L.node_shell_create_opts.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int,
+                                             C.c_char_p, C.c_size_t]
+        L.node_shell_camera_model.restype = C.c_int
+        L.node_shell_camera_model.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
         L.node_shell_destroy.argtypes = [C.c_void_p]
+        L.node_shell_on_frame_info.restype = C.c_int
+        L.node_shell_on_frame_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.POINTER(C.c_double),
+                                               C.c_char_p, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32,
+                                               C.POINTER(ShellDetection), C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_opts.restype = C.c_void_p
+        L.node_shell_multi_create_opts.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                   C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_on_frame_info.restype = C.c_int
+        L.node_shell_multi_on_frame_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32,
+                                                     C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p,
+                                                     C.POINTER(C.c_double), C.c_char_p, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32,
+                                                     C.c_char_p, C.c_size_t]
         L.node_shell_on_frame.restype = C.c_int
         L.node_shell_on_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.c_double), C.c_char_p, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32,
@@ -71,18 +90,39 @@ def _unpack(out, n):
     return dets
 
 
+def _info_extras(D, distortion_model, P12):
+    """sensor_msgs/CameraInfo's D, distortion_model and P as the flat view takes them (None: left empty)."""
+    d = (C.c_double * len(D))(*[float(v) for v in D]) if D is not None and len(D) else None
+    p = (C.c_double * 12)(*[float(v) for v in P12]) if P12 is not None else None
+    return d, (len(D) if d is not None else 0), (distortion_model.encode() if distortion_model is not None else None), p
+
+
+def camera_model(K9, D=None, distortion_model=None, P12=None):
+    """RectificationModel (include/apriltag_node_shell.hpp) of a CameraInfo with these fields: (K[9], D[5], Knew[9]) as lists.
+    Raises RuntimeError with the shell's text for a model NodeOptions::rectify does not take.  Host only."""
+    k = (C.c_double * 9)(*[float(v) for v in K9])
+    d, nd, m, p = _info_extras(D, distortion_model, P12)
+    out = (C.c_double * 23)()
+    err = C.create_string_buffer(1024)
+    if lib().node_shell_camera_model(k, d, nd, m, p, out, err, 1024) != 0:
+        raise RuntimeError(err.value.decode())
+    v = list(out)
+    return v[:9], v[9:14], v[14:]
+
+
 class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0):
+                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
-        sizes); 0: one size, the first frame's, and frames of another size are dropped."""
+        sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
+        undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12)."""
         err = C.create_string_buffer(1024)
         self._L = lib()
-        self._h = self._L.node_shell_multi_create_sized(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
-                                                        decimate, 1 if auto_flush else 0, float(quad_sigma), int(max_width),
-                                                        int(max_height), err, 1024)
+        self._h = self._L.node_shell_multi_create_opts(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
+                                                       decimate, 1 if auto_flush else 0, float(quad_sigma), int(max_width),
+                                                       int(max_height), 1 if rectify else 0, err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags, self.num_streams = max_tags, num_streams
@@ -98,12 +138,15 @@ class AprilTagMultiCameraNode:
         except Exception:
             pass
 
-    def on_frame(self, stream, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0), info_stamp=None):
+    def on_frame(self, stream, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0), info_stamp=None,
+                 D=None, distortion_model=None, P12=None):
         info_stamp = stamp if info_stamp is None else info_stamp
         err = C.create_string_buffer(1024)
         k = (C.c_double * 9)(*[float(v) for v in K9])
-        rc = self._L.node_shell_multi_on_frame(self._h, stream, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step, k,
-                                               frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1], err, 1024)
+        d, nd, m, p = _info_extras(D, distortion_model, P12)
+        rc = self._L.node_shell_multi_on_frame_info(self._h, stream, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step,
+                                                    k, d, nd, m, p, frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1],
+                                                    err, 1024)
         if rc == -2:
             raise RuntimeError(err.value.decode())
         return rc == 1
@@ -127,12 +170,15 @@ class AprilTagNode:
     """Parameters and defaults of the reference node (apriltag_node.cpp:564-568)."""
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 strict_cuapriltags_encodings=False, quad_sigma=0.0):
-        """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma)."""
+                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False):
+        """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
+        (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
+        (on_frame: D, distortion_model, P12), and the pose is computed with Knew."""
         err = C.create_string_buffer(1024)
         self._L = lib()
-        self._h = self._L.node_shell_create_ex(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
-                                               1 if strict_cuapriltags_encodings else 0, float(quad_sigma), err, 1024)
+        self._h = self._L.node_shell_create_opts(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                 1 if strict_cuapriltags_encodings else 0, float(quad_sigma), 1 if rectify else 0,
+                                                 err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags = max_tags
@@ -149,15 +195,16 @@ class AprilTagNode:
             pass
 
     def on_frame(self, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0),
-                 info_stamp=None):
+                 info_stamp=None, D=None, distortion_model=None, P12=None):
         info_stamp = stamp if info_stamp is None else info_stamp
         out = (ShellDetection * self.max_tags)()
         fid = C.create_string_buffer(128)
         err = C.create_string_buffer(1024)
         k = (C.c_double * 9)(*[float(v) for v in K9])
-        n = self._L.node_shell_on_frame(self._h, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step, k,
-                                        frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1], out, self.max_tags,
-                                        fid, 128, err, 1024)
+        d, nd, m, p = _info_extras(D, distortion_model, P12)
+        n = self._L.node_shell_on_frame_info(self._h, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step, k,
+                                             d, nd, m, p, frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1], out,
+                                             self.max_tags, fid, 128, err, 1024)
         if n == -2:
             raise RuntimeError(err.value.decode())
         if n < 0:

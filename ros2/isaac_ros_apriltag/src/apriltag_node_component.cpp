@@ -48,6 +48,9 @@ public:
     opt.backends = declare_parameter<std::string>("backends", "CUDA");  // name or comma list; exactly "CUDA" = cuAprilTags mode
     opt.decimate = static_cast<uint32_t>(declare_parameter<int>("decimate", 1));
     opt.quad_sigma = declare_parameter<double>("quad_sigma", 0.0);   // AprilRobotics quad_sigma (apriltag_ros `blur` / `sigma`)
+    // the image topic is the camera's distorted image: undistorted inside the detector's submission with camera_info's plumb_bob model
+    // (K, D; the rectified camera is the left 3x3 of P), in place of a RectifyNode in front of this one
+    opt.rectify = declare_parameter<bool>("rectify", false);
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);
@@ -124,6 +127,9 @@ private:
     info.width = camera_info->width;
     info.height = camera_info->height;
     for (int i = 0; i < 9; i++) {info.k[i] = camera_info->k[i];}
+    info.d = camera_info->d;
+    info.distortion_model = camera_info->distortion_model;
+    for (int i = 0; i < 12; i++) {info.p[i] = camera_info->p[i];}
     last_info_header_ = camera_info->header;  // output headers = camera_info header (reference :501,:534)
     impl_->CameraImageCallback(img, info);
   }
