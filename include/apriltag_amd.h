@@ -313,6 +313,32 @@ typedef struct { double K[9]; double D[5]; double Knew[9]; } amdAprilTagsCameraM
  * the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the models does not. */
 int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModel_t* cams);
 
+/* Resize inside the submission, fused with the rectification where that is on: the reference's camera -> rectify -> resize -> AprilTag
+ * graph as one submission. */
+typedef struct { uint32_t width, height; } amdAprilTagsSize_t;
+/* nsizes = 0 turns the resize off (the default: nothing changes).  Otherwise frame i of every following submission, whatever its own
+ * size sw x sh (images[i].width / height: 1 .. 16384 each, larger or smaller than the handle's; beyond that AMDAT_SIZE_MISMATCH), is
+ * first resized to sizes[i % nsizes] = dw x dh into a plane the handle owns, and detected there: its records are exactly those of the
+ * same handle given the resized frame S as a mono8 frame, at every decimate, tile_size and quad_sigma.  S is what
+ * amdAprilTagsResizeMono8 computes from the frame's gray plane G at the source size (oracle: ato_resize_mono8):
+ * G = convert(frame) -- mono8 as it stands, colour through the BT.601 weights of amdAprilTagsConvertToMono8 -- or, with
+ * amdAprilTagsSetRectification on, G = rectify(convert(frame)) with cams[i % ncams] and w = sw, h = sh.  With sw == dw and sh == dh
+ * S == G.  One launch per submission covers all frames, writes the same plane rectification uses (the footprint grows by the
+ * descriptors only), never writes the caller's buffers, and with rectification on never forms G in memory.
+ * The TARGET size takes the place of the image size in every size rule: equal to the handle's size, or with
+ * amdAprilTagsSetPerFrameSizes on any admissible size up to it; a violation is AMDAT_SIZE_MISMATCH at submit, with nothing enqueued.
+ * The pitch rules apply to the source width.
+ * The library does NOT touch the pose intrinsics.  The resized image's camera follows image_proc's convention: fx * dw / sw,
+ * cx * dw / sw, fy * dh / sh, cy * dh / sh, and the skew * dw / sw; with rectification the same scaling applies to Knew.
+ * The sizes are host state of the handle and travel with each submission's descriptors: no device synchronisation.  Applies to
+ * Detect[Color], DetectBatch[Color][Ex], SubmitBatch[Color] / WaitBatch[Ex], on both launch sets; amdAprilTagsThresholdOnly[Color]
+ * never resizes.
+ * Callable whenever no submission is in flight.  AMDAT_INVALID_ARGUMENT: null handle, null sizes with nsizes > 0, nsizes > max_batch,
+ * a zero dimension, a dimension above the handle's, a submission in flight; AMDAT_OUT_OF_MEMORY: the plane could not be allocated.  A
+ * refused call leaves the previous setting in force.  Turning the mode on or off retires the handle's captured launch graphs, against
+ * the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the sizes does not. */
+int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdAprilTagsSize_t* sizes);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

@@ -68,8 +68,11 @@ typedef enum {
   AMDAT_DBG_QUADS = 6,     /* {float p[4][2]; i32 reversed_border; u32 pad; u64 key} x nquads */
   AMDAT_DBG_COUNTS = 7,    /* u32[8]: npoints_raw, nclusters, npoints_kept, nquads, ndets, flags, w, h */
   AMDAT_DBG_FQPROF = 8,    /* u64[64]: shader-cycle totals, 8 phases x up to 8 size classes of the quad-fit kernel (profiling on) */
-  AMDAT_DBG_RECTIFIED = 9  /* u8  W0*H0 dense (the frame's INPUT size): its rectified plane of the last submission
-                            * (amdAprilTagsSetRectification); AMDAT_INVALID_ARGUMENT when rectification is off */
+  AMDAT_DBG_RECTIFIED = 9, /* u8  W0*H0 dense (the frame's INPUT size): its rectified plane of the last submission
+                            * (amdAprilTagsSetRectification); AMDAT_INVALID_ARGUMENT when rectification is off -- and when
+                            * amdAprilTagsSetResize is on as well: the resize samples the rectification in place, that plane is never formed */
+  AMDAT_DBG_RESIZED = 10   /* u8  dw*dh dense (the frame's TARGET size): its slot of the last submission (amdAprilTagsSetResize);
+                            * AMDAT_INVALID_ARGUMENT when the last submission did not resize */
 } amdAprilTagsDebugBuffer;
 /* Copies an intermediate buffer of frame `frame` of the last submission to host memory.  w, h: the FRAME's own working size (with
  * amdAprilTagsSetPerFrameSizes on, the size that frame was submitted with; the planes are dense w x h whatever the handle's size).

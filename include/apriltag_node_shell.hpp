@@ -99,6 +99,14 @@ struct NodeOptions {
   // stream's CameraInfo (AprilTagNode: of the first frame's, like K; AprilTagMultiCameraNode: of every staged frame's, set before each
   // flush in slot order), and the pose is computed with Knew -- fx, fy, cx, cy, and its [0][1] as the skew in VPI mode -- in place of K.
   bool rectify = false;
+  // Extension: every frame is resized to resize_width x resize_height INSIDE the detector's submission, behind the rectification where
+  // `rectify` is set (amdAprilTagsSetResize; the reference puts a ResizeNode in front and recommends it for 4K input, README.md:16-29).
+  // Both set: AprilTagNode creates its handle at that size, AprilTagMultiCameraNode at that size too (or at max_width x max_height with
+  // per-frame image sizes where those are set); frames of ANY size (1 .. 16384 a side) are accepted instead of dropped; the resize is set
+  // once; and the pose is computed with the camera of the resized image, image_proc's convention: fx, cx and the skew of K (`rectify`:
+  // of Knew) times resize_width / width, fy and cy times resize_height / height -- of the first frame's CameraInfo for AprilTagNode,
+  // of every staged frame's for AprilTagMultiCameraNode.  0 (the default): off.
+  uint32_t resize_width = 0, resize_height = 0;
 };
 
 class AprilTagNode {

@@ -16,6 +16,7 @@ FAMILY_ENUM = {"tag36h11": 0, "tag25h9": 1, "tag16h5": 2}
 SLOT_TAG36H10, SLOT_CUSTOM0 = 3, 4   # registrable slots: 3 (tag36h10: no built-in table) and 4..8
 (DBG_GRAY, DBG_THRESH, DBG_LABEL, DBG_CSIZE, DBG_CLUSTERS, DBG_POINTS, DBG_QUADS, DBG_COUNTS) = range(8)
 DBG_RECTIFIED = 9   # u8 W0 x H0: the frame's rectified plane (amdAprilTagsSetRectification)
+DBG_RESIZED = 10    # u8 dw x dh: the frame's resized plane (amdAprilTagsSetResize)
 
 STATUS = {0: "AMDAT_SUCCESS", 1: "AMDAT_INVALID_ARGUMENT", 2: "AMDAT_UNSUPPORTED", 3: "AMDAT_HIP_ERROR",
           4: "AMDAT_SIZE_MISMATCH", 5: "AMDAT_OUT_OF_MEMORY", 6: "AMDAT_BATCH_TOO_LARGE"}
@@ -32,6 +33,11 @@ class ImageInput(C.Structure):
 class CameraModel(C.Structure):
     """amdAprilTagsCameraModel_t: row-major 3x3 K and Knew, plumb_bob D = k1, k2, p1, p2, k3."""
     _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 5), ("Knew", C.c_double * 9)]
+
+
+class Size(C.Structure):
+    """amdAprilTagsSize_t."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
 
 class Float2(C.Structure):
@@ -75,7 +81,7 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSubmitBatchColor", "amdAprilTagsThresholdOnlyColor", "amdAprilTagsCopyToDeviceAsync", "amdAprilTagsStreamCreate",
            "amdAprilTagsStreamDestroy", "amdAprilTagsDebugGraphReplay", "amdAprilTagsConfigLayoutVersion",
            "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes",
-           "amdAprilTagsSetRectification"]
+           "amdAprilTagsSetRectification", "amdAprilTagsSetResize"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 ENC_CHANNELS = {"mono8": 1, "rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4}
@@ -151,6 +157,7 @@ def lib():
     L.amdAprilTagsSetQuadSigma.argtypes = [H, C.c_float]
     L.amdAprilTagsSetPerFrameSizes.argtypes = [H, C.c_int]
     L.amdAprilTagsSetRectification.argtypes = [H, C.c_uint32, C.POINTER(CameraModel)]
+    L.amdAprilTagsSetResize.argtypes = [H, C.c_uint32, C.POINTER(Size)]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -226,6 +233,17 @@ def camera_models(models):
             raise ValueError("a camera model is (K[3x3], D[<= 5], Knew[3x3])")
         m.K[:], m.Knew[:] = list(k), list(kn)
         m.D[:] = list(d) + [0.0] * (5 - d.size)
+    return arr
+
+
+def sizes(pairs):
+    """[(width, height)] -> a ctypes array of amdAprilTagsSize_t (None for an empty list)."""
+    pairs = list(pairs or [])
+    if not pairs:
+        return None
+    arr = (Size * len(pairs))()
+    for s, (w, h) in zip(arr, pairs):
+        s.width, s.height = int(w), int(h)
     return arr
 
 

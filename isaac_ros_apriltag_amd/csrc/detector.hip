@@ -256,6 +256,12 @@ struct amdAprilTagsDetector_st {
   DevBuf<RectDesc> d_rdesc;
   std::vector<amdAprilTagsImageInput_t> rect_imgs;      // the plane's slots as the mono8 images of the submission (fill_rect)
   bool last_rectified = false;                          // the last submission rectified (AMDAT_DBG_RECTIFIED)
+  // amdAprilTagsSetResize: frame i of a submission, at any source size, is resized to resize_sizes[i % size] into slot i of the same
+  // plane by k_resize_frames -- through the rectification where that is on, in place of k_rectify_frames -- and detected there
+  std::vector<amdAprilTagsSize_t> resize_sizes;         // empty: off
+  ResizeDesc* h_zdesc = nullptr;                        // pinned, one per batch slot, uploaded by k_prologue
+  DevBuf<ResizeDesc> d_zdesc;
+  bool last_resized = false;                            // the last submission resized (AMDAT_DBG_RESIZED)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -489,6 +495,7 @@ static void free_all(amdAprilTagsDetector_st* D) {
   if (D->h_counters) hipHostFree(D->h_counters);
   if (D->h_out) hipHostFree(D->h_out);
   if (D->h_rdesc) hipHostFree(D->h_rdesc);
+  if (D->h_zdesc) hipHostFree(D->h_zdesc);
   for (auto& e : D->ev) if (e) hipEventDestroy(e);
   if (D->own_stream) hipStreamDestroy(D->own_stream);
   for (auto& a : D->aux_stream) if (a) hipStreamDestroy(a);
@@ -934,6 +941,43 @@ int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, cons
   return AMDAT_SUCCESS;
 }
 
+// What the first call that turns the resize on allocates: the plane rectification uses (d_conv) and the descriptor blocks of
+// k_resize_frames.
+static int ensure_resize_buffers(amdAprilTagsDetector_st* D) {
+  const size_t B = D->cfg.max_batch;
+  if (!D->d_conv) {
+    D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
+    if (!dev_alloc(D, D->d_conv, B * D->conv_pitch * D->cfg.height)) return AMDAT_OUT_OF_MEMORY;
+  }
+  if (!D->d_zdesc && !dev_alloc(D, D->d_zdesc, B * sizeof(ResizeDesc))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->h_zdesc) {
+    if (hipHostMalloc((void**)&D->h_zdesc, B * sizeof(ResizeDesc), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+      D->h_zdesc = nullptr;
+      (void)hipGetLastError();
+      return AMDAT_OUT_OF_MEMORY;
+    }
+    memset(D->h_zdesc, 0, B * sizeof(ResizeDesc));
+  }
+  D->rect_imgs.resize(B);
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdAprilTagsSize_t* sizes) {
+  if (!handle || handle->inflight.active || (nsizes && !sizes) || nsizes > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  for (uint32_t c = 0; c < nsizes; c++)
+    if (sizes[c].width == 0 || sizes[c].height == 0 || sizes[c].width > handle->cfg.width || sizes[c].height > handle->cfg.height)
+      return AMDAT_INVALID_ARGUMENT;
+  const bool on = nsizes > 0;
+  if (on != !handle->resize_sizes.empty()) {
+    DeviceGuard guard(handle->device);
+    if (!guard.ok) return AMDAT_HIP_ERROR;
+    if (on) { const int rc = ensure_resize_buffers(handle); if (rc) return rc; }
+    drop_graphs(handle);   // captured with or without the resize launch; the sizes themselves travel through the descriptors
+  }
+  handle->resize_sizes.assign(sizes, sizes + nsizes);
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
   if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
   if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
@@ -967,17 +1011,27 @@ int amdAprilTagsGetStageMs(amdAprilTagsHandle handle, float* ms) {
   return AMDAT_SUCCESS;
 }
 
-static int check_images(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt = AMDAT_ENC_MONO8) {
+// resizing: the submission resizes (every submitting call with amdAprilTagsSetResize on; ThresholdOnly never).  The size the frame is
+// detected at -- its target size then, its own otherwise -- obeys the size rules; the source size of a resized frame is free.
+static int check_images(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt = AMDAT_ENC_MONO8,
+                        bool resizing = false) {
   if (n == 0 || !images) return AMDAT_INVALID_ARGUMENT;
   if (fmt > AMDAT_ENC_BGRA8) return AMDAT_UNSUPPORTED;
   if (n > D->cfg.max_batch) return AMDAT_BATCH_TOO_LARGE;
+  const uint32_t nsizes = (uint32_t)D->resize_sizes.size();
   for (uint32_t i = 0; i < n; i++) {
     if (!images[i].dev_ptr) return AMDAT_INVALID_ARGUMENT;
+    uint32_t fw = images[i].width, fh = images[i].height;
+    if (resizing) {
+      if (fw < 1 || fw > 16384 || fh < 1 || fh > 16384) return AMDAT_SIZE_MISMATCH;
+      const amdAprilTagsSize_t& t = D->resize_sizes[RESIZE_SIZE_OF_SLOT(i, nsizes)];   // (tools_hooks.h: i % nsizes)
+      fw = t.width; fh = t.height;
+    }
     if (!D->per_frame_sizes) {
-      if (images[i].width != D->cfg.width || images[i].height != D->cfg.height) return AMDAT_SIZE_MISMATCH;
+      if (fw != D->cfg.width || fh != D->cfg.height) return AMDAT_SIZE_MISMATCH;
     } else {   // any size up to the handle's whose working image has a full threshold tile in both directions
-      if (images[i].width < 1 || images[i].width > D->cfg.width || images[i].height < 1 || images[i].height > D->cfg.height) return AMDAT_SIZE_MISMATCH;
-      const uint32_t w = 1 + (images[i].width - 1) / D->cfg.decimate, h = 1 + (images[i].height - 1) / D->cfg.decimate;
+      if (fw < 1 || fw > D->cfg.width || fh < 1 || fh > D->cfg.height) return AMDAT_SIZE_MISMATCH;
+      const uint32_t w = 1 + (fw - 1) / D->cfg.decimate, h = 1 + (fh - 1) / D->cfg.decimate;
       if (w < D->cfg.tile_size || h < D->cfg.tile_size) return AMDAT_SIZE_MISMATCH;
     }
     if (images[i].pitch < (size_t)images[i].width * enc_channels(fmt)) return AMDAT_INVALID_ARGUMENT;
@@ -1067,6 +1121,32 @@ static const amdAprilTagsImageInput_t* fill_rect(amdAprilTagsDetector_st* D, uin
     r.model = {m.K[0], m.K[4], m.K[2], m.K[5], m.D[0], m.D[1], m.D[2], m.D[3], m.D[4], m.Knew[0], m.Knew[4], m.Knew[2], m.Knew[5]};
     D->rect_imgs[i] = images[i];
     D->rect_imgs[i].dev_ptr = r.dst;
+    D->rect_imgs[i].pitch = D->conv_pitch;
+  }
+  return D->rect_imgs.data();
+}
+
+// Resize on: the descriptors of k_resize_frames for the caller's frames (encoding fmt; with their camera models where rectification
+// is on too), and the plane's slots at the target sizes as the mono8 images the rest of the submission is filled from.
+static const amdAprilTagsImageInput_t* fill_resize(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
+  const uint32_t nsizes = (uint32_t)D->resize_sizes.size(), ncams = (uint32_t)D->rect_models.size();
+  for (uint32_t i = 0; i < n; i++) {
+    const amdAprilTagsSize_t& t = D->resize_sizes[RESIZE_SIZE_OF_SLOT(i, nsizes)];   // (tools_hooks.h: i % nsizes)
+    ResizeDesc& z = D->h_zdesc[i];
+    z.src = images[i].dev_ptr;
+    z.src_pitch = (uint32_t)images[i].pitch;
+    z.dst = D->d_conv + (size_t)i * D->conv_pitch * D->cfg.height;
+    z.dst_pitch = (uint32_t)D->conv_pitch;
+    z.fmt = fmt;
+    z.SW = (int32_t)images[i].width; z.SH = (int32_t)images[i].height;
+    z.DW = (int32_t)t.width; z.DH = (int32_t)t.height;
+    z.rectify = ncams ? 1u : 0u;
+    if (ncams) {
+      const amdAprilTagsCameraModel_t& m = D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)];
+      z.model = {m.K[0], m.K[4], m.K[2], m.K[5], m.D[0], m.D[1], m.D[2], m.D[3], m.D[4], m.Knew[0], m.Knew[4], m.Knew[2], m.Knew[5]};
+    }
+    D->rect_imgs[i].width = t.width; D->rect_imgs[i].height = t.height;
+    D->rect_imgs[i].dev_ptr = z.dst;
     D->rect_imgs[i].pitch = D->conv_pitch;
   }
   return D->rect_imgs.data();
@@ -1276,19 +1356,26 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
 // Everything one submission enqueues on stream s (and the auxiliary streams forked from it): descriptor upload, clears,
 // the stage sequence, result download.  No host synchronisation inside, so the sequence can be stream-captured.
 static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride, hipStream_t s, uint32_t fmt, const std::function<void()>& mark) {
-  const bool rect = !D->rect_models.empty();   // (the setter refuses while a submission is in flight: a regrowth relaunch rectifies again)
+  // (the setters refuse while a submission is in flight: a regrowth relaunch resizes and rectifies again)
+  const bool resize = !D->resize_sizes.empty(), rect = !resize && !D->rect_models.empty();
   mark();
   // descriptor upload + clears in one small kernel (it reads the pinned descriptor block over the bus itself): a copy
   // command and a fill command ahead of the first kernel cost a one-frame call about 15 us, this launch 4
   static_assert(sizeof(FrameDesc) % 4 == 0 && sizeof(FrameDesc) <= 256 && sizeof(FrameCounters) % 4 == 0 && sizeof(FrameCounters) <= 256, "k_prologue: one word per thread");
   hipLaunchKernelGGL(k_prologue, dim3(n), dim3(64), 0, s, reinterpret_cast<const uint32_t*>(D->h_frames),
                      static_cast<uint32_t*>(D->d_frames.p), D->d_workctl, reinterpret_cast<uint32_t*>(D->d_counters),
-                     (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4), reinterpret_cast<const uint32_t*>(D->h_rdesc),
-                     static_cast<uint32_t*>(D->d_rdesc.p), rect ? (int)(sizeof(RectDesc) / 4) : 0);
+                     (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4),
+                     resize ? reinterpret_cast<const uint32_t*>(D->h_zdesc) : reinterpret_cast<const uint32_t*>(D->h_rdesc),
+                     resize ? static_cast<uint32_t*>(D->d_zdesc.p) : static_cast<uint32_t*>(D->d_rdesc.p),
+                     resize ? (int)(sizeof(ResizeDesc) / 4) : rect ? (int)(sizeof(RectDesc) / 4) : 0);
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
-  if (rect)
+  // resize: the same, at each slot's target size, through the rectification where that is on (in place of k_rectify_frames)
+  if (resize)
+    hipLaunchKernelGGL(k_resize_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
+                       D->d_zdesc);
+  else if (rect)
     hipLaunchKernelGGL(k_rectify_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
                        D->d_rdesc);
   mark();
@@ -1522,8 +1609,12 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   if (!guard.ok) return AMDAT_HIP_ERROR;
   if (D->unusable) return AMDAT_OUT_OF_MEMORY;   // (never launch on the half-allocated buffers of a failed regrowth)
   const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
-  D->last_rectified = !D->rect_models.empty();
-  if (D->last_rectified) {   // from here on a mono8 submission of the rectified plane's slots
+  D->last_resized = !D->resize_sizes.empty();
+  D->last_rectified = !D->last_resized && !D->rect_models.empty();   // (resized: the rectified plane is never formed)
+  if (D->last_resized) {   // from here on a mono8 submission of the plane's slots at their target sizes
+    images = fill_resize(D, n, images, fmt);
+    fmt = AMDAT_ENC_MONO8;
+  } else if (D->last_rectified) {   // from here on a mono8 submission of the rectified plane's slots
     images = fill_rect(D, n, images, fmt);
     fmt = AMDAT_ENC_MONO8;
   }
@@ -1591,7 +1682,7 @@ int amdAprilTagsDetectBatchColorEx(amdAprilTagsHandle handle, uint32_t n, const 
                                    const amdAprilTagsCameraIntrinsics_t* per_frame_intrinsics, amdAprilTagsDetectionEx_t* dets_out,
                                    uint32_t* num_dets, uint32_t max_dets, amdAprilTagsStream stream) {
   if (!handle || !dets_out || !num_dets || max_dets == 0) return AMDAT_INVALID_ARGUMENT;
-  int rc = check_images(handle, n, images, (uint32_t)encoding);
+  int rc = check_images(handle, n, images, (uint32_t)encoding, !handle->resize_sizes.empty());
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : handle->own_stream;
   uint32_t ostride = max_dets < handle->P.dcap ? max_dets : handle->P.dcap;
@@ -1641,7 +1732,7 @@ int amdAprilTagsDetectBatchColor(amdAprilTagsHandle handle, uint32_t n, const am
                                  const amdAprilTagsCameraIntrinsics_t* per_frame_intrinsics, amdAprilTagsID_t* tags_out,
                                  uint32_t* num_tags, uint32_t max_tags, amdAprilTagsStream stream) {
   if (!handle || !tags_out || !num_tags || max_tags == 0) return AMDAT_INVALID_ARGUMENT;
-  int rc = check_images(handle, n, images, (uint32_t)encoding);
+  int rc = check_images(handle, n, images, (uint32_t)encoding, !handle->resize_sizes.empty());
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : handle->own_stream;
   uint32_t ostride = max_tags < handle->P.dcap ? max_tags : handle->P.dcap;
@@ -1670,7 +1761,7 @@ int amdAprilTagsDetectColor(amdAprilTagsHandle handle, const amdAprilTagsImageIn
 int amdAprilTagsSubmitBatchColor(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsImageInput_t* images, amdAprilTagsEncoding encoding,
                                  const amdAprilTagsCameraIntrinsics_t* per_frame_intrinsics, uint32_t max_tags, amdAprilTagsStream stream) {
   if (!handle || max_tags == 0) return AMDAT_INVALID_ARGUMENT;
-  int rc = check_images(handle, n, images, (uint32_t)encoding);
+  int rc = check_images(handle, n, images, (uint32_t)encoding, !handle->resize_sizes.empty());
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : handle->own_stream;
   const uint32_t ostride = max_tags < handle->P.dcap ? max_tags : handle->P.dcap;
@@ -1739,6 +1830,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   fill_frames(handle, n, images, nullptr, fmt);
   handle->last_n = n;
   handle->last_rectified = false;   // (never rectifies)
+  handle->last_resized = false;     // (never resizes)
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));
   if (handle->profiling) hipEventRecord(handle->ev[1], s);
   { DetParams P0 = handle->P; P0.frame0 = 0; launch_threshold(handle, P0, n, s, fmt); }
@@ -1872,6 +1964,16 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       const size_t n0 = (size_t)r.W0 * r.H0;
       tmp.resize(n0);
       HIP_TRY(hipMemcpy2D(tmp.data(), r.W0, r.dst, r.dst_pitch, r.W0, r.H0, hipMemcpyDeviceToHost));
+      *bytes = n0;
+      if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
+      return AMDAT_SUCCESS;
+    }
+    case AMDAT_DBG_RESIZED: {   // DW x DH dense: the frame's slot of the plane
+      if (handle->resize_sizes.empty() || !handle->last_resized) return AMDAT_INVALID_ARGUMENT;
+      const ResizeDesc& z = handle->h_zdesc[frame];
+      const size_t n0 = (size_t)z.DW * z.DH;
+      tmp.resize(n0);
+      HIP_TRY(hipMemcpy2D(tmp.data(), z.DW, z.dst, z.dst_pitch, z.DW, z.DH, hipMemcpyDeviceToHost));
       *bytes = n0;
       if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
       return AMDAT_SUCCESS;

@@ -5,27 +5,36 @@
 #pragma once
 #include "common.h"
 
-// dst(x,y) = bilinear sample of src at ((x+0.5)*sw/dw - 0.5, (y+0.5)*sh/dh - 0.5), coordinates in 1/2048
+// ---- the resize statement (oracle: ato_resize_mono8), stated once for k_resize_mono8 and k_resize_frames.
+// dst(x,y) = bilinear sample of src at ((x+0.5)*sw/dw - 0.5, (y+0.5)*sh/dh - 0.5), coordinates in 1/2048.  The position is the same
+// statement along x and along y: the two source indices of destination index i and the 1/2048 weight of the second.
+struct ResizePos { int i0, i1, w; };
+__device__ __forceinline__ ResizePos resize_pos(int i, int sn, int dn) {
+  // fixed-point source position: ((2i+1)*sn*1024/dn - 1024), exact in 64-bit integers (tools_hooks.h: RESIZE_FIXED)
+  long long f = RESIZE_FIXED(i, sn, dn);
+  if (f < 0) f = 0;
+  ResizePos p;
+  p.i0 = (int)(f >> 11);
+  p.w = (int)(f & 2047);
+  if (p.i0 >= sn - 1) { p.i0 = sn - 1; p.w = 0; }
+  p.i1 = min(p.i0 + 1, sn - 1);
+  return p;
+}
+// the 22-bit rounded blend of the four taps
+__device__ __forceinline__ uint32_t resize_blend(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, int wx, int wy) {
+  const uint32_t top = p00 * (2048 - wx) + p01 * wx, bot = p10 * (2048 - wx) + p11 * wx;
+  const uint64_t v = (uint64_t)top * (2048 - wy) + (uint64_t)bot * wy;
+  return (uint32_t)((v + (1ull << 21)) >> 22);
+}
+
 __global__ __launch_bounds__(256) void k_resize_mono8(const uint8_t* __restrict__ src, size_t spitch, int sw, int sh,
                                                       uint8_t* __restrict__ dst, size_t dpitch, int dw, int dh) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= dw || y >= dh) return;
-  // fixed-point source position: ((2x+1)*sw*1024/dw - 1024), exact in 64-bit integers
-  long long fx = ((long long)(2 * x + 1) * sw * 1024) / dw - 1024;
-  long long fy = ((long long)(2 * y + 1) * sh * 1024) / dh - 1024;
-  if (fx < 0) fx = 0;
-  if (fy < 0) fy = 0;
-  int x0 = (int)(fx >> 11), y0 = (int)(fy >> 11);
-  int wx = (int)(fx & 2047), wy = (int)(fy & 2047);
-  if (x0 >= sw - 1) { x0 = sw - 1; wx = 0; }
-  if (y0 >= sh - 1) { y0 = sh - 1; wy = 0; }
-  const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
-  const uint32_t p00 = src[(size_t)y0 * spitch + x0], p01 = src[(size_t)y0 * spitch + x1];
-  const uint32_t p10 = src[(size_t)y1 * spitch + x0], p11 = src[(size_t)y1 * spitch + x1];
-  const uint32_t top = p00 * (2048 - wx) + p01 * wx, bot = p10 * (2048 - wx) + p11 * wx;
-  const uint64_t v = (uint64_t)top * (2048 - wy) + (uint64_t)bot * wy;
-  dst[(size_t)y * dpitch + x] = (uint8_t)((v + (1ull << 21)) >> 22);
+  const ResizePos px = resize_pos(x, sw, dw), py = resize_pos(y, sh, dh);
+  const uint8_t *r0 = src + (size_t)py.i0 * spitch, *r1 = src + (size_t)py.i1 * spitch;
+  dst[(size_t)y * dpitch + x] = (uint8_t)resize_blend(r0[px.i0], r0[px.i1], r1[px.i0], r1[px.i1], px.w, py.w);
 }
 
 struct RectifyParams {
@@ -172,4 +181,99 @@ __global__ __launch_bounds__(256) void k_rectify_frames(const RectDesc* __restri
     case 3: rectify_frame_tile<4, 0, 2>(d); break;
     default: rectify_frame_tile<4, 2, 0>(d); break;
   }
+}
+
+// ---- resize inside the submission (amdAprilTagsSetResize), fused with the rectification where that is on -----------------------------
+// One descriptor per batch slot, uploaded by k_prologue as RectDesc is: the caller's frame at its own size SW x SH, the target size
+// DW x DH of the slot, and the slot of the handle's plane (the one rectification uses) the resized frame S becomes.  S is
+// resize(G), G the frame's gray plane at the source size: convert(frame), or rectify(convert(frame)) with `rectify` set (section 7b's
+// statement with w = SW, h = SH and `model`).  G is never written: a tap of the resize that falls on G is computed where it is needed.
+struct ResizeDesc {
+  const uint8_t* src;
+  uint8_t* dst;          // 4-byte aligned, dst_pitch a multiple of 4 and >= DW rounded up to 4: whole dwords are stored
+  uint32_t src_pitch, dst_pitch;
+  uint32_t fmt;          // amdAprilTagsEncoding of `src`
+  int32_t SW, SH, DW, DH;
+  uint32_t rectify;      // 0: G = convert(frame); 1: G = rectify(convert(frame)) with `model`
+  RectifyParams model;
+};
+static_assert(sizeof(ResizeDesc) % 4 == 0, "k_prologue copies ResizeDesc one word per thread");
+
+// G(x, y) with rectification on, x's and y's terms of the projection given: the rectified value, 0 where it maps outside the source
+template <int NCH, int RIDX, int BIDX, class Src>
+__device__ __forceinline__ uint32_t rectified_gray(Src src, uint32_t pitch, const RectCol& c, const RectRow& r, const RectifyParams& R,
+                                                   int w, int h) {
+  RectTaps t;
+  if (!rect_taps(c, r, R, w, h, t)) return 0u;
+  const Src r0 = src + (size_t)t.y0 * pitch, r1 = src + (size_t)t.y1 * pitch;
+  return rect_blend(rect_gray<NCH, RIDX, BIDX>(r0, t.x0), rect_gray<NCH, RIDX, BIDX>(r0, t.x1), rect_gray<NCH, RIDX, BIDX>(r1, t.x0),
+                    rect_gray<NCH, RIDX, BIDX>(r1, t.x1), t);
+}
+
+// The thread shape of rectify_frame_tile: RF_PX adjacent output pixels by RF_ROWS rows, one dword store a row.  What depends on the
+// column alone -- the resize position, and with RECT the projection terms of its two source columns -- is formed once for the rows;
+// what depends on the row alone once for the pixels.
+template <int NCH, int RIDX, int BIDX, bool RECT>
+__device__ __forceinline__ void resize_frame_tile(const ResizeDesc& d) {
+  const int sw = d.SW, sh = d.SH, dw = d.DW, dh = d.DH;
+  const int x4 = (int)blockIdx.x * RF_BW + (int)(threadIdx.x & 63) * RF_PX;
+  const int ya = (int)blockIdx.y * RF_BH + (int)(threadIdx.x >> 6) * RF_ROWS;
+  if (x4 >= dw || ya >= dh) return;
+  const RectifyParams& R = d.model;
+  typedef __attribute__((address_space(1))) const uint8_t* GlobalSrc;
+  typedef __attribute__((address_space(1))) uint32_t* GlobalDst;
+  const GlobalSrc src = (GlobalSrc)d.src;
+  ResizePos px[RF_PX];
+  RectCol c0[RECT ? RF_PX : 1], c1[RECT ? RF_PX : 1];
+#pragma unroll
+  for (int k = 0; k < RF_PX; k++) {
+    px[k] = resize_pos(min(x4 + k, dw - 1), sw, dw);   // (columns at or beyond dw: the last column's, never stored)
+    if (RECT) { c0[k] = rect_col(px[k].i0, R); c1[k] = rect_col(px[k].i1, R); }
+  }
+#pragma unroll
+  for (int j = 0; j < RF_ROWS; j++) {
+    const int y = ya + j;
+    if (y >= dh) break;
+    const ResizePos py = resize_pos(y, sh, dh);
+    uint32_t word = 0;
+    if (RECT) {
+      const RectRow r0 = rect_row(py.i0, R), r1 = rect_row(py.i1, R);
+#pragma unroll
+      for (int k = 0; k < RF_PX; k++) {
+        if (x4 + k >= dw) break;
+        const uint32_t p00 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c0[k], r0, R, sw, sh);
+        const uint32_t p01 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c1[k], r0, R, sw, sh);
+        const uint32_t p10 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c0[k], r1, R, sw, sh);
+        const uint32_t p11 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c1[k], r1, R, sw, sh);
+        word |= resize_blend(p00, p01, p10, p11, px[k].w, py.w) << (8 * k);
+      }
+    } else {
+      const GlobalSrc r0 = src + (size_t)py.i0 * d.src_pitch, r1 = src + (size_t)py.i1 * d.src_pitch;
+#pragma unroll
+      for (int k = 0; k < RF_PX; k++) {
+        if (x4 + k >= dw) break;
+        word |= resize_blend(rect_gray<NCH, RIDX, BIDX>(r0, px[k].i0), rect_gray<NCH, RIDX, BIDX>(r0, px[k].i1),
+                             rect_gray<NCH, RIDX, BIDX>(r1, px[k].i0), rect_gray<NCH, RIDX, BIDX>(r1, px[k].i1), px[k].w, py.w) << (8 * k);
+      }
+    }
+    *(GlobalDst)(d.dst + (size_t)y * d.dst_pitch + x4) = word;
+  }
+}
+
+template <bool RECT>
+__device__ __forceinline__ void resize_frame_fmt(const ResizeDesc& d) {
+  switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
+    case 0: resize_frame_tile<1, 0, 0, RECT>(d); break;
+    case 1: resize_frame_tile<3, 0, 2, RECT>(d); break;
+    case 2: resize_frame_tile<3, 2, 0, RECT>(d); break;
+    case 3: resize_frame_tile<4, 0, 2, RECT>(d); break;
+    default: resize_frame_tile<4, 2, 0, RECT>(d); break;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_resize_frames(const ResizeDesc* __restrict__ descs) {
+  const ResizeDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x * RF_BW >= d.DW || (int)blockIdx.y * RF_BH >= d.DH) return;   // blocks beyond this frame's target extent
+  if (d.rectify) resize_frame_fmt<true>(d);
+  else resize_frame_fmt<false>(d);
 }

@@ -45,6 +45,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetQuadSigma) set_quad_sigma = nullptr;
   decltype(&amdAprilTagsSetPerFrameSizes) set_per_frame_sizes = nullptr;
   decltype(&amdAprilTagsSetRectification) set_rectification = nullptr;
+  decltype(&amdAprilTagsSetResize) set_resize = nullptr;
 };
 
 DetectorApi& api() {
@@ -82,6 +83,7 @@ DetectorApi& api() {
   BIND(set_quad_sigma, "amdAprilTagsSetQuadSigma")
   BIND(set_per_frame_sizes, "amdAprilTagsSetPerFrameSizes")
   BIND(set_rectification, "amdAprilTagsSetRectification")
+  BIND(set_resize, "amdAprilTagsSetResize")
 #undef BIND
   return a;
 }
@@ -105,9 +107,29 @@ amdAprilTagsCameraModel_t to_abi(const CameraModel& m) {
   return o;
 }
 
-// The camera matrix the pose is computed with: Knew of the stream's model with NodeOptions::rectify, K otherwise.
+bool resizing(const NodeOptions& opt) { return opt.resize_width != 0 && opt.resize_height != 0; }
+
+// The camera matrix the pose is computed with: Knew of the stream's model with NodeOptions::rectify, K otherwise -- and with
+// NodeOptions::resize_width x resize_height that camera scaled to the resized image (image_proc's convention: the first row times
+// resize_width / width, the second times resize_height / height).
 std::array<double, 9> pose_camera(const NodeOptions& opt, const CameraInfo& info) {
-  return opt.rectify ? RectificationModel(info).knew : info.k;
+  std::array<double, 9> k = opt.rectify ? RectificationModel(info).knew : info.k;
+  if (resizing(opt) && info.width != 0 && info.height != 0) {
+    for (int c = 0; c < 3; c++) {
+      k[c] = k[c] * static_cast<double>(opt.resize_width) / static_cast<double>(info.width);
+      k[3 + c] = k[3 + c] * static_cast<double>(opt.resize_height) / static_cast<double>(info.height);
+    }
+  }
+  return k;
+}
+
+void apply_resize(amdAprilTagsHandle detector, const NodeOptions& opt) {
+  if (!resizing(opt)) return;
+  const amdAprilTagsSize_t size = {opt.resize_width, opt.resize_height};
+  const int error = api().set_resize(detector, 1, &size);
+  if (error != 0)
+    throw std::runtime_error("'resize_width' x 'resize_height' " + std::to_string(opt.resize_width) + " x " +
+                             std::to_string(opt.resize_height) + " refused (error code " + std::to_string(error) + ")");
 }
 
 int bytes_per_pixel(const std::string& enc) {
@@ -272,12 +294,13 @@ struct AprilTagNode::Impl {
     if (detector) { api().destroy(detector); detector = nullptr; }   // left over from a failed attempt
     // intrinsics from K, double -> float as the reference does (src/apriltag_node.cpp:442-447)
     amdAprilTagsConfig_t cfg;
-    api().default_config(&cfg, info.width, info.height);
+    const bool resize = resizing(opt);   // the handle has the size the frames are resized to
+    api().default_config(&cfg, resize ? opt.resize_width : info.width, resize ? opt.resize_height : info.height);
     cfg.tile_size = opt.tile_size;
     cfg.decimate = opt.decimate;
     cfg.num_families = 1;
     cfg.families[0] = static_cast<amdAprilTagsFamily>(family_enum);
-    const std::array<double, 9> k = pose_camera(opt, info);   // (rectify: Knew; throws on a model it cannot rectify)
+    const std::array<double, 9> k = pose_camera(opt, info);   // (rectify: Knew; throws on a model it cannot rectify; resize: scaled)
     cfg.intrinsics.fx = static_cast<float>(k[0]);
     cfg.intrinsics.fy = static_cast<float>(k[4]);
     cfg.intrinsics.cx = static_cast<float>(k[2]);
@@ -297,6 +320,7 @@ struct AprilTagNode::Impl {
       const int rerr = api().set_rectification(detector, 1, &model);
       if (rerr != 0) throw std::runtime_error("'rectify': camera model refused (error code " + std::to_string(rerr) + ")");
     }
+    apply_resize(detector, opt);
     width = info.width;
     height = info.height;
     if (!stream && api().stream_create(&stream) != 0) throw std::runtime_error("stream creation failed");
@@ -319,7 +343,11 @@ struct AprilTagNode::Impl {
     }
     // the detector and the conversion buffer are sized from camera_info at initialisation
     // (src/apriltag_node.cpp:228-231,257-260): a frame of another size is dropped before anything is written
-    if (image.width != width || image.height != height || info.width != width || info.height != height ||
+    // (NodeOptions::resize_width x resize_height: a frame of any size the library resizes is taken)
+    const bool size_ok = resizing(opt) ? image.width >= 1 && image.width <= 16384 && image.height >= 1 && image.height <= 16384 &&
+                                             info.width == image.width && info.height == image.height
+                                       : image.width == width && image.height == height && info.width == width && info.height == height;
+    if (!size_ok ||
         static_cast<size_t>(image.step) < static_cast<size_t>(image.width) * bpp || image.data == nullptr) {
       std::fprintf(stderr, "[apriltag_node] image %ux%u (step %u) does not match the initialised size %ux%u: frame dropped\n",
                    image.width, image.height, image.step, width, height);
@@ -413,7 +441,12 @@ struct AprilTagMultiCameraNode::Impl {
   void* d_input = nullptr;         // staging for host / colour frames
   size_t d_input_bytes = 0;
   // k: the camera the pose is computed with (NodeOptions::rectify: Knew of `model`, the stream's camera model)
-  struct Slot { bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; CameraModel model; };
+  // dev, pitch: where the staged mono8 frame lies -- the stream's slot of d_mono, or with NodeOptions::resize_width x resize_height,
+  // where a frame may be larger than the handle, a buffer of the slot's own (own, own_bytes) that grows with the frames
+  struct Slot {
+    bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; CameraModel model;
+    uint8_t* dev = nullptr; size_t pitch = 0; void* own = nullptr; size_t own_bytes = 0;
+  };
   std::vector<Slot> slots;
 
 
@@ -424,7 +457,9 @@ struct AprilTagMultiCameraNode::Impl {
     if (d_mono) { api().dev_free(d_mono); d_mono = nullptr; }
     amdAprilTagsConfig_t cfg;
     mixed = opt.max_width != 0 && opt.max_height != 0;
-    api().default_config(&cfg, mixed ? opt.max_width : info.width, mixed ? opt.max_height : info.height);
+    const bool resize = resizing(opt);   // the handle has the size the frames are resized to (mixed: the largest such size)
+    api().default_config(&cfg, mixed ? opt.max_width : resize ? opt.resize_width : info.width,
+                         mixed ? opt.max_height : resize ? opt.resize_height : info.height);
     cfg.tile_size = opt.tile_size;
     cfg.decimate = opt.decimate;
     cfg.num_families = 1;
@@ -442,13 +477,16 @@ struct AprilTagMultiCameraNode::Impl {
     if (error != 0) throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
     apply_quad_sigma(detector, opt.quad_sigma);
     if (mixed && api().set_per_frame_sizes(detector, 1) != 0) throw std::runtime_error("per-frame image sizes refused");
+    apply_resize(detector, opt);
     width = cfg.width;
     height = cfg.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
     slot_bytes = pitch * height;
-    void* p = nullptr;
-    if (api().dev_alloc(&p, slot_bytes * S) != 0) throw std::runtime_error("device allocation failed");
-    d_mono = static_cast<uint8_t*>(p);
+    if (!resize) {   // (resize: every slot stages into a buffer of its own, sized by its frames)
+      void* p = nullptr;
+      if (api().dev_alloc(&p, slot_bytes * S) != 0) throw std::runtime_error("device allocation failed");
+      d_mono = static_cast<uint8_t*>(p);
+    }
     initialized = true;
   }
 
@@ -462,9 +500,11 @@ struct AprilTagMultiCameraNode::Impl {
     // one size (the first frame's), or -- max_width x max_height set -- every size the handle admits (include/apriltag_amd.h,
     // amdAprilTagsSetPerFrameSizes: up to the handle's, a full threshold tile of the working image in both directions)
     const auto working = [&](uint32_t v) { return 1 + (v - 1) / opt.decimate; };
-    const bool size_ok = mixed ? image.width >= 1 && image.width <= width && image.height >= 1 && image.height <= height &&
+    const bool resize = resizing(opt);
+    const bool size_ok = resize ? image.width >= 1 && image.width <= 16384 && image.height >= 1 && image.height <= 16384
+                         : mixed ? image.width >= 1 && image.width <= width && image.height >= 1 && image.height <= height &&
                                      working(image.width) >= opt.tile_size && working(image.height) >= opt.tile_size
-                               : image.width == width && image.height == height;
+                                 : image.width == width && image.height == height;
     if (!size_ok || info.width != image.width || info.height != image.height ||
         static_cast<size_t>(image.step) < static_cast<size_t>(image.width) * bpp || image.data == nullptr) {
       std::fprintf(stderr, "[apriltag_node] stream %u: image %ux%u (step %u) does not match the initialised size %s%ux%u: frame dropped\n",
@@ -474,7 +514,23 @@ struct AprilTagMultiCameraNode::Impl {
     slots[stream].width = image.width;
     slots[stream].height = image.height;
     const uint8_t* dev_src = image.data;
-    uint8_t* slot = d_mono + slot_bytes * stream;
+    Slot& sl = slots[stream];
+    if (resize) {
+      sl.pitch = (static_cast<size_t>(image.width) + 63) & ~static_cast<size_t>(63);
+      const size_t need = sl.pitch * image.height;
+      if (need > sl.own_bytes) {
+        if (sl.own) api().dev_free(sl.own);
+        sl.own = nullptr; sl.own_bytes = 0;
+        if (api().dev_alloc(&sl.own, need) != 0) throw std::runtime_error("device allocation failed");
+        sl.own_bytes = need;
+      }
+      sl.dev = static_cast<uint8_t*>(sl.own);
+    } else {
+      sl.dev = d_mono + slot_bytes * stream;
+      sl.pitch = this->pitch;
+    }
+    uint8_t* slot = sl.dev;
+    const size_t pitch = sl.pitch;
     if (!image.is_device) {
       const size_t bytes = static_cast<size_t>(image.step) * image.height;
       if (bpp == 1 && image.step == pitch) {   // straight into the slot
@@ -508,6 +564,7 @@ AprilTagMultiCameraNode::~AprilTagMultiCameraNode() {
     if (impl_->detector) api().destroy(impl_->detector);
     if (impl_->d_input) api().dev_free(impl_->d_input);
     if (impl_->d_mono) api().dev_free(impl_->d_mono);
+    for (auto& sl : impl_->slots) if (sl.own) api().dev_free(sl.own);
   }
 }
 
@@ -531,7 +588,7 @@ bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& 
   if (!impl_->Stage(stream, image, camera_info)) return false;
   sl.pending = true;
   sl.info_header = camera_info.header;
-  sl.k = impl_->opt.rectify ? model.knew : camera_info.k;
+  sl.k = pose_camera(impl_->opt, camera_info);   // (rectify: Knew; resize: scaled to the resized image)
   sl.model = model;
   if (impl_->auto_flush) {
     bool all = true;
@@ -551,7 +608,7 @@ uint32_t AprilTagMultiCameraNode::Flush() {
   std::vector<amdAprilTagsCameraIntrinsics_t> intr(n);
   for (uint32_t i = 0; i < n; i++) {
     const Impl::Slot& sl = I.slots[who[i]];
-    imgs[i].width = sl.width; imgs[i].height = sl.height; imgs[i].dev_ptr = I.d_mono + I.slot_bytes * who[i]; imgs[i].pitch = I.pitch;
+    imgs[i].width = sl.width; imgs[i].height = sl.height; imgs[i].dev_ptr = sl.dev; imgs[i].pitch = sl.pitch;
     // K of the stream's own CameraInfo, double -> float as the reference does (src/apriltag_node.cpp:442-447)
     intr[i].fx = static_cast<float>(sl.k[0]); intr[i].fy = static_cast<float>(sl.k[4]);
     intr[i].cx = static_cast<float>(sl.k[2]); intr[i].cy = static_cast<float>(sl.k[5]);
@@ -651,10 +708,10 @@ int node_shell_camera_model(const double* k9, const double* d, int nd, const cha
   }
 }
 
-// Every NodeOptions field the flat view carries (node.py): the create calls below are this one with quad_sigma 0 and rectify off.
+// Every NodeOptions field the flat view carries (node.py): the create calls below are this one with quad_sigma 0, rectify off and no resize.
 NodeShellHarness* node_shell_create_opts(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
-                                         int decimate, int strict_cuapriltags_encodings, double quad_sigma, int rectify, char* err,
-                                         size_t err_len) {
+                                         int decimate, int strict_cuapriltags_encodings, double quad_sigma, int rectify,
+                                         uint32_t resize_width, uint32_t resize_height, char* err, size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
@@ -662,6 +719,7 @@ NodeShellHarness* node_shell_create_opts(int max_tags, double size, int tile_siz
     o.strict_cuapriltags_encodings = strict_cuapriltags_encodings != 0;
     o.quad_sigma = quad_sigma;
     o.rectify = rectify != 0;
+    o.resize_width = resize_width; o.resize_height = resize_height;
     auto* h = new NodeShellHarness();
     h->node.reset(new AprilTagNode(o));
     h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
@@ -676,7 +734,7 @@ NodeShellHarness* node_shell_create_opts(int max_tags, double size, int tile_siz
 NodeShellHarness* node_shell_create_ex(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
                                        int decimate, int strict_cuapriltags_encodings, double quad_sigma, char* err, size_t err_len) {
   return node_shell_create_opts(max_tags, size, tile_size, tag_family, backends, decimate, strict_cuapriltags_encodings, quad_sigma, 0,
-                                err, err_len);
+                                0, 0, err, err_len);
 }
 
 // Returns nullptr and fills err on a constructor exception (mirrors test/apriltag_node_test.cpp).
@@ -752,10 +810,11 @@ struct MultiShellHarness {
   std::vector<int> publishes;
 };
 
-// max_width, max_height, rectify: NodeOptions of the same names (0, 0: one size, the first frame's)
+// max_width, max_height, rectify, resize_width, resize_height: NodeOptions of the same names (0, 0: one size, the first frame's)
 MultiShellHarness* node_shell_multi_create_opts(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
                                                 const char* backends, int decimate, int auto_flush, double quad_sigma,
-                                                uint32_t max_width, uint32_t max_height, int rectify, char* err, size_t err_len) {
+                                                uint32_t max_width, uint32_t max_height, int rectify, uint32_t resize_width,
+                                                uint32_t resize_height, char* err, size_t err_len) {
   try {
     NodeOptions o;
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
@@ -763,6 +822,7 @@ MultiShellHarness* node_shell_multi_create_opts(int num_streams, int max_tags, d
     o.quad_sigma = quad_sigma;
     o.max_width = max_width; o.max_height = max_height;
     o.rectify = rectify != 0;
+    o.resize_width = resize_width; o.resize_height = resize_height;
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
     h->node->set_auto_flush(auto_flush != 0);
@@ -780,7 +840,7 @@ MultiShellHarness* node_shell_multi_create_sized(int num_streams, int max_tags, 
                                                  const char* backends, int decimate, int auto_flush, double quad_sigma,
                                                  uint32_t max_width, uint32_t max_height, char* err, size_t err_len) {
   return node_shell_multi_create_opts(num_streams, max_tags, size, tile_size, tag_family, backends, decimate, auto_flush, quad_sigma,
-                                      max_width, max_height, 0, err, err_len);
+                                      max_width, max_height, 0, 0, 0, err, err_len);
 }
 
 MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,

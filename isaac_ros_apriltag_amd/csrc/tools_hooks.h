@@ -31,12 +31,16 @@
 //                           9 = the rectification statement (kernels_frontend.h: rect_taps) truncates the fixed-point source position,
 //                               (int)(u * 32.0) without the + 0.5: taps and weights one 1/32 step low wherever the fraction is a half or more
 //                           10 = amdAprilTagsSetRectification: every frame of a submission takes cams[0] instead of cams[i % ncams]
-//                           (4 .. 10 change values only: no address, index bound, launch size or loop count)
+//                           11 = the resize statement (kernels_frontend.h: resize_pos) without the half-pixel term: the source
+//                               position (2i * sn * 1024) / dn instead of ((2i + 1) * sn * 1024) / dn - 1024 (indices clamped as before)
+//                           12 = amdAprilTagsSetResize: every frame of a submission takes sizes[0] instead of sizes[i % nsizes]
+//                           (4 .. 12 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
 //                           tests/test_fit_classes_gpu.py::test_fit_class_tests_fail_on_the_wrong_builds for 7 and 8,
-//                           tests/test_rectify_submission_gpu.py::test_the_rectify_tests_fail_on_the_wrong_builds for 9 and 10)
+//                           tests/test_rectify_submission_gpu.py::test_the_rectify_tests_fail_on_the_wrong_builds for 9 and 10,
+//                           tests/test_resize_submission_gpu.py::test_the_resize_tests_fail_on_the_wrong_builds for 11 and 12)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -78,6 +82,18 @@
 #define RECT_MODEL_OF_SLOT(i, ncams) ((void)(i), (void)(ncams), 0u)
 #else
 #define RECT_MODEL_OF_SLOT(i, ncams) ((i) % (ncams))
+#endif
+
+// ---- resize: the source position in 1/2048 pixel of destination index i, and the target size of batch slot i -------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 11
+#define RESIZE_FIXED(i, sn, dn) (((long long)(2 * (i)) * (sn) * 1024) / (dn))
+#else
+#define RESIZE_FIXED(i, sn, dn) (((long long)(2 * (i) + 1) * (sn) * 1024) / (dn) - 1024)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 12
+#define RESIZE_SIZE_OF_SLOT(i, nsizes) ((void)(i), (void)(nsizes), 0u)
+#else
+#define RESIZE_SIZE_OF_SLOT(i, nsizes) ((i) % (nsizes))
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------

@@ -50,7 +50,8 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
-                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, **caps):
+                 tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
+                 **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -78,6 +79,7 @@ class AprilTagDetector:
         capi._check("amdCreateAprilTagsDetectorEx", L.amdCreateAprilTagsDetectorEx(C.byref(self._h), C.byref(cfg)))
         self._L = L
         self.per_frame_sizes = False
+        self.resizing = False
         try:
             if quad_sigma:
                 self.set_quad_sigma(quad_sigma)
@@ -85,6 +87,8 @@ class AprilTagDetector:
                 self.set_per_frame_sizes(True)
             if rectification:
                 self.set_rectification(rectification)
+            if resize:
+                self.set_resize(resize)
         except Exception:
             self.close()
             raise
@@ -106,6 +110,15 @@ class AprilTagDetector:
         arr = capi.camera_models(models)
         capi._check("amdAprilTagsSetRectification", self._L.amdAprilTagsSetRectification(self._h, len(arr) if arr is not None else 0, arr))
 
+    def set_resize(self, sizes):
+        """amdAprilTagsSetResize: sizes is a list of (width, height) -- frame i of every following submission, whatever its own size, is
+        resized to sizes[i % len(sizes)] inside the submission (through the rectification where that is on) and detected there; None
+        or [] turns it off.  Tensors are then taken at their shape.  The pose intrinsics stay the caller's: scale them by dw / sw and
+        dh / sh."""
+        arr = capi.sizes(sizes)
+        capi._check("amdAprilTagsSetResize", self._L.amdAprilTagsSetResize(self._h, len(arr) if arr is not None else 0, arr))
+        self.resizing = arr is not None
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self._L.amdAprilTagsDestroy(self._h)
@@ -120,7 +133,7 @@ class AprilTagDetector:
     # ---- detection --------------------------------------------------------------------------------
     def detect_batch_ex(self, frames, max_dets=64, intrinsics=None, stream=None, encoding="mono8"):
         """encoding != "mono8": frames are interleaved colour ([n,H,W,C]) and go through amdAprilTagsDetectBatchColorEx."""
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes)
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes or self.resizing)
         n = len(imgs)
         out = (capi.DetectionEx * (n * max_dets))()
         cnt = (C.c_uint32 * n)()
@@ -148,7 +161,7 @@ class AprilTagDetector:
 
     # ---- prepared submissions: argument marshalling done once, the timed call is only the C ABI call ----
     def prepare(self, frames, max_dets=64, intrinsics=None, encoding="mono8"):
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes)
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes or self.resizing)
         n = len(imgs)
         intr = None
         if intrinsics is not None:
@@ -197,7 +210,7 @@ class AprilTagDetector:
 
     def detect_batch_raw(self, frames, max_tags=64, intrinsics=None, stream=None):
         """Returns (TagID ctypes array of n*max_tags, counts) -- the cuAprilTagsID_t-shaped records."""
-        imgs, keep = _as_images(frames, self.width, self.height, 1, self.per_frame_sizes)
+        imgs, keep = _as_images(frames, self.width, self.height, 1, self.per_frame_sizes or self.resizing)
         n = len(imgs)
         out = (capi.TagID * (n * max_tags))()
         cnt = (C.c_uint32 * n)()
@@ -269,7 +282,7 @@ class AprilTagDetector:
         capi._check("amdAprilTagsDebugCopy",
                     self._L.amdAprilTagsDebugCopy(self._h, frame, what, buf.ctypes.data, buf.size, C.byref(nbytes)))
         buf = buf[:nbytes.value]
-        if what in (capi.DBG_GRAY, capi.DBG_THRESH, capi.DBG_RECTIFIED):
+        if what in (capi.DBG_GRAY, capi.DBG_THRESH, capi.DBG_RECTIFIED, capi.DBG_RESIZED):
             return buf
         if what in (capi.DBG_LABEL, capi.DBG_CSIZE, capi.DBG_POINTS, capi.DBG_COUNTS):
             return buf.view(np.uint32)

@@ -34,7 +34,7 @@ def lib():
                                            C.c_char_p, C.c_size_t]
         L.node_shell_create_opts.restype = C.c_void_p
         L.node_shell_create_opts.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int,
-                                             C.c_char_p, C.c_size_t]
+                                             C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
         L.node_shell_camera_model.restype = C.c_int
         L.node_shell_camera_model.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
@@ -46,7 +46,8 @@ def lib():
                                                C.POINTER(ShellDetection), C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         L.node_shell_multi_create_opts.restype = C.c_void_p
         L.node_shell_multi_create_opts.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
-                                                   C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+                                                   C.c_double, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p,
+                                                   C.c_size_t]
         L.node_shell_multi_on_frame_info.restype = C.c_int
         L.node_shell_multi_on_frame_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32,
                                                      C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p,
@@ -114,15 +115,18 @@ class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False):
+                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
-        undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12)."""
+        undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12).  resize
+        (NodeOptions::resize_width, resize_height): (w, h) -- frames of any size are resized to it inside the submission, behind the
+        rectification, and the pose is computed with the scaled camera."""
+        rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self._h = self._L.node_shell_multi_create_opts(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
                                                        decimate, 1 if auto_flush else 0, float(quad_sigma), int(max_width),
-                                                       int(max_height), 1 if rectify else 0, err, 1024)
+                                                       int(max_height), 1 if rectify else 0, rw, rh, err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags, self.num_streams = max_tags, num_streams
@@ -170,15 +174,18 @@ class AprilTagNode:
     """Parameters and defaults of the reference node (apriltag_node.cpp:564-568)."""
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False):
+                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None):
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
-        (on_frame: D, distortion_model, P12), and the pose is computed with Knew."""
+        (on_frame: D, distortion_model, P12), and the pose is computed with Knew.  resize (NodeOptions::resize_width, resize_height):
+        (w, h) -- the handle has that size, frames of any size are resized to it inside the submission, behind the rectification, and
+        the pose is computed with the camera scaled by w / width and h / height."""
+        rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self._h = self._L.node_shell_create_opts(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
                                                  1 if strict_cuapriltags_encodings else 0, float(quad_sigma), 1 if rectify else 0,
-                                                 err, 1024)
+                                                 rw, rh, err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags = max_tags

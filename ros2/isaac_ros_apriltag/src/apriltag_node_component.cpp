@@ -51,6 +51,10 @@ public:
     // the image topic is the camera's distorted image: undistorted inside the detector's submission with camera_info's plumb_bob model
     // (K, D; the rectified camera is the left 3x3 of P), in place of a RectifyNode in front of this one
     opt.rectify = declare_parameter<bool>("rectify", false);
+    // both set: every frame, whatever its size, is resized to resize_width x resize_height inside the detector's submission (behind the
+    // rectification), in place of a ResizeNode in front of this one; the pose uses the camera scaled to that size.  0: off
+    opt.resize_width = static_cast<uint32_t>(declare_parameter<int>("resize_width", 0));
+    opt.resize_height = static_cast<uint32_t>(declare_parameter<int>("resize_height", 0));
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);
