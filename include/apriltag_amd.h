@@ -313,6 +313,34 @@ typedef struct { double K[9]; double D[5]; double Knew[9]; } amdAprilTagsCameraM
  * the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the models does not. */
 int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModel_t* cams);
 
+/* The same for every camera sensor_msgs/CameraInfo describes: its three distortion models, behind its rectification rotation R (the
+ * one a stereo head fills in).  The values are those of amdAprilTagsDistortionFromName. */
+typedef enum {
+  AMDAT_DISTORTION_PLUMB_BOB = 0,             /* D = k1, k2, p1, p2, k3 */
+  AMDAT_DISTORTION_RATIONAL_POLYNOMIAL = 1,   /* D = k1, k2, p1, p2, k3, k4, k5, k6 */
+  AMDAT_DISTORTION_EQUIDISTANT = 2            /* D = k1, k2, k3, k4 (OpenCV's fisheye model) */
+} amdAprilTagsDistortion;
+/* "plumb_bob", "rational_polynomial", "equidistant" (CameraInfo.distortion_model) -> the enum; -1 for any other string or null. */
+int amdAprilTagsDistortionFromName(const char* name);
+/* K, R, Knew: row-major 3x3.  D: the kind's coefficients in CameraInfo's order; the entries beyond the kind's own must be 0. */
+typedef struct { uint32_t kind; uint32_t reserved; double K[9]; double D[8]; double R[9]; double Knew[9]; } amdAprilTagsCameraModelEx_t;
+/* amdAprilTagsSetRectification for cameras of any of the three kinds, with a rotation: the same contract, word for word -- host state
+ * of the handle, no device synchronisation, cams[i % ncams] for frame i, one front launch per submission (one submission may mix kinds
+ * and rotations), graphs retired only when the mode turns on or off, the same refusals, a refused call leaves the previous setting in
+ * force -- and amdAprilTagsSetResize composes with it as with the other call: a tap of the resize is the rectified value under the
+ * slot's model.  amdAprilTagsSetRectification is this call with AMDAT_DISTORTION_PLUMB_BOB and R = I; the later of the two calls holds.
+ * Destination pixel (x, y) is projected as xp = (x - Knew[2]) / Knew[0], yp = (y - Knew[5]) / Knew[4], (X, Y, W) = R^T (xp, yp, 1),
+ * xn = X / W, yn = Y / W (W <= 0: the pixel is 0), then through the kind's distortion and K, in double precision; position, bilinear
+ * sum and bounds are those of amdAprilTagsRectifyMono8 (DESIGN.md section 7b has every operation).  A plumb_bob camera whose R is
+ * exactly the identity gives what amdAprilTagsSetRectification gives, byte for byte, and so does rational_polynomial with k4 = k5 =
+ * k6 = 0.
+ * The pose intrinsics stay the caller's: pass Knew's fx, fy, cx, cy as with the other call.  R never touches the pose -- the tag pose
+ * is reported in the RECTIFIED camera's frame, as it is behind a RectifyNode.
+ * AMDAT_INVALID_ARGUMENT in addition to the other call's cases: a kind outside the enum, a non-finite entry of D or R, a non-zero
+ * coefficient beyond the kind's own, and an R that is all zero -- a CameraInfo that was never filled in; the library does not guess,
+ * a monocular camera passes the identity. */
+int amdAprilTagsSetRectificationEx(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams);
+
 /* Resize inside the submission, fused with the rectification where that is on: the reference's camera -> rectify -> resize -> AprilTag
  * graph as one submission. */
 typedef struct { uint32_t width, height; } amdAprilTagsSize_t;
@@ -365,6 +393,10 @@ int amdAprilTagsResizeMono8(const uint8_t* src_dev, size_t src_pitch, uint32_t s
 int amdAprilTagsRectifyMono8(const uint8_t* src_dev, size_t src_pitch, uint8_t* dst_dev, size_t dst_pitch, uint32_t width,
                              uint32_t height, const double* K9, const double* D5, const double* Knew9,
                              amdAprilTagsStream stream);
+/* The same for a camera of any of the three kinds with a rotation (amdAprilTagsCameraModelEx_t, validated as by
+ * amdAprilTagsSetRectificationEx): what that call computes inside the submission, for one mono8 frame on the caller's stream. */
+int amdAprilTagsRectifyMono8Ex(const uint8_t* src_dev, size_t src_pitch, uint8_t* dst_dev, size_t dst_pitch, uint32_t width,
+                               uint32_t height, const amdAprilTagsCameraModelEx_t* cam, amdAprilTagsStream stream);
 
 /* Device-memory helpers for hosts that do not link the HIP runtime themselves (the node shell copies
  * sensor_msgs/Image payloads with these).  Plain hipMalloc / hipFree / hipMemcpyAsync + sync. */

@@ -40,10 +40,11 @@ struct CameraInfo {
   Header header;
   uint32_t height = 0, width = 0;
   std::array<double, 9> k{};  // the node reads K (k[0],k[4],k[2],k[5]), src/apriltag_node.cpp:442-446
-  // read only with NodeOptions::rectify (RectificationModel below)
+  // read only with NodeOptions::rectify (RectificationModel below) or rectify_full (RectificationModelEx)
   std::vector<double> d;            // distortion coefficients: k1, k2, p1, p2, k3 of "plumb_bob" (fewer: zero-padded)
-  std::string distortion_model;     // "plumb_bob" or empty
+  std::string distortion_model;     // "plumb_bob" or empty; with rectify_full also "rational_polynomial" and "equidistant"
   std::array<double, 12> p{};       // projection matrix: its left 3x3 is the rectified image's camera when p[0] != 0
+  std::array<double, 9> r{};        // rectification rotation (rectify_full only); all zero, as a driver that never fills it leaves it: the identity
 };
 
 // The camera model NodeOptions::rectify hands the detector (amdAprilTagsCameraModel_t): K and D of the distorted image, and the
@@ -55,6 +56,20 @@ struct CameraModel {
 };
 // Throws std::runtime_error for a distortion_model other than "plumb_bob" / empty and for more than five coefficients.
 CameraModel RectificationModel(const CameraInfo& camera_info);
+
+// The camera model NodeOptions::rectify_full hands the detector (amdAprilTagsCameraModelEx_t): kind is amdAprilTagsDistortion --
+// "plumb_bob" or empty 0, "rational_polynomial" 1, "equidistant" 2 -- with up to 5, 8 and 4 coefficients, zero-padded; r is
+// CameraInfo::r, the identity where that is all zero; knew as in CameraModel.
+struct CameraModelEx {
+  uint32_t kind = 0;
+  std::array<double, 9> k{};
+  std::array<double, 8> d{};
+  std::array<double, 9> r{};
+  std::array<double, 9> knew{};
+};
+// Throws std::runtime_error for any other distortion_model (the text names the three known ones) and for more coefficients than
+// the model has.
+CameraModelEx RectificationModelEx(const CameraInfo& camera_info);
 
 struct Point { double x = 0, y = 0, z = 0; };
 struct Quaternion { double x = 0, y = 0, z = 0, w = 1; };
@@ -99,6 +114,10 @@ struct NodeOptions {
   // stream's CameraInfo (AprilTagNode: of the first frame's, like K; AprilTagMultiCameraNode: of every staged frame's, set before each
   // flush in slot order), and the pose is computed with Knew -- fx, fy, cx, cy, and its [0][1] as the skew in VPI mode -- in place of K.
   bool rectify = false;
+  // The same for every camera a CameraInfo describes (amdAprilTagsSetRectificationEx): the model is RectificationModelEx -- the three
+  // distortion models, and the rectification rotation r of a stereo head.  Turns rectification on by itself; with it off `rectify`
+  // takes plumb_bob alone and ignores r, as it always has.  The pose is reported in the rectified camera's frame.
+  bool rectify_full = false;
   // Extension: every frame is resized to resize_width x resize_height INSIDE the detector's submission, behind the rectification where
   // `rectify` is set (amdAprilTagsSetResize; the reference puts a ResizeNode in front and recommends it for 4K input, README.md:16-29).
   // Both set: AprilTagNode creates its handle at that size, AprilTagMultiCameraNode at that size too (or at max_width x max_height with

@@ -35,6 +35,12 @@ class CameraModel(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 5), ("Knew", C.c_double * 9)]
 
 
+class CameraModelEx(C.Structure):
+    """amdAprilTagsCameraModelEx_t: kind (DISTORTIONS), row-major 3x3 K, R and Knew, D in CameraInfo's order for the kind."""
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9),
+                ("Knew", C.c_double * 9)]
+
+
 class Size(C.Structure):
     """amdAprilTagsSize_t."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
@@ -81,9 +87,12 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSubmitBatchColor", "amdAprilTagsThresholdOnlyColor", "amdAprilTagsCopyToDeviceAsync", "amdAprilTagsStreamCreate",
            "amdAprilTagsStreamDestroy", "amdAprilTagsDebugGraphReplay", "amdAprilTagsConfigLayoutVersion",
            "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes",
-           "amdAprilTagsSetRectification", "amdAprilTagsSetResize"]
+           "amdAprilTagsSetRectification", "amdAprilTagsSetResize", "amdAprilTagsDistortionFromName",
+           "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
+DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
+DISTORTION_COEFFS = {"plumb_bob": 5, "rational_polynomial": 8, "equidistant": 4}
 ENC_CHANNELS = {"mono8": 1, "rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4}
 
 _lib = None
@@ -158,10 +167,14 @@ def lib():
     L.amdAprilTagsSetPerFrameSizes.argtypes = [H, C.c_int]
     L.amdAprilTagsSetRectification.argtypes = [H, C.c_uint32, C.POINTER(CameraModel)]
     L.amdAprilTagsSetResize.argtypes = [H, C.c_uint32, C.POINTER(Size)]
+    L.amdAprilTagsDistortionFromName.argtypes = [C.c_char_p]
+    L.amdAprilTagsSetRectificationEx.argtypes = [H, C.c_uint32, C.POINTER(CameraModelEx)]
+    L.amdAprilTagsRectifyMono8Ex.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                             C.POINTER(CameraModelEx), H]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if fn.restype is C.c_int or name in ("amdAprilTagsFamilyFromName", "amdAprilTagsEncodingFromName"):
+        if fn.restype is C.c_int or name in ("amdAprilTagsFamilyFromName", "amdAprilTagsEncodingFromName", "amdAprilTagsDistortionFromName"):
             fn.restype = C.c_int
     _lib = L
     return L
@@ -233,6 +246,37 @@ def camera_models(models):
             raise ValueError("a camera model is (K[3x3], D[<= 5], Knew[3x3])")
         m.K[:], m.Knew[:] = list(k), list(kn)
         m.D[:] = list(d) + [0.0] * (5 - d.size)
+    return arr
+
+
+def camera_model_ex(K, D, Knew, model_name="plumb_bob", R=None):
+    """One amdAprilTagsCameraModelEx_t.  model_name: a key of DISTORTIONS, or the enum's integer (passed on as it stands, for the
+    library to judge); D: up to the kind's coefficients (eight for an integer kind), zero-padded; R: 3x3 or 9 values, None: the
+    identity."""
+    m = CameraModelEx()
+    if isinstance(model_name, str):
+        if model_name not in DISTORTIONS:
+            raise ValueError("unknown distortion model %r: known are plumb_bob, rational_polynomial and equidistant" % (model_name,))
+        m.kind, nmax = DISTORTIONS[model_name], DISTORTION_COEFFS[model_name]
+    else:
+        m.kind, nmax = int(model_name), 8
+    k, d, kn = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (K, D, Knew))
+    r = np.eye(3).reshape(-1) if R is None else np.asarray(R, dtype=np.float64).reshape(-1)
+    if k.size != 9 or kn.size != 9 or r.size != 9 or d.size > nmax:
+        raise ValueError("a camera model is (K[3x3], D[<= %d for this kind], Knew[3x3], model_name, R[3x3] or None)" % nmax)
+    m.K[:], m.Knew[:], m.R[:] = list(k), list(kn), list(r)
+    m.D[:] = list(d) + [0.0] * (8 - d.size)
+    return m
+
+
+def camera_models_ex(models):
+    """[(K, D, Knew) or (K, D, Knew, model_name, R)] -> a ctypes array of amdAprilTagsCameraModelEx_t (a 3-tuple: plumb_bob, R = I)."""
+    models = list(models)
+    arr = (CameraModelEx * len(models))()
+    for i, m in enumerate(models):
+        if len(m) not in (3, 5):
+            raise ValueError("a camera model is (K, D, Knew) or (K, D, Knew, model_name, R)")
+        arr[i] = camera_model_ex(*m)
     return arr
 
 

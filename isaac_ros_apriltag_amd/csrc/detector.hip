@@ -223,7 +223,8 @@ struct amdAprilTagsDetector_st {
   bool fq_attr_set = false;
   // captured enqueue sequence of small submissions (see run_batch)
   uint32_t graph_max_frames = 8;
-  struct GraphEntry { hipGraphExec_t exec = nullptr; uint32_t n = 0, ostride = 0, fmt = 0; hipStream_t stream = nullptr; uint64_t last_use = 0; };
+  struct GraphEntry { hipGraphExec_t exec = nullptr; uint32_t n = 0, ostride = 0, fmt = 0; hipStream_t stream = nullptr; uint64_t last_use = 0;
+                      bool general = false; };   // general: captured with the general front kernel (rect_general)
   GraphEntry graphs[6];
   std::vector<hipGraphExec_t> retired_graphs;   // see drop_graphs
   uint64_t graph_clock = 0;
@@ -251,7 +252,8 @@ struct amdAprilTagsDetector_st {
   bool per_frame_sizes = false;
   // amdAprilTagsSetRectification: frame i of a submission is undistorted with rect_models[i % size] into slot i of the rectified plane
   // (d_conv: a rectified submission never takes the conversion launch) by k_rectify_frames, and the pipeline sees that slot as a mono8 frame
-  std::vector<amdAprilTagsCameraModel_t> rect_models;   // empty: off
+  std::vector<amdAprilTagsCameraModelEx_t> rect_models; // empty: off (amdAprilTagsSetRectification stores plumb_bob, R = I)
+  bool rect_general = false;                            // some model needs the general projection: the front launch is the _general kernel
   RectDesc* h_rdesc = nullptr;                          // pinned, one per batch slot: k_prologue uploads them with the frame descriptors
   DevBuf<RectDesc> d_rdesc;
   std::vector<amdAprilTagsImageInput_t> rect_imgs;      // the plane's slots as the mono8 images of the submission (fill_rect)
@@ -275,6 +277,7 @@ __global__ void k_debug_math(int op, uint32_t n, const double* a, const double* 
   else if (op == 2) out[i] = (double)at_sqrtf_rn((float)a[i]);
   else if (op == 3) out[i] = (double)__fdiv_rn((float)a[i], (float)b[i]);
   else if (op == 5) out[i] = sqrt_u18((uint32_t)a[i]);     // integer arguments below 2^18
+  else if (op == 6) out[i] = atan_s(a[i]);                 // the equidistant model's arctangent (camera_models.h)
   else out[i] = div_by(a[i], b[i], shared_recip(b[i]));   // the line fit's shared-reciprocal division
 }
 
@@ -922,13 +925,67 @@ static int ensure_rect_buffers(amdAprilTagsDetector_st* D) {
   return AMDAT_SUCCESS;
 }
 
+// What amdAprilTagsSetRectificationEx and amdAprilTagsRectifyMono8Ex refuse in a camera model.
+static bool camera_model_ok(const amdAprilTagsCameraModelEx_t& m) {
+  static const int ncoef[3] = {5, 8, 4};   // plumb_bob, rational_polynomial, equidistant
+  if (m.kind > AMDAT_DISTORTION_EQUIDISTANT) return false;
+  for (double v : m.K) if (!std::isfinite(v)) return false;
+  for (double v : m.D) if (!std::isfinite(v)) return false;
+  for (double v : m.R) if (!std::isfinite(v)) return false;
+  for (double v : m.Knew) if (!std::isfinite(v)) return false;
+  if (m.Knew[0] == 0.0 || m.Knew[4] == 0.0) return false;
+  for (int j = ncoef[m.kind]; j < 8; j++) if (m.D[j] != 0.0) return false;
+  bool any = false;
+  for (double v : m.R) any = any || v != 0.0;
+  return any;   // (all zero: a CameraInfo that was never filled in)
+}
+
+// plumb_bob with R exactly the identity: the hoisted statement of section 7b serves it (one division a column)
+static bool camera_model_general(const amdAprilTagsCameraModelEx_t& m) {
+  if (m.kind != AMDAT_DISTORTION_PLUMB_BOB) return true;
+  for (int j = 0; j < 9; j++) if (m.R[j] != (j % 4 == 0 ? 1.0 : 0.0)) return true;
+  return false;
+}
+
+// The kernels' parameters of a camera model: D[0 .. 4] in RectifyParams' k1, k2, p1, p2, k3 for every kind (the equidistant
+// projection reads its k1 .. k4 there), the rational denominator and the transpose of R (formed here, exactly) beside them.
+static void camera_model_params(const amdAprilTagsCameraModelEx_t& m, RectifyParams& R, CamGeneral& G) {
+  R = {m.K[0], m.K[4], m.K[2], m.K[5], m.D[0], m.D[1], m.D[2], m.D[3], m.D[4], m.Knew[0], m.Knew[4], m.Knew[2], m.Knew[5]};
+  G.general = camera_model_general(m) ? 1u : 0u;
+  G.kind = m.kind;
+  G.k4 = m.D[5]; G.k5 = m.D[6]; G.k6 = m.D[7];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) G.Ri[3 * r + c] = m.R[3 * c + r];
+}
+
+int amdAprilTagsDistortionFromName(const char* name) {
+  if (!name) return -1;
+  if (!strcmp(name, "plumb_bob")) return AMDAT_DISTORTION_PLUMB_BOB;
+  if (!strcmp(name, "rational_polynomial")) return AMDAT_DISTORTION_RATIONAL_POLYNOMIAL;
+  if (!strcmp(name, "equidistant")) return AMDAT_DISTORTION_EQUIDISTANT;
+  return -1;
+}
+
 int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModel_t* cams) {
-  if (!handle || handle->inflight.active || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  if (!handle || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  std::vector<amdAprilTagsCameraModelEx_t> ex(ncams);   // the Ex call with plumb_bob and R = I
   for (uint32_t c = 0; c < ncams; c++) {
-    for (double v : cams[c].K) if (!std::isfinite(v)) return AMDAT_INVALID_ARGUMENT;
-    for (double v : cams[c].D) if (!std::isfinite(v)) return AMDAT_INVALID_ARGUMENT;
-    for (double v : cams[c].Knew) if (!std::isfinite(v)) return AMDAT_INVALID_ARGUMENT;
-    if (cams[c].Knew[0] == 0.0 || cams[c].Knew[4] == 0.0) return AMDAT_INVALID_ARGUMENT;
+    ex[c] = {};
+    ex[c].kind = AMDAT_DISTORTION_PLUMB_BOB;
+    memcpy(ex[c].K, cams[c].K, sizeof ex[c].K);
+    memcpy(ex[c].D, cams[c].D, sizeof cams[c].D);
+    memcpy(ex[c].Knew, cams[c].Knew, sizeof ex[c].Knew);
+    ex[c].R[0] = ex[c].R[4] = ex[c].R[8] = 1.0;
+  }
+  return amdAprilTagsSetRectificationEx(handle, ncams, ncams ? ex.data() : nullptr);
+}
+
+int amdAprilTagsSetRectificationEx(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams) {
+  if (!handle || handle->inflight.active || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  bool general = false;
+  for (uint32_t c = 0; c < ncams; c++) {
+    if (!camera_model_ok(cams[c])) return AMDAT_INVALID_ARGUMENT;
+    general = general || camera_model_general(cams[c]);
   }
   const bool on = ncams > 0;
   if (on != !handle->rect_models.empty()) {
@@ -938,6 +995,7 @@ int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, cons
     drop_graphs(handle);   // captured with or without the rectification launch; the models themselves travel through the descriptors
   }
   handle->rect_models.assign(cams, cams + ncams);
+  handle->rect_general = general;   // (which of the two front kernels a submission launches: a launch parameter, like the models no graph's concern -- see enqueue_submission)
   return AMDAT_SUCCESS;
 }
 
@@ -1110,7 +1168,7 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
 static const amdAprilTagsImageInput_t* fill_rect(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
   const uint32_t ncams = (uint32_t)D->rect_models.size();
   for (uint32_t i = 0; i < n; i++) {
-    const amdAprilTagsCameraModel_t& m = D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)];   // (tools_hooks.h: i % ncams)
+    const amdAprilTagsCameraModelEx_t& m = D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)];   // (tools_hooks.h: i % ncams)
     RectDesc& r = D->h_rdesc[i];
     r.src = images[i].dev_ptr;
     r.src_pitch = (uint32_t)images[i].pitch;
@@ -1118,7 +1176,7 @@ static const amdAprilTagsImageInput_t* fill_rect(amdAprilTagsDetector_st* D, uin
     r.dst_pitch = (uint32_t)D->conv_pitch;
     r.fmt = fmt;
     r.W0 = (int32_t)images[i].width; r.H0 = (int32_t)images[i].height;
-    r.model = {m.K[0], m.K[4], m.K[2], m.K[5], m.D[0], m.D[1], m.D[2], m.D[3], m.D[4], m.Knew[0], m.Knew[4], m.Knew[2], m.Knew[5]};
+    camera_model_params(m, r.model, r.gen);
     D->rect_imgs[i] = images[i];
     D->rect_imgs[i].dev_ptr = r.dst;
     D->rect_imgs[i].pitch = D->conv_pitch;
@@ -1142,8 +1200,7 @@ static const amdAprilTagsImageInput_t* fill_resize(amdAprilTagsDetector_st* D, u
     z.DW = (int32_t)t.width; z.DH = (int32_t)t.height;
     z.rectify = ncams ? 1u : 0u;
     if (ncams) {
-      const amdAprilTagsCameraModel_t& m = D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)];
-      z.model = {m.K[0], m.K[4], m.K[2], m.K[5], m.D[0], m.D[1], m.D[2], m.D[3], m.D[4], m.Knew[0], m.Knew[4], m.Knew[2], m.Knew[5]};
+      camera_model_params(D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)], z.model, z.gen);
     }
     D->rect_imgs[i].width = t.width; D->rect_imgs[i].height = t.height;
     D->rect_imgs[i].dev_ptr = z.dst;
@@ -1372,11 +1429,15 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
   // resize: the same, at each slot's target size, through the rectification where that is on (in place of k_rectify_frames)
+  // Either way ONE front launch: where some camera of the handle is not plumb_bob with R = I, the kernel that also holds the general
+  // projection (it switches per slot, as on the encoding); otherwise today's, whose registers and occupancy stay what they were.
+  // (Which of the two is part of a captured graph's key: a change of models retires nothing.)
+  const bool general = D->rect_general && !D->rect_models.empty();
   if (resize)
-    hipLaunchKernelGGL(k_resize_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
+    hipLaunchKernelGGL(general ? k_resize_frames_general : k_resize_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
                        D->d_zdesc);
   else if (rect)
-    hipLaunchKernelGGL(k_rectify_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
+    hipLaunchKernelGGL(general ? k_rectify_frames_general : k_rectify_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
                        D->d_rdesc);
   mark();
   {
@@ -1471,7 +1532,7 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
   if (n <= 8 && !prof && D->path_mode != AMDAT_PATH_THROUGHPUT) {
     amdAprilTagsDetector_st::GraphEntry* hit = nullptr;
     for (auto& g : D->graphs)
-      if (g.exec && g.n == n && g.ostride == ostride && g.stream == s && g.fmt == fmt) hit = &g;
+      if (g.exec && g.n == n && g.ostride == ostride && g.stream == s && g.fmt == fmt && g.general == D->rect_general) hit = &g;
     if (hit) {
       D->graph_misses = 0;
       hit->last_use = ++D->graph_clock;
@@ -1493,7 +1554,7 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
       }
       if (ok) ok = hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess;
       if (graph) hipGraphDestroy(graph);
-      if (ok) { slot->n = n; slot->ostride = ostride; slot->fmt = fmt; slot->stream = s; slot->last_use = ++D->graph_clock; hit = slot; }
+      if (ok) { slot->n = n; slot->ostride = ostride; slot->fmt = fmt; slot->stream = s; slot->general = D->rect_general; slot->last_use = ++D->graph_clock; hit = slot; }
       else {
         // A capture can be invalidated from OUTSIDE the library: on this runtime a legacy-stream call of any other host thread on
         // the same device (a plain hipMemcpy) while this thread captures fails that call and poisons the capture, in every capture
@@ -1888,6 +1949,24 @@ int amdAprilTagsRectifyMono8(const uint8_t* src_dev, size_t src_pitch, uint8_t* 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_rectify_mono8, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, s, src_dev, src_pitch, dst_dev, dst_pitch,
                      (int)width, (int)height, R);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsRectifyMono8Ex(const uint8_t* src_dev, size_t src_pitch, uint8_t* dst_dev, size_t dst_pitch, uint32_t width,
+                               uint32_t height, const amdAprilTagsCameraModelEx_t* cam, amdAprilTagsStream stream) {
+  if (!src_dev || !dst_dev || !cam || width == 0 || height == 0 || src_pitch < width || dst_pitch < width || !camera_model_ok(*cam))
+    return AMDAT_INVALID_ARGUMENT;
+  RectifyParams R;
+  CamGeneral G;
+  camera_model_params(*cam, R, G);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((width + 63) / 64, (height + 3) / 4);
+  if (G.general)
+    hipLaunchKernelGGL(k_rectify_mono8_ex, grid, dim3(256), 0, s, src_dev, src_pitch, dst_dev, dst_pitch, (int)width, (int)height, R, G);
+  else
+    hipLaunchKernelGGL(k_rectify_mono8, grid, dim3(256), 0, s, src_dev, src_pitch, dst_dev, dst_pitch, (int)width, (int)height, R);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
   return AMDAT_SUCCESS;

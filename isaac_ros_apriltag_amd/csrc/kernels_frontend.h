@@ -4,6 +4,7 @@
 // integer fixed point so that the CPU oracle reproduces the bytes exactly.
 #pragma once
 #include "common.h"
+#include "camera_models.h"   // RectifyParams, and the general projection (three distortion models behind a rotation)
 
 // ---- the resize statement (oracle: ato_resize_mono8), stated once for k_resize_mono8 and k_resize_frames.
 // dst(x,y) = bilinear sample of src at ((x+0.5)*sw/dw - 0.5, (y+0.5)*sh/dh - 0.5), coordinates in 1/2048.  The position is the same
@@ -37,12 +38,6 @@ __global__ __launch_bounds__(256) void k_resize_mono8(const uint8_t* __restrict_
   dst[(size_t)y * dpitch + x] = (uint8_t)resize_blend(r0[px.i0], r0[px.i1], r1[px.i0], r1[px.i1], px.w, py.w);
 }
 
-struct RectifyParams {
-  double fx, fy, cx, cy;        // source camera K
-  double k1, k2, p1, p2, k3;    // plumb_bob
-  double nfx, nfy, ncx, ncy;    // destination (pinhole) camera
-};
-
 // ---- the rectification statement (oracle: ato_rectify_mono8), stated once for k_rectify_mono8 and k_rectify_frames.
 // The projection of destination pixel (x, y) is split where its operands allow: what depends on x alone, what on y alone, and the
 // rest.  Every operation below is the oracle's, on the oracle's operands, in the oracle's order (no re-association, and
@@ -69,6 +64,16 @@ __device__ __forceinline__ RectRow rect_row(int y, const RectifyParams& R) {
   r.tyy = 2.0 * r.yn * r.yn;
   return r;
 }
+// the bounds test, the 1/32-pixel position and the clamps of source position (u, v); false: outside the source (the pixel is 0)
+__device__ __forceinline__ bool rect_taps_at(double u, double v, int w, int h, RectTaps& t) {
+  if (!(u >= 0.0 && v >= 0.0 && u <= (double)(w - 1) && v <= (double)(h - 1))) return false;
+  const int fu = RECT_FIXED(u), fv = RECT_FIXED(v);  // 1/32 pixel (tools_hooks.h: (int)(u * 32.0 + 0.5))
+  t.x0 = fu >> 5; t.y0 = fv >> 5; t.wx = fu & 31; t.wy = fv & 31;
+  if (t.x0 >= w - 1) { t.x0 = w - 1; t.wx = 0; }
+  if (t.y0 >= h - 1) { t.y0 = h - 1; t.wy = 0; }
+  t.x1 = min(t.x0 + 1, w - 1); t.y1 = min(t.y0 + 1, h - 1);
+  return true;
+}
 // false: the pixel maps outside the source (its value is 0)
 __device__ __forceinline__ bool rect_taps(const RectCol& c, const RectRow& r, const RectifyParams& R, int w, int h, RectTaps& t) {
   // normalised pinhole ray of the destination pixel, then the plumb_bob model, then source pixels
@@ -78,13 +83,12 @@ __device__ __forceinline__ bool rect_taps(const RectCol& c, const RectRow& r, co
   const double xd = xn * radial + (c.p1x * yn + R.p2 * (r2 + c.txx));
   const double yd = yn * radial + (R.p1 * (r2 + r.tyy) + c.p2x * yn);
   const double u = R.fx * xd + R.cx, v = R.fy * yd + R.cy;
-  if (!(u >= 0.0 && v >= 0.0 && u <= (double)(w - 1) && v <= (double)(h - 1))) return false;
-  const int fu = RECT_FIXED(u), fv = RECT_FIXED(v);  // 1/32 pixel (tools_hooks.h: (int)(u * 32.0 + 0.5))
-  t.x0 = fu >> 5; t.y0 = fv >> 5; t.wx = fu & 31; t.wy = fv & 31;
-  if (t.x0 >= w - 1) { t.x0 = w - 1; t.wx = 0; }
-  if (t.y0 >= h - 1) { t.y0 = h - 1; t.wy = 0; }
-  t.x1 = min(t.x0 + 1, w - 1); t.y1 = min(t.y0 + 1, h - 1);
-  return true;
+  return rect_taps_at(u, v, w, h, t);
+}
+// the same for a camera of any kind behind a rotation (camera_models.h), x's and y's terms of its projection given
+__device__ __forceinline__ bool cam_taps(const CamCol& c, const CamRow& r, const RectifyParams& R, const CamGeneral& G, int w, int h, RectTaps& t) {
+  double u, v;
+  return cam_project(c, r, R, G, u, v) && rect_taps_at(u, v, w, h, t);
 }
 __device__ __forceinline__ uint32_t rect_blend(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, const RectTaps& t) {
   const uint32_t top = p00 * (32 - t.wx) + p01 * t.wx, bot = p10 * (32 - t.wx) + p11 * t.wx;
@@ -105,6 +109,43 @@ __global__ __launch_bounds__(256) void k_rectify_mono8(const uint8_t* __restrict
   dst[(size_t)y * dpitch + x] = out;
 }
 
+// The two statements behind one name, for the tile loops below: Proj<false> is the hoisted plumb_bob statement above (R the identity),
+// Proj<true> the general projection of camera_models.h.
+template <bool GEN> struct Proj;
+template <> struct Proj<false> {
+  typedef RectCol Col;
+  typedef RectRow Row;
+  static __device__ __forceinline__ Col col(int x, const RectifyParams& R, const CamGeneral&) { return rect_col(x, R); }
+  static __device__ __forceinline__ Row row(int y, const RectifyParams& R, const CamGeneral&) { return rect_row(y, R); }
+  static __device__ __forceinline__ bool taps(const Col& c, const Row& r, const RectifyParams& R, const CamGeneral&, int w, int h, RectTaps& t) {
+    return rect_taps(c, r, R, w, h, t);
+  }
+};
+template <> struct Proj<true> {
+  typedef CamCol Col;
+  typedef CamRow Row;
+  static __device__ __forceinline__ Col col(int x, const RectifyParams& R, const CamGeneral& G) { return cam_col(x, R, G); }
+  static __device__ __forceinline__ Row row(int y, const RectifyParams& R, const CamGeneral& G) { return cam_row(y, R, G); }
+  static __device__ __forceinline__ bool taps(const Col& c, const Row& r, const RectifyParams& R, const CamGeneral& G, int w, int h, RectTaps& t) {
+    return cam_taps(c, r, R, G, w, h, t);
+  }
+};
+
+// amdAprilTagsRectifyMono8Ex: k_rectify_mono8 with the general projection
+__global__ __launch_bounds__(256) void k_rectify_mono8_ex(const uint8_t* __restrict__ src, size_t spitch, uint8_t* __restrict__ dst,
+                                                          size_t dpitch, int w, int h, RectifyParams R, CamGeneral G) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= w || y >= h) return;
+  uint8_t out = 0;
+  RectTaps t;
+  if (cam_taps(cam_col(x, R, G), cam_row(y, R, G), R, G, w, h, t)) {
+    const uint8_t *r0 = src + (size_t)t.y0 * spitch, *r1 = src + (size_t)t.y1 * spitch;
+    out = (uint8_t)rect_blend(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t);
+  }
+  dst[(size_t)y * dpitch + x] = out;
+}
+
 // ---- rectification inside the submission (amdAprilTagsSetRectification) -----------------------------------------------------------------
 // One descriptor per batch slot, written by the host for every submission and uploaded by k_prologue beside the FrameDescs: the
 // caller's frame (mono8 or interleaved colour, any base address and pitch), its own size, its camera, and the slot of the handle's
@@ -117,6 +158,7 @@ struct RectDesc {
   int32_t W0, H0;
   uint32_t pad;
   RectifyParams model;
+  CamGeneral gen;        // gen.general: the slot's camera is not plumb_bob with R = I (k_rectify_frames_general switches on it, as on fmt)
 };
 static_assert(sizeof(RectDesc) % 4 == 0, "k_prologue copies RectDesc one word per thread");
 
@@ -137,30 +179,31 @@ __device__ __forceinline__ uint32_t rect_gray(Row row, int x) {
 
 // A block of 256 threads covers RF_BW x RF_BH output pixels of frame blockIdx.z: a wave is 256 pixels wide, a thread RF_PX
 // columns by RF_ROWS rows.  The taps are gathered through the cache (neighbouring lanes read neighbouring source bytes).
-template <int NCH, int RIDX, int BIDX>
+template <int NCH, int RIDX, int BIDX, bool GEN>
 __device__ __forceinline__ void rectify_frame_tile(const RectDesc& d) {
   const int w = d.W0, h = d.H0;
   const int x4 = (int)blockIdx.x * RF_BW + (int)(threadIdx.x & 63) * RF_PX;
   const int ya = (int)blockIdx.y * RF_BH + (int)(threadIdx.x >> 6) * RF_ROWS;
   if (x4 >= w || ya >= h) return;
   const RectifyParams& R = d.model;
+  const CamGeneral& G = d.gen;
   // (the descriptor's pointers are device memory: said so, the compiler addresses them as global, not flat)
   typedef __attribute__((address_space(1))) const uint8_t* GlobalSrc;
   typedef __attribute__((address_space(1))) uint32_t* GlobalDst;
   const GlobalSrc src = (GlobalSrc)d.src;
-  RectCol col[RF_PX];
+  typename Proj<GEN>::Col col[RF_PX];
 #pragma unroll
-  for (int k = 0; k < RF_PX; k++) col[k] = rect_col(x4 + k, R);   // (columns at or beyond w: computed, never sampled)
+  for (int k = 0; k < RF_PX; k++) col[k] = Proj<GEN>::col(x4 + k, R, G);   // (columns at or beyond w: computed, never sampled)
 #pragma unroll
   for (int j = 0; j < RF_ROWS; j++) {
     const int y = ya + j;
     if (y >= h) break;
-    const RectRow row = rect_row(y, R);
+    const typename Proj<GEN>::Row row = Proj<GEN>::row(y, R, G);
     uint32_t word = 0;
 #pragma unroll
     for (int k = 0; k < RF_PX; k++) {
       RectTaps t;
-      if (x4 + k < w && rect_taps(col[k], row, R, w, h, t)) {
+      if (x4 + k < w && Proj<GEN>::taps(col[k], row, R, G, w, h, t)) {
         const GlobalSrc r0 = src + (size_t)t.y0 * d.src_pitch, r1 = src + (size_t)t.y1 * d.src_pitch;
         const uint32_t g = rect_blend(rect_gray<NCH, RIDX, BIDX>(r0, t.x0), rect_gray<NCH, RIDX, BIDX>(r0, t.x1),
                                       rect_gray<NCH, RIDX, BIDX>(r1, t.x0), rect_gray<NCH, RIDX, BIDX>(r1, t.x1), t);
@@ -171,16 +214,31 @@ __device__ __forceinline__ void rectify_frame_tile(const RectDesc& d) {
   }
 }
 
+template <bool GEN>
+__device__ __forceinline__ void rectify_frame_fmt(const RectDesc& d) {
+  switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
+    case 0: rectify_frame_tile<1, 0, 0, GEN>(d); break;
+    case 1: rectify_frame_tile<3, 0, 2, GEN>(d); break;
+    case 2: rectify_frame_tile<3, 2, 0, GEN>(d); break;
+    case 3: rectify_frame_tile<4, 0, 2, GEN>(d); break;
+    default: rectify_frame_tile<4, 2, 0, GEN>(d); break;
+  }
+}
+
+// every slot's camera is plumb_bob with R = I
 __global__ __launch_bounds__(256) void k_rectify_frames(const RectDesc* __restrict__ descs) {
   const RectDesc& d = descs[blockIdx.z];
   if ((int)blockIdx.x * RF_BW >= d.W0 || (int)blockIdx.y * RF_BH >= d.H0) return;   // blocks beyond this frame's extent
-  switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
-    case 0: rectify_frame_tile<1, 0, 0>(d); break;
-    case 1: rectify_frame_tile<3, 0, 2>(d); break;
-    case 2: rectify_frame_tile<3, 2, 0>(d); break;
-    case 3: rectify_frame_tile<4, 0, 2>(d); break;
-    default: rectify_frame_tile<4, 2, 0>(d); break;
-  }
+  rectify_frame_fmt<false>(d);
+}
+
+// Some slot's camera is of another kind or has a rotation: the same launch, with the general projection for the slots that say so.
+// (A kernel of its own, chosen by the host per submission, so that k_rectify_frames keeps its registers and occupancy.)
+__global__ __launch_bounds__(256) void k_rectify_frames_general(const RectDesc* __restrict__ descs) {
+  const RectDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x * RF_BW >= d.W0 || (int)blockIdx.y * RF_BH >= d.H0) return;
+  if (d.gen.general) rectify_frame_fmt<true>(d);
+  else rectify_frame_fmt<false>(d);
 }
 
 // ---- resize inside the submission (amdAprilTagsSetResize), fused with the rectification where that is on -----------------------------
@@ -196,15 +254,16 @@ struct ResizeDesc {
   int32_t SW, SH, DW, DH;
   uint32_t rectify;      // 0: G = convert(frame); 1: G = rectify(convert(frame)) with `model`
   RectifyParams model;
+  CamGeneral gen;        // as in RectDesc
 };
 static_assert(sizeof(ResizeDesc) % 4 == 0, "k_prologue copies ResizeDesc one word per thread");
 
 // G(x, y) with rectification on, x's and y's terms of the projection given: the rectified value, 0 where it maps outside the source
-template <int NCH, int RIDX, int BIDX, class Src>
-__device__ __forceinline__ uint32_t rectified_gray(Src src, uint32_t pitch, const RectCol& c, const RectRow& r, const RectifyParams& R,
-                                                   int w, int h) {
+template <int NCH, int RIDX, int BIDX, bool GEN, class Src>
+__device__ __forceinline__ uint32_t rectified_gray(Src src, uint32_t pitch, const typename Proj<GEN>::Col& c, const typename Proj<GEN>::Row& r,
+                                                   const RectifyParams& R, const CamGeneral& G, int w, int h) {
   RectTaps t;
-  if (!rect_taps(c, r, R, w, h, t)) return 0u;
+  if (!Proj<GEN>::taps(c, r, R, G, w, h, t)) return 0u;
   const Src r0 = src + (size_t)t.y0 * pitch, r1 = src + (size_t)t.y1 * pitch;
   return rect_blend(rect_gray<NCH, RIDX, BIDX>(r0, t.x0), rect_gray<NCH, RIDX, BIDX>(r0, t.x1), rect_gray<NCH, RIDX, BIDX>(r1, t.x0),
                     rect_gray<NCH, RIDX, BIDX>(r1, t.x1), t);
@@ -213,22 +272,23 @@ __device__ __forceinline__ uint32_t rectified_gray(Src src, uint32_t pitch, cons
 // The thread shape of rectify_frame_tile: RF_PX adjacent output pixels by RF_ROWS rows, one dword store a row.  What depends on the
 // column alone -- the resize position, and with RECT the projection terms of its two source columns -- is formed once for the rows;
 // what depends on the row alone once for the pixels.
-template <int NCH, int RIDX, int BIDX, bool RECT>
+template <int NCH, int RIDX, int BIDX, bool RECT, bool GEN>
 __device__ __forceinline__ void resize_frame_tile(const ResizeDesc& d) {
   const int sw = d.SW, sh = d.SH, dw = d.DW, dh = d.DH;
   const int x4 = (int)blockIdx.x * RF_BW + (int)(threadIdx.x & 63) * RF_PX;
   const int ya = (int)blockIdx.y * RF_BH + (int)(threadIdx.x >> 6) * RF_ROWS;
   if (x4 >= dw || ya >= dh) return;
   const RectifyParams& R = d.model;
+  const CamGeneral& G = d.gen;
   typedef __attribute__((address_space(1))) const uint8_t* GlobalSrc;
   typedef __attribute__((address_space(1))) uint32_t* GlobalDst;
   const GlobalSrc src = (GlobalSrc)d.src;
   ResizePos px[RF_PX];
-  RectCol c0[RECT ? RF_PX : 1], c1[RECT ? RF_PX : 1];
+  typename Proj<GEN>::Col c0[RECT ? RF_PX : 1], c1[RECT ? RF_PX : 1];
 #pragma unroll
   for (int k = 0; k < RF_PX; k++) {
     px[k] = resize_pos(min(x4 + k, dw - 1), sw, dw);   // (columns at or beyond dw: the last column's, never stored)
-    if (RECT) { c0[k] = rect_col(px[k].i0, R); c1[k] = rect_col(px[k].i1, R); }
+    if (RECT) { c0[k] = Proj<GEN>::col(px[k].i0, R, G); c1[k] = Proj<GEN>::col(px[k].i1, R, G); }
   }
 #pragma unroll
   for (int j = 0; j < RF_ROWS; j++) {
@@ -237,14 +297,14 @@ __device__ __forceinline__ void resize_frame_tile(const ResizeDesc& d) {
     const ResizePos py = resize_pos(y, sh, dh);
     uint32_t word = 0;
     if (RECT) {
-      const RectRow r0 = rect_row(py.i0, R), r1 = rect_row(py.i1, R);
+      const typename Proj<GEN>::Row r0 = Proj<GEN>::row(py.i0, R, G), r1 = Proj<GEN>::row(py.i1, R, G);
 #pragma unroll
       for (int k = 0; k < RF_PX; k++) {
         if (x4 + k >= dw) break;
-        const uint32_t p00 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c0[k], r0, R, sw, sh);
-        const uint32_t p01 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c1[k], r0, R, sw, sh);
-        const uint32_t p10 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c0[k], r1, R, sw, sh);
-        const uint32_t p11 = rectified_gray<NCH, RIDX, BIDX>(src, d.src_pitch, c1[k], r1, R, sw, sh);
+        const uint32_t p00 = rectified_gray<NCH, RIDX, BIDX, GEN>(src, d.src_pitch, c0[k], r0, R, G, sw, sh);
+        const uint32_t p01 = rectified_gray<NCH, RIDX, BIDX, GEN>(src, d.src_pitch, c1[k], r0, R, G, sw, sh);
+        const uint32_t p10 = rectified_gray<NCH, RIDX, BIDX, GEN>(src, d.src_pitch, c0[k], r1, R, G, sw, sh);
+        const uint32_t p11 = rectified_gray<NCH, RIDX, BIDX, GEN>(src, d.src_pitch, c1[k], r1, R, G, sw, sh);
         word |= resize_blend(p00, p01, p10, p11, px[k].w, py.w) << (8 * k);
       }
     } else {
@@ -260,20 +320,29 @@ __device__ __forceinline__ void resize_frame_tile(const ResizeDesc& d) {
   }
 }
 
-template <bool RECT>
+template <bool RECT, bool GEN>
 __device__ __forceinline__ void resize_frame_fmt(const ResizeDesc& d) {
   switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
-    case 0: resize_frame_tile<1, 0, 0, RECT>(d); break;
-    case 1: resize_frame_tile<3, 0, 2, RECT>(d); break;
-    case 2: resize_frame_tile<3, 2, 0, RECT>(d); break;
-    case 3: resize_frame_tile<4, 0, 2, RECT>(d); break;
-    default: resize_frame_tile<4, 2, 0, RECT>(d); break;
+    case 0: resize_frame_tile<1, 0, 0, RECT, GEN>(d); break;
+    case 1: resize_frame_tile<3, 0, 2, RECT, GEN>(d); break;
+    case 2: resize_frame_tile<3, 2, 0, RECT, GEN>(d); break;
+    case 3: resize_frame_tile<4, 0, 2, RECT, GEN>(d); break;
+    default: resize_frame_tile<4, 2, 0, RECT, GEN>(d); break;
   }
 }
 
 __global__ __launch_bounds__(256) void k_resize_frames(const ResizeDesc* __restrict__ descs) {
   const ResizeDesc& d = descs[blockIdx.z];
   if ((int)blockIdx.x * RF_BW >= d.DW || (int)blockIdx.y * RF_BH >= d.DH) return;   // blocks beyond this frame's target extent
-  if (d.rectify) resize_frame_fmt<true>(d);
-  else resize_frame_fmt<false>(d);
+  if (d.rectify) resize_frame_fmt<true, false>(d);
+  else resize_frame_fmt<false, false>(d);
+}
+
+// as k_rectify_frames_general: chosen by the host when some slot's camera needs the general projection
+__global__ __launch_bounds__(256) void k_resize_frames_general(const ResizeDesc* __restrict__ descs) {
+  const ResizeDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x * RF_BW >= d.DW || (int)blockIdx.y * RF_BH >= d.DH) return;
+  if (d.rectify && d.gen.general) resize_frame_fmt<true, true>(d);
+  else if (d.rectify) resize_frame_fmt<true, false>(d);
+  else resize_frame_fmt<false, false>(d);
 }

@@ -46,6 +46,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetPerFrameSizes) set_per_frame_sizes = nullptr;
   decltype(&amdAprilTagsSetRectification) set_rectification = nullptr;
   decltype(&amdAprilTagsSetResize) set_resize = nullptr;
+  decltype(&amdAprilTagsSetRectificationEx) set_rectification_ex = nullptr;
 };
 
 DetectorApi& api() {
@@ -84,6 +85,7 @@ DetectorApi& api() {
   BIND(set_per_frame_sizes, "amdAprilTagsSetPerFrameSizes")
   BIND(set_rectification, "amdAprilTagsSetRectification")
   BIND(set_resize, "amdAprilTagsSetResize")
+  BIND(set_rectification_ex, "amdAprilTagsSetRectificationEx")
 #undef BIND
   return a;
 }
@@ -107,13 +109,52 @@ amdAprilTagsCameraModel_t to_abi(const CameraModel& m) {
   return o;
 }
 
+amdAprilTagsCameraModelEx_t to_abi(const CameraModelEx& m) {
+  amdAprilTagsCameraModelEx_t o = {};
+  o.kind = m.kind;
+  for (int i = 0; i < 9; i++) { o.K[i] = m.k[i]; o.R[i] = m.r[i]; o.Knew[i] = m.knew[i]; }
+  for (int i = 0; i < 8; i++) o.D[i] = m.d[i];
+  return o;
+}
+
+bool rectifying(const NodeOptions& opt) { return opt.rectify || opt.rectify_full; }
+
+// The model of a stream's CameraInfo under the options: RectificationModelEx with rectify_full, otherwise RectificationModel (plumb_bob
+// alone, no rotation) in the same form.  Throws what they throw.
+CameraModelEx stream_model(const NodeOptions& opt, const CameraInfo& info) {
+  if (opt.rectify_full) return RectificationModelEx(info);
+  const CameraModel m = RectificationModel(info);
+  CameraModelEx e;
+  e.k = m.k; e.knew = m.knew;
+  for (int i = 0; i < 5; i++) e.d[i] = m.d[i];
+  e.r = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  return e;
+}
+
+// n models to the handle: the Ex call with rectify_full, the plumb_bob call otherwise (as before there was another)
+int apply_models(amdAprilTagsHandle detector, const NodeOptions& opt, const CameraModelEx* models, uint32_t n) {
+  if (opt.rectify_full) {
+    std::vector<amdAprilTagsCameraModelEx_t> abi(n);
+    for (uint32_t i = 0; i < n; i++) abi[i] = to_abi(models[i]);
+    return api().set_rectification_ex(detector, n, abi.data());
+  }
+  std::vector<amdAprilTagsCameraModel_t> abi(n);
+  for (uint32_t i = 0; i < n; i++) {
+    CameraModel m;
+    m.k = models[i].k; m.knew = models[i].knew;
+    for (int j = 0; j < 5; j++) m.d[j] = models[i].d[j];
+    abi[i] = to_abi(m);
+  }
+  return api().set_rectification(detector, n, abi.data());
+}
+
 bool resizing(const NodeOptions& opt) { return opt.resize_width != 0 && opt.resize_height != 0; }
 
 // The camera matrix the pose is computed with: Knew of the stream's model with NodeOptions::rectify, K otherwise -- and with
 // NodeOptions::resize_width x resize_height that camera scaled to the resized image (image_proc's convention: the first row times
 // resize_width / width, the second times resize_height / height).
 std::array<double, 9> pose_camera(const NodeOptions& opt, const CameraInfo& info) {
-  std::array<double, 9> k = opt.rectify ? RectificationModel(info).knew : info.k;
+  std::array<double, 9> k = rectifying(opt) ? stream_model(opt, info).knew : info.k;
   if (resizing(opt) && info.width != 0 && info.height != 0) {
     for (int c = 0; c < 3; c++) {
       k[c] = k[c] * static_cast<double>(opt.resize_width) / static_cast<double>(info.width);
@@ -273,6 +314,35 @@ CameraModel RectificationModel(const CameraInfo& info) {
   return m;
 }
 
+CameraModelEx RectificationModelEx(const CameraInfo& info) {
+  static const char* const names[3] = {"plumb_bob", "rational_polynomial", "equidistant"};
+  static const size_t ncoef[3] = {5, 8, 4};
+  CameraModelEx m;
+  const std::string& name = info.distortion_model;
+  if (name.empty() || name == names[0]) m.kind = 0;
+  else if (name == names[1]) m.kind = 1;
+  else if (name == names[2]) m.kind = 2;
+  else
+    throw std::runtime_error("'rectify_full' supports the distortion models 'plumb_bob', 'rational_polynomial' and 'equidistant', not '" +
+                             name + "'");
+  if (info.d.size() > ncoef[m.kind])
+    throw std::runtime_error(std::string("'rectify_full': '") + names[m.kind] + "' has " + std::to_string(ncoef[m.kind]) +
+                             " coefficients, camera_info carries " + std::to_string(info.d.size()));
+  m.k = info.k;
+  for (size_t i = 0; i < info.d.size(); i++) m.d[i] = info.d[i];
+  bool filled = false;
+  for (double v : info.r) filled = filled || v != 0.0;
+  if (filled) m.r = info.r;
+  else m.r = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // a monocular driver leaves r at zero
+  if (info.p[0] != 0.0) {
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) m.knew[r * 3 + c] = info.p[r * 4 + c];
+  } else {
+    m.knew = info.k;
+  }
+  return m;
+}
+
 struct AprilTagNode::Impl {
   NodeOptions opt;
   DetectionsCallback on_detections;
@@ -315,9 +385,9 @@ struct AprilTagNode::Impl {
       throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
     }
     apply_quad_sigma(detector, opt.quad_sigma);
-    if (opt.rectify) {
-      const amdAprilTagsCameraModel_t model = to_abi(RectificationModel(info));
-      const int rerr = api().set_rectification(detector, 1, &model);
+    if (rectifying(opt)) {
+      const CameraModelEx model = stream_model(opt, info);
+      const int rerr = apply_models(detector, opt, &model, 1);
       if (rerr != 0) throw std::runtime_error("'rectify': camera model refused (error code " + std::to_string(rerr) + ")");
     }
     apply_resize(detector, opt);
@@ -444,7 +514,7 @@ struct AprilTagMultiCameraNode::Impl {
   // dev, pitch: where the staged mono8 frame lies -- the stream's slot of d_mono, or with NodeOptions::resize_width x resize_height,
   // where a frame may be larger than the handle, a buffer of the slot's own (own, own_bytes) that grows with the frames
   struct Slot {
-    bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; CameraModel model;
+    bool pending = false; Header info_header; std::array<double, 9> k{}; uint32_t width = 0, height = 0; CameraModelEx model;
     uint8_t* dev = nullptr; size_t pitch = 0; void* own = nullptr; size_t own_bytes = 0;
   };
   std::vector<Slot> slots;
@@ -578,8 +648,8 @@ bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& 
   if (stream >= impl_->S) throw std::runtime_error("stream index out of range");
   if (image.header.stamp.sec != camera_info.header.stamp.sec || image.header.stamp.nanosec != camera_info.header.stamp.nanosec)
     return false;  // ExactTime synchroniser would not fire
-  CameraModel model;
-  if (impl_->opt.rectify) model = RectificationModel(camera_info);   // (throws before anything is staged)
+  CameraModelEx model;
+  if (rectifying(impl_->opt)) model = stream_model(impl_->opt, camera_info);   // (throws before anything is staged)
   if (!impl_->initialized) impl_->Initialize(camera_info);
   Impl::Slot& sl = impl_->slots[stream];
   // the slot's device image is about to be overwritten: a frame staged earlier and not yet submitted is gone either way,
@@ -625,10 +695,10 @@ uint32_t AprilTagMultiCameraNode::Flush() {
       return 0;
     }
   }
-  if (I.opt.rectify) {   // the models of the streams of this round, in slot order (host state of the handle: no device work)
-    std::vector<amdAprilTagsCameraModel_t> models(n);
-    for (uint32_t i = 0; i < n; i++) models[i] = to_abi(I.slots[who[i]].model);
-    const int rerr = api().set_rectification(I.detector, n, models.data());
+  if (rectifying(I.opt)) {   // the models of the streams of this round, in slot order (host state of the handle: no device work)
+    std::vector<CameraModelEx> models(n);
+    for (uint32_t i = 0; i < n; i++) models[i] = I.slots[who[i]].model;
+    const int rerr = apply_models(I.detector, I.opt, models.data(), n);
     if (rerr != 0) {   // (a round whose models were refused must not run with stale ones)
       std::fprintf(stderr, "[apriltag_node] per-stream camera models refused (error code %d): round dropped\n", rerr);
       for (uint32_t s : who) I.slots[s].pending = false;
@@ -684,10 +754,37 @@ struct NodeShellDetection {
 extern "C" {
 
 // sensor_msgs/CameraInfo's D, distortion_model and P through the flat view (null / 0: left empty)
-static void fill_camera_info_extras(CameraInfo* info, const double* d, int nd, const char* distortion_model, const double* p12) {
+static void fill_camera_info_extras(CameraInfo* info, const double* d, int nd, const char* distortion_model, const double* p12,
+                                    const double* r9 = nullptr) {
   if (d && nd > 0) info->d.assign(d, d + nd);
   if (distortion_model) info->distortion_model = distortion_model;
   if (p12) for (int i = 0; i < 12; i++) info->p[i] = p12[i];
+  if (r9) for (int i = 0; i < 9; i++) info->r[i] = r9[i];
+}
+
+// the flat value of `rectify`: 0 off, 1 NodeOptions::rectify, 2 NodeOptions::rectify_full
+static void set_rectify_option(NodeOptions* o, int rectify) {
+  o->rectify = rectify == 1;
+  o->rectify_full = rectify == 2;
+}
+
+// RectificationModelEx of a CameraInfo with these fields: out36 = kind, K[9], D[8], R[9], Knew[9].  0, or -2 with the exception's text.
+// (host only: loads no detector library)
+int node_shell_camera_model_ex(const double* k9, const double* d, int nd, const char* distortion_model, const double* p12,
+                               const double* r9, double* out36, char* err, size_t err_len) {
+  try {
+    CameraInfo info;
+    for (int i = 0; i < 9; i++) info.k[i] = k9[i];
+    fill_camera_info_extras(&info, d, nd, distortion_model, p12, r9);
+    const amd::isaac_ros::apriltag::CameraModelEx m = amd::isaac_ros::apriltag::RectificationModelEx(info);
+    out36[0] = static_cast<double>(m.kind);
+    for (int i = 0; i < 9; i++) { out36[1 + i] = m.k[i]; out36[18 + i] = m.r[i]; out36[27 + i] = m.knew[i]; }
+    for (int i = 0; i < 8; i++) out36[10 + i] = m.d[i];
+    return 0;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return -2;
+  }
 }
 
 // RectificationModel of a CameraInfo with these fields: out23 = K[9], D[5], Knew[9].  0, or -2 with the exception's text in err.
@@ -718,7 +815,7 @@ NodeShellHarness* node_shell_create_opts(int max_tags, double size, int tile_siz
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     o.strict_cuapriltags_encodings = strict_cuapriltags_encodings != 0;
     o.quad_sigma = quad_sigma;
-    o.rectify = rectify != 0;
+    set_rectify_option(&o, rectify);
     o.resize_width = resize_width; o.resize_height = resize_height;
     auto* h = new NodeShellHarness();
     h->node.reset(new AprilTagNode(o));
@@ -753,10 +850,10 @@ void node_shell_destroy(NodeShellHarness* h) { delete h; }
 
 // Feeds one image + camera_info pair.  Returns the number of detections published, -1 if the stamps
 // differ (no callback), -2 on an exception (message in err).
-// (d, nd, distortion_model, p12: the CameraInfo fields NodeOptions::rectify reads)
-int node_shell_on_frame_info(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
+// (d, nd, distortion_model, p12, r9: the CameraInfo fields NodeOptions::rectify and rectify_full read)
+int node_shell_on_frame_full(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
                              uint32_t height, uint32_t step, const double* k9, const double* d, int nd, const char* distortion_model,
-                             const double* p12, const char* frame_id, int32_t sec, uint32_t nanosec, int32_t info_sec,
+                             const double* p12, const double* r9, const char* frame_id, int32_t sec, uint32_t nanosec, int32_t info_sec,
                              uint32_t info_nanosec, NodeShellDetection* out, int max_out, char* out_frame_id, size_t frame_id_len,
                              char* err, size_t err_len) {
   try {
@@ -767,7 +864,7 @@ int node_shell_on_frame_info(NodeShellHarness* h, const uint8_t* data, int is_de
     info.header.frame_id = frame_id; info.header.stamp.sec = info_sec; info.header.stamp.nanosec = info_nanosec;
     info.width = width; info.height = height;
     for (int i = 0; i < 9; i++) info.k[i] = k9[i];
-    fill_camera_info_extras(&info, d, nd, distortion_model, p12);
+    fill_camera_info_extras(&info, d, nd, distortion_model, p12, r9);
     const int before = h->publishes;
     if (!h->node->CameraImageCallback(img, info)) return -1;
     if (h->publishes == before) return 0;  // frame dropped
@@ -792,6 +889,15 @@ int node_shell_on_frame_info(NodeShellHarness* h, const uint8_t* data, int is_de
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return -2;
   }
+}
+
+int node_shell_on_frame_info(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
+                             uint32_t height, uint32_t step, const double* k9, const double* d, int nd, const char* distortion_model,
+                             const double* p12, const char* frame_id, int32_t sec, uint32_t nanosec, int32_t info_sec,
+                             uint32_t info_nanosec, NodeShellDetection* out, int max_out, char* out_frame_id, size_t frame_id_len,
+                             char* err, size_t err_len) {
+  return node_shell_on_frame_full(h, data, is_device, encoding, width, height, step, k9, d, nd, distortion_model, p12, nullptr, frame_id,
+                                  sec, nanosec, info_sec, info_nanosec, out, max_out, out_frame_id, frame_id_len, err, err_len);
 }
 
 int node_shell_on_frame(NodeShellHarness* h, const uint8_t* data, int is_device, const char* encoding, uint32_t width,
@@ -821,7 +927,7 @@ MultiShellHarness* node_shell_multi_create_opts(int num_streams, int max_tags, d
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     o.quad_sigma = quad_sigma;
     o.max_width = max_width; o.max_height = max_height;
-    o.rectify = rectify != 0;
+    set_rectify_option(&o, rectify);
     o.resize_width = resize_width; o.resize_height = resize_height;
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
@@ -858,10 +964,10 @@ MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double
 void node_shell_multi_destroy(MultiShellHarness* h) { delete h; }
 
 // 1 staged, 0 not (stamps differ / dropped), -2 exception
-int node_shell_multi_on_frame_info(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding,
+int node_shell_multi_on_frame_full(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding,
                                    uint32_t width, uint32_t height, uint32_t step, const double* k9, const double* d, int nd,
-                                   const char* distortion_model, const double* p12, const char* frame_id, int32_t sec, uint32_t nanosec,
-                                   int32_t info_sec, uint32_t info_nanosec, char* err, size_t err_len) {
+                                   const char* distortion_model, const double* p12, const double* r9, const char* frame_id, int32_t sec,
+                                   uint32_t nanosec, int32_t info_sec, uint32_t info_nanosec, char* err, size_t err_len) {
   try {
     Image img;
     img.header.frame_id = "image_frame"; img.header.stamp.sec = sec; img.header.stamp.nanosec = nanosec;
@@ -870,12 +976,20 @@ int node_shell_multi_on_frame_info(MultiShellHarness* h, int stream, const uint8
     info.header.frame_id = frame_id; info.header.stamp.sec = info_sec; info.header.stamp.nanosec = info_nanosec;
     info.width = width; info.height = height;
     for (int i = 0; i < 9; i++) info.k[i] = k9[i];
-    fill_camera_info_extras(&info, d, nd, distortion_model, p12);
+    fill_camera_info_extras(&info, d, nd, distortion_model, p12, r9);
     return h->node->CameraImageCallback(static_cast<uint32_t>(stream), img, info) ? 1 : 0;
   } catch (const std::exception& e) {
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return -2;
   }
+}
+
+int node_shell_multi_on_frame_info(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding,
+                                   uint32_t width, uint32_t height, uint32_t step, const double* k9, const double* d, int nd,
+                                   const char* distortion_model, const double* p12, const char* frame_id, int32_t sec, uint32_t nanosec,
+                                   int32_t info_sec, uint32_t info_nanosec, char* err, size_t err_len) {
+  return node_shell_multi_on_frame_full(h, stream, data, is_device, encoding, width, height, step, k9, d, nd, distortion_model, p12,
+                                        nullptr, frame_id, sec, nanosec, info_sec, info_nanosec, err, err_len);
 }
 
 int node_shell_multi_on_frame(MultiShellHarness* h, int stream, const uint8_t* data, int is_device, const char* encoding, uint32_t width,

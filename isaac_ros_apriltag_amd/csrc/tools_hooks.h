@@ -34,13 +34,17 @@
 //                           11 = the resize statement (kernels_frontend.h: resize_pos) without the half-pixel term: the source
 //                               position (2i * sn * 1024) / dn instead of ((2i + 1) * sn * 1024) / dn - 1024 (indices clamped as before)
 //                           12 = amdAprilTagsSetResize: every frame of a submission takes sizes[0] instead of sizes[i % nsizes]
-//                           (4 .. 12 change values only: no address, index bound, launch size or loop count)
+//                           13 = the general projection (camera_models.h) takes the identity for the transpose of the rectification
+//                               rotation: a camera with R is rectified as if it had none
+//                           14 = the general projection takes 1 for the denominator of rational_polynomial's radial factor: k4 .. k6 are ignored
+//                           (4 .. 14 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
 //                           tests/test_fit_classes_gpu.py::test_fit_class_tests_fail_on_the_wrong_builds for 7 and 8,
 //                           tests/test_rectify_submission_gpu.py::test_the_rectify_tests_fail_on_the_wrong_builds for 9 and 10,
-//                           tests/test_resize_submission_gpu.py::test_the_resize_tests_fail_on_the_wrong_builds for 11 and 12)
+//                           tests/test_resize_submission_gpu.py::test_the_resize_tests_fail_on_the_wrong_builds for 11 and 12,
+//                           tests/test_camera_models_gpu.py::test_the_camera_model_tests_fail_on_the_wrong_builds for 13 and 14)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -82,6 +86,18 @@
 #define RECT_MODEL_OF_SLOT(i, ncams) ((void)(i), (void)(ncams), 0u)
 #else
 #define RECT_MODEL_OF_SLOT(i, ncams) ((i) % (ncams))
+#endif
+
+// ---- the general projection: entry j of the transposed rectification rotation, and the rational model's denominator -------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 13
+#define CAM_RI(Ri, j) ((void)(Ri), ((j) % 4 == 0 ? 1.0 : 0.0))
+#else
+#define CAM_RI(Ri, j) ((Ri)[j])
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 14
+#define CAM_RATIONAL_DEN(den) ((void)(den), 1.0)
+#else
+#define CAM_RATIONAL_DEN(den) (den)
 #endif
 
 // ---- resize: the source position in 1/2048 pixel of destination index i, and the target size of batch slot i -------------------------

@@ -104,9 +104,16 @@ class AprilTagDetector:
         self.per_frame_sizes = bool(enable)
 
     def set_rectification(self, models):
-        """amdAprilTagsSetRectification: models is a list of (K, D, Knew) -- frame i of every following submission is undistorted with
-        models[i % len(models)] inside the submission and detected there; None or [] turns it off.  The pose intrinsics stay the
-        caller's: pass Knew's fx, fy, cx, cy."""
+        """amdAprilTagsSetRectification[Ex]: models is a list of (K, D, Knew) -- a plumb_bob camera -- or (K, D, Knew, model_name, R)
+        with model_name "plumb_bob", "rational_polynomial" or "equidistant" and R the CameraInfo's rectification rotation (None: the
+        identity).  Frame i of every following submission is undistorted with models[i % len(models)] inside the submission and
+        detected there; None or [] turns it off.  The pose intrinsics stay the caller's: pass Knew's fx, fy, cx, cy (R does not enter
+        the pose: it is reported in the rectified camera's frame).  A list of 3-tuples alone goes through amdAprilTagsSetRectification."""
+        models = list(models or [])
+        if any(len(m) != 3 for m in models):
+            arr = capi.camera_models_ex(models)
+            capi._check("amdAprilTagsSetRectificationEx", self._L.amdAprilTagsSetRectificationEx(self._h, len(arr), arr))
+            return
         arr = capi.camera_models(models)
         capi._check("amdAprilTagsSetRectification", self._L.amdAprilTagsSetRectification(self._h, len(arr) if arr is not None else 0, arr))
 

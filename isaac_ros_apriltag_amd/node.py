@@ -38,6 +38,19 @@ def lib():
         L.node_shell_camera_model.restype = C.c_int
         L.node_shell_camera_model.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+        L.node_shell_camera_model_ex.restype = C.c_int
+        L.node_shell_camera_model_ex.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+        L.node_shell_on_frame_full.restype = C.c_int
+        L.node_shell_on_frame_full.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.c_char_p, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32,
+                                               C.POINTER(ShellDetection), C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_on_frame_full.restype = C.c_int
+        L.node_shell_multi_on_frame_full.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32,
+                                                     C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p,
+                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_int32, C.c_uint32,
+                                                     C.c_int32, C.c_uint32, C.c_char_p, C.c_size_t]
         L.node_shell_destroy.argtypes = [C.c_void_p]
         L.node_shell_on_frame_info.restype = C.c_int
         L.node_shell_on_frame_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -111,6 +124,36 @@ def camera_model(K9, D=None, distortion_model=None, P12=None):
     return v[:9], v[9:14], v[14:]
 
 
+def _rotation(R):
+    """sensor_msgs/CameraInfo's R, 3 x 3 or nine values (None: left all zero, as a monocular driver leaves it)."""
+    if R is None:
+        return None
+    flat = [float(v) for row in R for v in row] if len(R) == 3 else [float(v) for v in R]
+    return (C.c_double * 9)(*flat)
+
+
+def _rectify_flag(rectify):
+    """NodeOptions::rectify / rectify_full as the flat view takes them: False 0, True 1, "full" 2."""
+    if rectify == "full":
+        return 2
+    if isinstance(rectify, str):
+        raise ValueError("rectify is False, True or \"full\"")
+    return 1 if rectify else 0
+
+
+def camera_model_ex(K9, D=None, distortion_model=None, P12=None, R=None):
+    """RectificationModelEx (include/apriltag_node_shell.hpp) of a CameraInfo with these fields: (kind, K[9], D[8], R[9], Knew[9]).
+    Raises RuntimeError with the shell's text for a model NodeOptions::rectify_full does not take.  Host only."""
+    k = (C.c_double * 9)(*[float(v) for v in K9])
+    d, nd, m, p = _info_extras(D, distortion_model, P12)
+    out = (C.c_double * 36)()
+    err = C.create_string_buffer(1024)
+    if lib().node_shell_camera_model_ex(k, d, nd, m, p, _rotation(R), out, err, 1024) != 0:
+        raise RuntimeError(err.value.decode())
+    v = list(out)
+    return int(v[0]), v[1:10], v[10:18], v[18:27], v[27:]
+
+
 class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
@@ -118,7 +161,8 @@ class AprilTagMultiCameraNode:
                  auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
-        undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12).  resize
+        undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
+        (NodeOptions::rectify_full): with any of the three distortion models and the rotation R of its CameraInfo.  resize
         (NodeOptions::resize_width, resize_height): (w, h) -- frames of any size are resized to it inside the submission, behind the
         rectification, and the pose is computed with the scaled camera."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
@@ -126,7 +170,7 @@ class AprilTagMultiCameraNode:
         self._L = lib()
         self._h = self._L.node_shell_multi_create_opts(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
                                                        decimate, 1 if auto_flush else 0, float(quad_sigma), int(max_width),
-                                                       int(max_height), 1 if rectify else 0, rw, rh, err, 1024)
+                                                       int(max_height), _rectify_flag(rectify), rw, rh, err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
         self.max_tags, self.num_streams = max_tags, num_streams
@@ -143,14 +187,14 @@ class AprilTagMultiCameraNode:
             pass
 
     def on_frame(self, stream, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0), info_stamp=None,
-                 D=None, distortion_model=None, P12=None):
+                 D=None, distortion_model=None, P12=None, R=None):
         info_stamp = stamp if info_stamp is None else info_stamp
         err = C.create_string_buffer(1024)
         k = (C.c_double * 9)(*[float(v) for v in K9])
         d, nd, m, p = _info_extras(D, distortion_model, P12)
-        rc = self._L.node_shell_multi_on_frame_info(self._h, stream, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step,
-                                                    k, d, nd, m, p, frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1],
-                                                    err, 1024)
+        rc = self._L.node_shell_multi_on_frame_full(self._h, stream, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step,
+                                                    k, d, nd, m, p, _rotation(R), frame_id.encode(), stamp[0], stamp[1], info_stamp[0],
+                                                    info_stamp[1], err, 1024)
         if rc == -2:
             raise RuntimeError(err.value.decode())
         return rc == 1
@@ -177,14 +221,15 @@ class AprilTagNode:
                  strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None):
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
-        (on_frame: D, distortion_model, P12), and the pose is computed with Knew.  resize (NodeOptions::resize_width, resize_height):
+        (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
+        three distortion models and the rotation R of that CameraInfo.  resize (NodeOptions::resize_width, resize_height):
         (w, h) -- the handle has that size, frames of any size are resized to it inside the submission, behind the rectification, and
         the pose is computed with the camera scaled by w / width and h / height."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self._h = self._L.node_shell_create_opts(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
-                                                 1 if strict_cuapriltags_encodings else 0, float(quad_sigma), 1 if rectify else 0,
+                                                 1 if strict_cuapriltags_encodings else 0, float(quad_sigma), _rectify_flag(rectify),
                                                  rw, rh, err, 1024)
         if not self._h:
             raise RuntimeError(err.value.decode())
@@ -202,15 +247,15 @@ class AprilTagNode:
             pass
 
     def on_frame(self, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0),
-                 info_stamp=None, D=None, distortion_model=None, P12=None):
+                 info_stamp=None, D=None, distortion_model=None, P12=None, R=None):
         info_stamp = stamp if info_stamp is None else info_stamp
         out = (ShellDetection * self.max_tags)()
         fid = C.create_string_buffer(128)
         err = C.create_string_buffer(1024)
         k = (C.c_double * 9)(*[float(v) for v in K9])
         d, nd, m, p = _info_extras(D, distortion_model, P12)
-        n = self._L.node_shell_on_frame_info(self._h, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step, k,
-                                             d, nd, m, p, frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1], out,
+        n = self._L.node_shell_on_frame_full(self._h, data_ptr, 1 if is_device else 0, encoding.encode(), width, height, step, k,
+                                             d, nd, m, p, _rotation(R), frame_id.encode(), stamp[0], stamp[1], info_stamp[0], info_stamp[1], out,
                                              self.max_tags, fid, 128, err, 1024)
         if n == -2:
             raise RuntimeError(err.value.decode())

@@ -51,6 +51,9 @@ public:
     // the image topic is the camera's distorted image: undistorted inside the detector's submission with camera_info's plumb_bob model
     // (K, D; the rectified camera is the left 3x3 of P), in place of a RectifyNode in front of this one
     opt.rectify = declare_parameter<bool>("rectify", false);
+    // the same for every camera camera_info describes: plumb_bob, rational_polynomial or equidistant, behind its rectification
+    // rotation R (either half of a stereo pair)
+    opt.rectify_full = declare_parameter<bool>("rectify_full", false);
     // both set: every frame, whatever its size, is resized to resize_width x resize_height inside the detector's submission (behind the
     // rectification), in place of a ResizeNode in front of this one; the pose uses the camera scaled to that size.  0: off
     opt.resize_width = static_cast<uint32_t>(declare_parameter<int>("resize_width", 0));
@@ -133,6 +136,7 @@ private:
     for (int i = 0; i < 9; i++) {info.k[i] = camera_info->k[i];}
     info.d = camera_info->d;
     info.distortion_model = camera_info->distortion_model;
+    for (int i = 0; i < 9; i++) {info.r[i] = camera_info->r[i];}
     for (int i = 0; i < 12; i++) {info.p[i] = camera_info->p[i];}
     last_info_header_ = camera_info->header;  // output headers = camera_info header (reference :501,:534)
     impl_->CameraImageCallback(img, info);

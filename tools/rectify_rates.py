@@ -4,6 +4,8 @@
             plain     the unrectified submission (the same on a commit without amdAprilTagsSetRectification: the tool then runs
                       this form and the two-step form only)
             in-sub    amdAprilTagsSetRectification with n cameras, one DetectBatch[Color]Ex
+            in-sub <camera>   the same through amdAprilTagsSetRectificationEx (k_rectify_frames_general), n cameras of one kind:
+                      plumb_bob+R, rational, rational+R, equidistant, equidistant+R (--cameras; R a small stereo-like rotation)
             two-step  per frame amdAprilTagsRectifyMono8 on the caller's stream into a host-owned plane (bgr8: amdAprilTagsConvertToMono8
                       into a second host-owned plane first), then one mono8 DetectBatchEx on a handle without rectification
           Host clock around calls that end in a stream wait; the median of --steps steps each, with the minimum and the quartiles.
@@ -37,6 +39,34 @@ def model():
     Kn[0, 2] += 6.5
     Kn[1, 2] -= 4.25
     return K, DA, Kn
+
+
+D_RATIONAL = [0.35, -0.12, 0.0005, -0.0007, 0.02, 0.42, -0.05, 0.01]
+D_FISHEYE = [-0.03, 0.004, -0.0006, 0.0001]
+CAMERAS = ("plumb_bob+R", "rational", "rational+R", "equidistant", "equidistant+R")
+
+
+def rotation(rx=0.01, ry=-0.015, rz=0.004):
+    cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
+    return (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1.0]]) @ np.array([[cy, 0, sy], [0, 1.0, 0], [-sy, 0, cy]]) @
+            np.array([[1.0, 0, 0], [0, cx, -sx], [0, sx, cx]]))
+
+
+def model_ex(name):
+    """(K, D, Knew, model_name, R) of one of CAMERAS: the cameras of tests/camera_models_ref.py."""
+    K, D, Kn = model()
+    kind = name.split("+")[0]
+    if kind == "rational":
+        D = D_RATIONAL
+    elif kind == "equidistant":
+        D = D_FISHEYE
+        Kn = K.copy()
+        Kn[0, 0] *= 0.7
+        Kn[1, 1] *= 0.7
+        Kn[0, 2] += 6.5
+        Kn[1, 2] -= 4.25
+    full = {"plumb_bob": "plumb_bob", "rational": "rational_polynomial", "equidistant": "equidistant"}[kind]
+    return K, D, Kn, full, (rotation() if name.endswith("+R") else None)
 
 
 def frames(n, encoding, distinct=8, seed=1234):
@@ -80,6 +110,12 @@ def step_mode(args):
                 rect = AprilTagDetector(W, H, intrinsics=k4(Kn), max_batch=n, rectification=[(K, D, Kn)] * n)
                 p_rect = rect.prepare(batch, max_dets=64, intrinsics=intr, encoding=enc)
                 forms["in-sub"] = lambda: rect.run_prepared(p_rect)
+            general = []
+            for cam in (args.cameras if have else ()):
+                det = AprilTagDetector(W, H, intrinsics=k4(Kn), max_batch=n, rectification=[model_ex(cam)] * n)
+                prep = det.prepare(batch, max_dets=64, intrinsics=[k4(model_ex(cam)[2])] * n, encoding=enc)
+                forms["in-sub " + cam] = lambda det=det, prep=prep: det.run_prepared(prep)
+                general.append(det)
             times = {f: [] for f in forms}
             for f in forms.values():   # warm every form: code objects, graphs, planes
                 f()
@@ -93,13 +129,14 @@ def step_mode(args):
             for name in forms:
                 t = np.array(times[name])
                 q1, med, q3 = np.percentile(t, (25, 50, 75))
-                print("%3d x %s %-8s median %8.3f ms  (min %8.3f, quartiles %8.3f .. %8.3f, %d steps)" %
+                print("%3d x %s %-20s median %8.3f ms  (min %8.3f, quartiles %8.3f .. %8.3f, %d steps)" %
                       (n, enc, name, med, t.min(), q1, q3, len(t)), flush=True)
             if have:
                 a, b = plain.unpack(p_two), rect.unpack(p_rect)
                 same = all(len(x) == len(y) and all(np.array_equal(u["p"], v["p"]) for u, v in zip(x, y)) for x, y in zip(a, b))
                 print("%3d x %s records of in-sub and two-step equal: %s (%.1f per frame)" % (n, enc, same, np.mean([len(x) for x in b])), flush=True)
                 rect.close()
+            [det.close() for det in general]
             plain.close()
             del batch, plane, gray
 
@@ -124,5 +161,6 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 256])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cameras", nargs="*", default=list(CAMERAS), choices=CAMERAS, help="step: the general cameras to time (none: --cameras)")
     a = ap.parse_args()
     (step_mode if a.mode == "step" else kernel_mode)(a)

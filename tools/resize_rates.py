@@ -5,6 +5,8 @@
   step by step:
     in-sub  amdAprilTagsSetResize (and amdAprilTagsSetRectification with n cameras) on a handle of the target size, one
             DetectBatch[Color]Ex on the caller's frames
+    in-sub <camera>   with rectification, the same through amdAprilTagsSetRectificationEx (k_resize_frames_general), n cameras of one
+            kind: plumb_bob+R, rational, rational+R, equidistant, equidistant+R (--cameras; the cameras of tools/rectify_rates.py)
     chain   the host-side chain of the calls that exist without amdAprilTagsSetResize: per frame amdAprilTagsConvertToMono8 (bgr8 only),
             amdAprilTagsRectifyMono8 (with rectification only) and amdAprilTagsResizeMono8, each on the caller's stream into a host-owned
             plane, then one mono8 DetectBatchEx on a plain handle of the target size
@@ -22,6 +24,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isaac_ros_apriltag_amd import capi, synth  # noqa: E402
 from isaac_ros_apriltag_amd.detector import AprilTagDetector  # noqa: E402
 
@@ -40,6 +43,13 @@ def model(w, h):
     Kn[0, 2] += 6.5 * w / 1920.0
     Kn[1, 2] -= 4.25 * h / 1080.0
     return K, DA, Kn
+
+
+def model_ex(name, w, h):
+    """rectify_rates.model_ex scaled to w x h."""
+    import rectify_rates as rr
+    K, D, Kn, kind, R = rr.model_ex(name)
+    return scaled(K, 1920, 1080, w, h), D, scaled(Kn, 1920, 1080, w, h), kind, R
 
 
 def scaled(K, sw, sh, dw, dh):
@@ -93,6 +103,13 @@ def main(args):
                             L.amdAprilTagsResizeMono8(src.data_ptr(), sw, sw, sh, splane[i].data_ptr(), dw, dw, dh, None)
                         plain.run_prepared(p_chain)
                     forms = {"in-sub": lambda: fused.run_prepared(p_fused), "chain": chain}
+                    general = []
+                    for cam in (args.cameras if rect else ()):
+                        M = model_ex(cam, sw, sh)
+                        det = AprilTagDetector(dw, dh, max_batch=n, resize=[(dw, dh)], rectification=[M] * n)
+                        prep = det.prepare(batch, max_dets=64, intrinsics=[k4(scaled(M[2], sw, sh, dw, dh))] * n, encoding=enc)
+                        forms["in-sub " + cam] = lambda det=det, prep=prep: det.run_prepared(prep)
+                        general.append(det)
                     times = {f: [] for f in forms}
                     for f in forms.values():   # warm every form: code objects, graphs, planes
                         f()
@@ -107,11 +124,12 @@ def main(args):
                     for name in forms:
                         t = np.array(times[name])
                         q1, med, q3 = np.percentile(t, (25, 50, 75))
-                        print("%s %-6s median %8.3f ms  (min %8.3f, quartiles %8.3f .. %8.3f, %d steps)" %
+                        print("%s %-20s median %8.3f ms  (min %8.3f, quartiles %8.3f .. %8.3f, %d steps)" %
                               (tag, name, med, t.min(), q1, q3, len(t)), flush=True)
                     a, b = plain.unpack(p_chain), fused.unpack(p_fused)
                     same = all(len(x) == len(y) and all(np.array_equal(u["p"], v["p"]) for u, v in zip(x, y)) for x, y in zip(a, b))
                     print("%s records of in-sub and chain equal: %s (%.1f per frame)" % (tag, same, np.mean([len(x) for x in b])), flush=True)
+                    [det.close() for det in general]
                     fused.close()
                     plain.close()
                 del batch, gray, rplane, splane
@@ -121,4 +139,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", type=int, nargs="+", default=[8, 64])
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--cameras", nargs="*", default=["plumb_bob+R", "rational", "rational+R", "equidistant", "equidistant+R"],
+                    help="the general cameras to time in the rows with rectification (none: --cameras)")
     main(ap.parse_args())
