@@ -367,6 +367,51 @@ typedef struct { uint32_t width, height; } amdAprilTagsSize_t;
  * the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the sizes does not. */
 int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdAprilTagsSize_t* sizes);
 
+/* Board pose inside the submission: tag bundles (apriltag_ros' word) solved per frame, behind the detector.
+ * A bundle is a planar board: members (family_index, id, x, y, size) with the tag centre (x, y) on the board plane in metres, size the
+ * black-border edge in metres (the meaning of tag_size) and the tag axes parallel to the board axes -- corner k of a record,
+ * p[k] = H(c_k) with c = (-1, 1), (1, 1), (1, -1), (-1, -1), is the board point (x + size / 2 * c_k.x, y + size / 2 * c_k.y).
+ * family_index indexes the handle's family list, as amdAprilTagsDetectionEx_t.family does.  Members with in-plane quarter turns and
+ * non-planar bundles are not served. */
+typedef struct { uint32_t family_index; uint32_t id; double x, y, size; } amdAprilTagsBundleMember_t;
+typedef struct {
+  const amdAprilTagsBundleMember_t* members;
+  uint32_t nmembers;
+  uint32_t max_hamming;          /* a record is used only if hamming <= max_hamming */
+  float min_decision_margin;     /* ... and decision_margin >= min_decision_margin */
+  uint32_t min_tags;             /* >= 1: with fewer used tags the bundle is not solved */
+  char name[32];                 /* at most 31 characters and the terminator: the node shell's child frame is "bundle:<name>" */
+} amdAprilTagsBundle_t;
+#define AMDAT_BUNDLE_SOLVED 0u
+#define AMDAT_BUNDLE_TOO_FEW_TAGS 1u
+#define AMDAT_BUNDLE_SINGULAR 2u
+#define AMDAT_MAX_BUNDLES 8u
+#define AMDAT_MAX_BUNDLE_MEMBERS 1024u   /* over all bundles of a handle */
+/* One record per (frame, bundle).  ntags: records used; nskipped: records of the bundle's members refused by a gate or by the
+ * duplicate rule; R (row-major), t: the board frame in the camera frame, as a tag's; sq_err_sum: the sum of the squared pixel
+ * reprojection errors of the 4 * ntags corners under (R, t, the frame's intrinsics and skew) -- no square root is taken: the RMS is
+ * sqrt(sq_err_sum / (4 * ntags)).  A record whose status is not AMDAT_BUNDLE_SOLVED has R, t and sq_err_sum all zero. */
+typedef struct { uint32_t bundle, status, ntags, nskipped; double R[9]; double t[3]; double sq_err_sum; } amdAprilTagsBundlePose_t;
+/* nbundles = 0 turns the feature off (the default: nothing is launched or allocated).  Otherwise every following submission solves,
+ * in one small launch behind the last detector stage, one pose per frame and bundle from ALL kept records of the frame (also those
+ * beyond the caller's max_tags): one joint least-squares homography over the used tags' corners in normalised board and pixel
+ * coordinates, normal equations in FP64 summed per record and then in record order, the 8 x 9 pivoted elimination of the single-tag
+ * homography, and the single-tag pose routine (DESIGN.md section 7d has every operation; tests/bundle_ref.py states it in Python).
+ * A (family, id) that occurs more than once among a frame's kept records contributes none of its records.  The records are in the
+ * detected image's pixels and the intrinsics are the frame's, so the call composes with amdAprilTagsSetPerFrameSizes,
+ * amdAprilTagsSetRectification[Ex] and amdAprilTagsSetResize as it stands.  Applies to Detect[Color], DetectBatch[Color][Ex] and
+ * SubmitBatch[Color] / WaitBatch[Ex], on both launch sets.
+ * Callable whenever no submission is in flight.  AMDAT_INVALID_ARGUMENT: null handle, null bundles with nbundles > 0, a null members
+ * pointer or nmembers = 0, more than AMDAT_MAX_BUNDLES bundles or AMDAT_MAX_BUNDLE_MEMBERS members in all, a family_index outside the
+ * handle's list, an id outside the family's codes, a (family_index, id) named twice (within or across bundles), a non-finite or
+ * non-positive size, a non-finite coordinate, min_tags = 0, a name without terminator, a submission in flight; AMDAT_OUT_OF_MEMORY: the
+ * device buffers could not be allocated.  A refused call leaves the previous setting in force.  Turning the mode on or off retires the
+ * handle's captured launch graphs, against the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the layout does not. */
+int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundle_t* bundles);
+/* The bundle records of the last completed submission: nframes x nbundles, frame-major (out[f * nbundles + b]).
+ * AMDAT_INVALID_ARGUMENT: null handle or out, bundles off, nframes beyond the last submission's, a submission in flight. */
+int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose_t* out, uint32_t nframes);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

@@ -51,6 +51,9 @@ int amdAprilTagsDebugLateWaits(amdAprilTagsHandle handle);
  * graphs it has and enqueues everything else plainly, ~0.1 ms more per one-frame call), -1 for a null handle; the counts of live
  * cache entries and of retired graphs (kept until the handle is destroyed, see csrc/detector.hip: retire_graph) through the outputs. */
 int amdAprilTagsDebugGraphReplay(amdAprilTagsHandle handle, uint32_t* live_graphs, uint32_t* retired_graphs);
+/* The number of nodes (launches) of the captured graph the handle's last submission replayed; 0 if that submission went out as plain
+ * enqueues, -1 for a null handle. */
+int amdAprilTagsDebugLastGraphNodes(amdAprilTagsHandle handle);
 
 /* quad_sigma's taps as amdAprilTagsSetQuadSigma computes them (host only, no device): upstream's kernel size through *ksz (1 for the
  * identity, |quad_sigma| < 0.5) and, when it is above 1, the ksz taps (capacity >= ksz, else AMDAT_INVALID_ARGUMENT).  Same argument

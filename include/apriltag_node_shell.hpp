@@ -90,6 +90,26 @@ struct Vector3 { double x = 0, y = 0, z = 0; };
 struct Transform { Vector3 translation; Quaternion rotation; };
 struct TransformStamped { Header header; std::string child_frame_id; Transform transform; };
 
+// A tag bundle (apriltag_ros' word): a planar board of tags of the node's family whose pose the detector solves per frame from all its
+// detected tags at once (amdAprilTagsSetBundles, include/apriltag_amd.h).  (x, y): the tag centre on the board plane in metres, size:
+// its black-border edge; tag axes parallel to the board axes.
+struct BundleMember { uint32_t id = 0; double x = 0, y = 0, size = 0; };
+struct Bundle {
+  std::string name;                 // at most 31 characters: the TF child frame is "bundle:<name>"
+  std::vector<BundleMember> members;
+  uint32_t max_hamming = 2;         // a tag is used only with at most this many bit errors ...
+  double min_decision_margin = 0;   // ... and at least this decision margin
+  uint32_t min_tags = 1;            // with fewer used tags the bundle is not solved (no transform)
+};
+// The detector's record of one bundle for one frame (amdAprilTagsBundlePose_t): status 0 solved, 1 too few tags, 2 singular.
+struct BundlePose {
+  std::string name;
+  uint32_t status = 0, ntags = 0, nskipped = 0;
+  std::array<double, 9> R{};        // row-major
+  std::array<double, 3> t{};
+  double sq_err_sum = 0;            // squared pixel reprojection errors of the 4 * ntags corners, summed
+};
+
 // Parameters declared in the constructor of the reference node (src/apriltag_node.cpp:564-568).
 struct NodeOptions {
   int max_tags = 64;
@@ -126,6 +146,10 @@ struct NodeOptions {
   // of Knew) times resize_width / width, fy and cy times resize_height / height -- of the first frame's CameraInfo for AprilTagNode,
   // of every staged frame's for AprilTagMultiCameraNode.  0 (the default): off.
   uint32_t resize_width = 0, resize_height = 0;
+  // Extension: tag bundles, set once when the handle is created (amdAprilTagsSetBundles).  Both nodes append one TransformStamped per
+  // SOLVED bundle behind the tags' -- child frame "bundle:<name>", the camera info's header, as for tags -- and keep the frame's records
+  // (last_bundle_poses).  Empty (the default): off.
+  std::vector<Bundle> bundles;
 };
 
 class AprilTagNode {
@@ -148,6 +172,8 @@ class AprilTagNode {
 
   const NodeOptions& options() const;
   bool initialized() const;
+  // NodeOptions::bundles: the records of the last published frame, one per bundle in the options' order (empty: bundles off)
+  const std::vector<BundlePose>& last_bundle_poses() const;
 
  private:
   struct Impl;
@@ -187,6 +213,8 @@ class AprilTagMultiCameraNode {
 
   uint32_t num_streams() const;
   const NodeOptions& options() const;
+  // NodeOptions::bundles: the records of the last frame published for `stream`, one per bundle in the options' order
+  const std::vector<BundlePose>& last_bundle_poses(uint32_t stream) const;
 
  private:
   struct Impl;

@@ -46,6 +46,27 @@ class Size(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class BundleMember(C.Structure):
+    """amdAprilTagsBundleMember_t: tag (family_index, id) with its centre (x, y) on the board plane and its border edge, in metres."""
+    _fields_ = [("family_index", C.c_uint32), ("id", C.c_uint32), ("x", C.c_double), ("y", C.c_double), ("size", C.c_double)]
+
+
+class Bundle(C.Structure):
+    """amdAprilTagsBundle_t."""
+    _fields_ = [("members", C.POINTER(BundleMember)), ("nmembers", C.c_uint32), ("max_hamming", C.c_uint32),
+                ("min_decision_margin", C.c_float), ("min_tags", C.c_uint32), ("name", C.c_char * 32)]
+
+
+class BundlePose(C.Structure):
+    """amdAprilTagsBundlePose_t."""
+    _fields_ = [("bundle", C.c_uint32), ("status", C.c_uint32), ("ntags", C.c_uint32), ("nskipped", C.c_uint32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("sq_err_sum", C.c_double)]
+
+
+BUNDLE_SOLVED, BUNDLE_TOO_FEW_TAGS, BUNDLE_SINGULAR = 0, 1, 2
+MAX_BUNDLES, MAX_BUNDLE_MEMBERS = 8, 1024
+
+
 class Float2(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float)]
 
@@ -88,7 +109,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsStreamDestroy", "amdAprilTagsDebugGraphReplay", "amdAprilTagsConfigLayoutVersion",
            "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes",
            "amdAprilTagsSetRectification", "amdAprilTagsSetResize", "amdAprilTagsDistortionFromName",
-           "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex"]
+           "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex", "amdAprilTagsSetBundles", "amdAprilTagsGetBundlePoses",
+           "amdAprilTagsDebugLastGraphNodes"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -171,6 +193,9 @@ def lib():
     L.amdAprilTagsSetRectificationEx.argtypes = [H, C.c_uint32, C.POINTER(CameraModelEx)]
     L.amdAprilTagsRectifyMono8Ex.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                              C.POINTER(CameraModelEx), H]
+    L.amdAprilTagsDebugLastGraphNodes.argtypes = [H]
+    L.amdAprilTagsSetBundles.argtypes = [H, C.c_uint32, C.POINTER(Bundle)]
+    L.amdAprilTagsGetBundlePoses.argtypes = [H, C.POINTER(BundlePose), C.c_uint32]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -288,6 +313,32 @@ def sizes(pairs):
     arr = (Size * len(pairs))()
     for s, (w, h) in zip(arr, pairs):
         s.width, s.height = int(w), int(h)
+    return arr
+
+
+def bundles(specs):
+    """[{"name", "members": [(family_index, id, x, y, size)], "max_hamming" (2), "min_decision_margin" (0.0), "min_tags" (1)}] -> a ctypes
+    array of amdAprilTagsBundle_t (None for an empty list); the member arrays it points into are kept alive on the array."""
+    specs = list(specs or [])
+    if not specs:
+        return None
+    arr = (Bundle * len(specs))()
+    keep = []
+    for b, spec in zip(arr, specs):
+        mem = list(spec["members"])
+        m = (BundleMember * max(len(mem), 1))()
+        for dst, (fam, tid, x, y, size) in zip(m, mem):
+            dst.family_index, dst.id, dst.x, dst.y, dst.size = int(fam), int(tid), float(x), float(y), float(size)
+        keep.append(m)
+        b.members, b.nmembers = C.cast(m, C.POINTER(BundleMember)), len(mem)
+        b.max_hamming = int(spec.get("max_hamming", 2))
+        b.min_decision_margin = float(spec.get("min_decision_margin", 0.0))
+        b.min_tags = int(spec.get("min_tags", 1))
+        name = spec.get("name", "").encode()
+        if len(name) > 31:
+            raise ValueError("a bundle name has at most 31 characters")
+        b.name = name
+    arr._keep = keep
     return arr
 
 

@@ -20,6 +20,7 @@
 #include "../../include/apriltag_amd_debug.h"
 #include "../../include/apriltag_amd_families.h"
 #include "common.h"
+#include "kernels_bundle.h"
 #include "kernels_cc.h"
 #include "kernels_cluster.h"
 #include "kernels_decode.h"
@@ -224,11 +225,13 @@ struct amdAprilTagsDetector_st {
   // captured enqueue sequence of small submissions (see run_batch)
   uint32_t graph_max_frames = 8;
   struct GraphEntry { hipGraphExec_t exec = nullptr; uint32_t n = 0, ostride = 0, fmt = 0; hipStream_t stream = nullptr; uint64_t last_use = 0;
-                      bool general = false; };   // general: captured with the general front kernel (rect_general)
+                      bool general = false;      // general: captured with the general front kernel (rect_general)
+                      uint32_t nodes = 0; };     // the graph's nodes (amdAprilTagsDebugLastGraphNodes)
   GraphEntry graphs[6];
   std::vector<hipGraphExec_t> retired_graphs;   // see drop_graphs
   uint64_t graph_clock = 0;
   uint32_t graph_misses = 0;         // consecutive captures that had to evict an entry
+  uint32_t last_graph_nodes = 0;     // nodes of the graph the last launch replayed; 0: plain enqueues
   uint32_t capture_failures = 0;     // captures that did not end in a graph (recover_from_failed_capture)
   hipEvent_t ev[AMDAT_NUM_STAGES + 1] = {};
   // which launch set a submission gets: by its size (AMDAT_PATH_AUTO) or pinned by amdAprilTagsDebugSetSubmissionPath, so that
@@ -264,6 +267,14 @@ struct amdAprilTagsDetector_st {
   ResizeDesc* h_zdesc = nullptr;                        // pinned, one per batch slot, uploaded by k_prologue
   DevBuf<ResizeDesc> d_zdesc;
   bool last_resized = false;                            // the last submission resized (AMDAT_DBG_RESIZED)
+  // amdAprilTagsSetBundles: k_bundle_pose runs behind k_reconcile while nbundles > 0.  The device layout (bundle_layout.h) is allocated
+  // once, at its largest size, by the first call that turns the feature on, so that a later layout changes no launch argument
+  uint32_t nbundles = 0;                                // 0: off
+  uint32_t last_nbundles = 0;                           // of the last submission (amdAprilTagsGetBundlePoses)
+  DevBuf<BundleHeadDev> d_bundle_head;
+  DevBuf<BundleMemberDev> d_bundle_members;             // AMDAT_MAX_BUNDLE_MEMBERS
+  DevBuf<uint16_t> d_bundle_table;                      // one entry per code of every family of the handle
+  BundlePoseRec* h_bposes = nullptr;                    // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_pose writes frame * nbundles + bundle
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -499,6 +510,7 @@ static void free_all(amdAprilTagsDetector_st* D) {
   if (D->h_out) hipHostFree(D->h_out);
   if (D->h_rdesc) hipHostFree(D->h_rdesc);
   if (D->h_zdesc) hipHostFree(D->h_zdesc);
+  if (D->h_bposes) hipHostFree(D->h_bposes);
   for (auto& e : D->ev) if (e) hipEventDestroy(e);
   if (D->own_stream) hipStreamDestroy(D->own_stream);
   for (auto& a : D->aux_stream) if (a) hipStreamDestroy(a);
@@ -1036,6 +1048,53 @@ int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdA
   return AMDAT_SUCCESS;
 }
 
+// What the first call that turns bundles on allocates: the device layout at its largest size and the pinned record block.
+static int ensure_bundle_buffers(amdAprilTagsDetector_st* D, size_t table_entries) {
+  if (!D->d_bundle_head && !dev_alloc(D, D->d_bundle_head, sizeof(BundleHeadDev))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->d_bundle_members && !dev_alloc(D, D->d_bundle_members, AMDAT_MAX_BUNDLE_MEMBERS * sizeof(BundleMemberDev))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->d_bundle_table && !dev_alloc(D, D->d_bundle_table, table_entries * sizeof(uint16_t))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->h_bposes) {
+    const size_t bytes = (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(BundlePoseRec);
+    if (hipHostMalloc((void**)&D->h_bposes, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+      D->h_bposes = nullptr;
+      (void)hipGetLastError();
+      return AMDAT_OUT_OF_MEMORY;
+    }
+    memset(D->h_bposes, 0, bytes);
+  }
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundle_t* bundles) {
+  if (!handle || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  uint32_t ncodes[AT_MAX_FAMILIES] = {};
+  for (int i = 0; i < handle->P.nfam; i++) ncodes[i] = handle->P.fam[i].ncodes;
+  BundleLayout L;
+  { const int rc = bundle_layout_build((uint32_t)handle->P.nfam, ncodes, nbundles, bundles, &L); if (rc) return rc; }
+  const bool on = nbundles > 0;
+  DeviceGuard guard(handle->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  if (on) {
+    { const int rc = ensure_bundle_buffers(handle, L.table.size()); if (rc) return rc; }
+    // (no submission is in flight: nothing reads the layout; `L` is pageable, so the copies are waited for before it goes)
+    const hipStream_t s = handle->own_stream;
+    HIP_TRY(hipMemcpyAsync(handle->d_bundle_head, &L.head, sizeof(L.head), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(handle->d_bundle_members, L.members.data(), L.members.size() * sizeof(BundleMemberDev), hipMemcpyHostToDevice, s));
+    if (!L.table.empty()) HIP_TRY(hipMemcpyAsync(handle->d_bundle_table, L.table.data(), L.table.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (on != (handle->nbundles > 0)) drop_graphs(handle);   // captured with or without the bundle launch; the layout itself lives in device memory
+  handle->nbundles = nbundles;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose_t* out, uint32_t nframes) {
+  if (!handle || !out || handle->inflight.active || handle->last_nbundles == 0 || nframes > handle->last_n) return AMDAT_INVALID_ARGUMENT;
+  const size_t n = (size_t)nframes * handle->last_nbundles;
+  for (size_t i = 0; i < n; i++) out[i] = handle->h_bposes[i].pose;
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
   if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
   if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
@@ -1058,6 +1117,8 @@ int amdAprilTagsDebugGraphReplay(amdAprilTagsHandle handle, uint32_t* live_graph
   if (retired_graphs) *retired_graphs = (uint32_t)handle->retired_graphs.size();
   return handle->graph_max_frames ? 1 : 0;
 }
+
+int amdAprilTagsDebugLastGraphNodes(amdAprilTagsHandle handle) { return handle ? (int)handle->last_graph_nodes : -1; }
 
 int amdAprilTagsDebugLastSubmissionPath(amdAprilTagsHandle handle) {
   return handle ? handle->last_path : -1;
@@ -1406,6 +1467,9 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   mark();
   hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
                      D->h_counters, P);
+  if (D->nbundles)   // S10: one wave per (frame, bundle) on the kept records, straight behind k_reconcile (kernels_bundle.h)
+    hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+                       D->d_bundle_head, D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
   mark();
   return AMDAT_SUCCESS;
 }
@@ -1510,6 +1574,7 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
   D->launched_n = n;
   const bool prof = D->profiling;
   D->events_recorded = false;
+  D->last_graph_nodes = 0;
   int evi = 0;
   // profiling: one HIP event per stage boundary, and a roctx range per stage (it spans the stage's enqueues; rocprofv3
   // --marker-trace shows them beside the kernels they launched)
@@ -1552,9 +1617,11 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
         const hipError_t e = hipStreamEndCapture(s, &graph);
         ok = rc == AMDAT_SUCCESS && e == hipSuccess && graph != nullptr;
       }
+      size_t nodes = 0;
+      if (ok && hipGraphGetNodes(graph, nullptr, &nodes) != hipSuccess) { nodes = 0; (void)hipGetLastError(); }
       if (ok) ok = hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess;
       if (graph) hipGraphDestroy(graph);
-      if (ok) { slot->n = n; slot->ostride = ostride; slot->fmt = fmt; slot->stream = s; slot->general = D->rect_general; slot->last_use = ++D->graph_clock; hit = slot; }
+      if (ok) { slot->n = n; slot->ostride = ostride; slot->fmt = fmt; slot->stream = s; slot->general = D->rect_general; slot->nodes = (uint32_t)nodes; slot->last_use = ++D->graph_clock; hit = slot; }
       else {
         // A capture can be invalidated from OUTSIDE the library: on this runtime a legacy-stream call of any other host thread on
         // the same device (a plain hipMemcpy) while this thread captures fails that call and poisons the capture, in every capture
@@ -1568,6 +1635,7 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
       }
     }
     if (hit) {
+      D->last_graph_nodes = hit->nodes;
       HIP_TRY(hipGraphLaunch(hit->exec, s));
       return AMDAT_SUCCESS;
     }
@@ -1590,6 +1658,9 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
   auto stamped = [&]() {
     for (uint32_t f = 0; f < D->launched_n; f++)
       if (reinterpret_cast<volatile FrameCounters*>(D->h_counters)[f].seq != D->seq) return false;
+    // bundles on: k_bundle_pose, the last kernel, stamps its records the same way
+    for (uint32_t r = 0; r < D->launched_n * D->nbundles; r++)
+      if (reinterpret_cast<volatile BundlePoseRec*>(D->h_bposes)[r].seq != D->seq) return false;
     return true;
   };
   if (!stamped()) {
@@ -1682,6 +1753,7 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   { const int crc = ensure_colour_plane(D, fmt, filt); if (crc) return crc; }
   fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
   D->last_n = n;
+  D->last_nbundles = D->nbundles;
   D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
@@ -1890,6 +1962,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   if (rc) return rc;
   fill_frames(handle, n, images, nullptr, fmt);
   handle->last_n = n;
+  handle->last_nbundles = 0;        // (never solves bundles)
   handle->last_rectified = false;   // (never rectifies)
   handle->last_resized = false;     // (never resizes)
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));

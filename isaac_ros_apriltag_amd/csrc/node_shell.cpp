@@ -47,6 +47,8 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetRectification) set_rectification = nullptr;
   decltype(&amdAprilTagsSetResize) set_resize = nullptr;
   decltype(&amdAprilTagsSetRectificationEx) set_rectification_ex = nullptr;
+  decltype(&amdAprilTagsSetBundles) set_bundles = nullptr;
+  decltype(&amdAprilTagsGetBundlePoses) get_bundle_poses = nullptr;
 };
 
 DetectorApi& api() {
@@ -86,6 +88,8 @@ DetectorApi& api() {
   BIND(set_rectification, "amdAprilTagsSetRectification")
   BIND(set_resize, "amdAprilTagsSetResize")
   BIND(set_rectification_ex, "amdAprilTagsSetRectificationEx")
+  BIND(set_bundles, "amdAprilTagsSetBundles")
+  BIND(get_bundle_poses, "amdAprilTagsGetBundlePoses")
 #undef BIND
   return a;
 }
@@ -171,6 +175,64 @@ void apply_resize(amdAprilTagsHandle detector, const NodeOptions& opt) {
   if (error != 0)
     throw std::runtime_error("'resize_width' x 'resize_height' " + std::to_string(opt.resize_width) + " x " +
                              std::to_string(opt.resize_height) + " refused (error code " + std::to_string(error) + ")");
+}
+
+// NodeOptions::bundles on a freshly created handle (the node has one family: family_index 0)
+void apply_bundles(amdAprilTagsHandle detector, const NodeOptions& opt) {
+  if (opt.bundles.empty()) return;
+  std::vector<std::vector<amdAprilTagsBundleMember_t>> members(opt.bundles.size());
+  std::vector<amdAprilTagsBundle_t> abi(opt.bundles.size());
+  for (size_t b = 0; b < opt.bundles.size(); b++) {
+    const Bundle& in = opt.bundles[b];
+    if (in.name.size() > 31) throw std::runtime_error("'bundles': the name '" + in.name + "' has more than 31 characters");
+    for (const BundleMember& m : in.members) members[b].push_back({0u, m.id, m.x, m.y, m.size});
+    abi[b] = {};
+    abi[b].members = members[b].data();
+    abi[b].nmembers = static_cast<uint32_t>(members[b].size());
+    abi[b].max_hamming = in.max_hamming;
+    abi[b].min_decision_margin = static_cast<float>(in.min_decision_margin);
+    abi[b].min_tags = in.min_tags;
+    std::strncpy(abi[b].name, in.name.c_str(), sizeof(abi[b].name) - 1);
+  }
+  const int error = api().set_bundles(detector, static_cast<uint32_t>(abi.size()), abi.data());
+  if (error != 0) throw std::runtime_error("'bundles' refused (error code " + std::to_string(error) + ")");
+}
+
+Quaternion quaternion_from_colmajor(const float* o);
+
+// The bundle records of the first nframes frames of the submission that just returned (frame-major), and per frame one transform for
+// every solved bundle appended to tfs[f]: child frame "bundle:<name>", the frame's camera info header, as for tags.
+bool collect_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t nframes, const Header* const* headers,
+                     std::vector<std::vector<BundlePose>>* poses, std::vector<TransformStamped>* const* tfs) {
+  const size_t nb = opt.bundles.size();
+  poses->assign(nframes, std::vector<BundlePose>());
+  if (nb == 0) return true;
+  std::vector<amdAprilTagsBundlePose_t> recs(static_cast<size_t>(nframes) * nb);
+  if (api().get_bundle_poses(detector, recs.data(), nframes) != 0) return false;
+  for (uint32_t f = 0; f < nframes; f++) {
+    for (size_t b = 0; b < nb; b++) {
+      const amdAprilTagsBundlePose_t& r = recs[f * nb + b];
+      BundlePose p;
+      p.name = opt.bundles[b].name;
+      p.status = r.status; p.ntags = r.ntags; p.nskipped = r.nskipped; p.sq_err_sum = r.sq_err_sum;
+      for (int i = 0; i < 9; i++) p.R[i] = r.R[i];
+      for (int i = 0; i < 3; i++) p.t[i] = r.t[i];
+      (*poses)[f].push_back(p);
+      if (r.status != AMDAT_BUNDLE_SOLVED) continue;
+      TransformStamped tf;
+      tf.header = *headers[f];
+      tf.child_frame_id = "bundle:" + p.name;
+      tf.transform.translation.x = r.t[0];
+      tf.transform.translation.y = r.t[1];
+      tf.transform.translation.z = r.t[2];
+      float o[9];   // column-major float, the form a tag's orientation has
+      for (int rr = 0; rr < 3; rr++)
+        for (int c = 0; c < 3; c++) o[c * 3 + rr] = static_cast<float>(r.R[rr * 3 + c]);
+      tf.transform.rotation = quaternion_from_colmajor(o);
+      tfs[f]->push_back(tf);
+    }
+  }
+  return true;
 }
 
 int bytes_per_pixel(const std::string& enc) {
@@ -358,6 +420,7 @@ struct AprilTagNode::Impl {
 
   // exactly {CUDA}: the reference runs cuAprilTags, which decodes tag36h11 only (src/apriltag_node.cpp:429-432)
   bool cuapriltags_mode = false;
+  std::vector<BundlePose> last_bundles;   // NodeOptions::bundles: the records of the last published frame
 
   void Initialize(const Image& image, const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
@@ -391,6 +454,7 @@ struct AprilTagNode::Impl {
       if (rerr != 0) throw std::runtime_error("'rectify': camera model refused (error code " + std::to_string(rerr) + ")");
     }
     apply_resize(detector, opt);
+    apply_bundles(detector, opt);
     width = info.width;
     height = info.height;
     if (!stream && api().stream_create(&stream) != 0) throw std::runtime_error("stream creation failed");
@@ -460,6 +524,16 @@ struct AprilTagNode::Impl {
     AprilTagDetectionArray msg;
     std::vector<TransformStamped> tfs;
     assemble_messages(tags.data(), num_detections, info.header, opt.tag_family, &msg, &tfs);
+    {
+      std::vector<std::vector<BundlePose>> poses;
+      const Header* hdr = &info.header;
+      std::vector<TransformStamped>* out = &tfs;
+      if (!collect_bundles(detector, opt, 1, &hdr, &poses, &out)) {
+        std::fprintf(stderr, "[apriltag_node] bundle records not available: frame dropped\n");
+        return;
+      }
+      last_bundles = poses[0];
+    }
     if (on_detections) on_detections(msg);
     if (on_transforms) on_transforms(tfs);
   }
@@ -486,6 +560,7 @@ void AprilTagNode::set_detections_callback(DetectionsCallback cb) { impl_->on_de
 void AprilTagNode::set_transforms_callback(TransformsCallback cb) { impl_->on_transforms = std::move(cb); }
 const NodeOptions& AprilTagNode::options() const { return impl_->opt; }
 bool AprilTagNode::initialized() const { return impl_->initialized; }
+const std::vector<BundlePose>& AprilTagNode::last_bundle_poses() const { return impl_->last_bundles; }
 
 bool AprilTagNode::CameraImageCallback(const Image& image, const CameraInfo& camera_info) {
   if (image.header.stamp.sec != camera_info.header.stamp.sec || image.header.stamp.nanosec != camera_info.header.stamp.nanosec)
@@ -518,7 +593,7 @@ struct AprilTagMultiCameraNode::Impl {
     uint8_t* dev = nullptr; size_t pitch = 0; void* own = nullptr; size_t own_bytes = 0;
   };
   std::vector<Slot> slots;
-
+  std::vector<std::vector<BundlePose>> last_bundles;   // per stream (NodeOptions::bundles)
 
   void Initialize(const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
@@ -548,6 +623,7 @@ struct AprilTagMultiCameraNode::Impl {
     apply_quad_sigma(detector, opt.quad_sigma);
     if (mixed && api().set_per_frame_sizes(detector, 1) != 0) throw std::runtime_error("per-frame image sizes refused");
     apply_resize(detector, opt);
+    apply_bundles(detector, opt);
     width = cfg.width;
     height = cfg.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
@@ -626,6 +702,7 @@ AprilTagMultiCameraNode::AprilTagMultiCameraNode(const NodeOptions& options, uin
   impl_->opt = options;
   impl_->S = num_streams;
   impl_->slots.resize(num_streams);
+  impl_->last_bundles.resize(num_streams);
   impl_->family_enum = validate_family(options, &impl_->cuapriltags_mode);
 }
 
@@ -642,6 +719,7 @@ void AprilTagMultiCameraNode::set_detections_callback(DetectionsCallback cb) { i
 void AprilTagMultiCameraNode::set_transforms_callback(TransformsCallback cb) { impl_->on_transforms = std::move(cb); }
 void AprilTagMultiCameraNode::set_auto_flush(bool on) { impl_->auto_flush = on; }
 uint32_t AprilTagMultiCameraNode::num_streams() const { return impl_->S; }
+const std::vector<BundlePose>& AprilTagMultiCameraNode::last_bundle_poses(uint32_t stream) const { return impl_->last_bundles.at(stream); }
 const NodeOptions& AprilTagMultiCameraNode::options() const { return impl_->opt; }
 
 bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& image, const CameraInfo& camera_info) {
@@ -712,12 +790,24 @@ uint32_t AprilTagMultiCameraNode::Flush() {
     std::fprintf(stderr, "[apriltag_node] Failed to run AprilTags detector (error code %d)\n", error);
     return 0;
   }
+  std::vector<AprilTagDetectionArray> msgs(n);
+  std::vector<std::vector<TransformStamped>> tfs(n);
+  std::vector<const Header*> headers(n);
+  std::vector<std::vector<TransformStamped>*> tf_ptrs(n);
   for (uint32_t i = 0; i < n; i++) {
-    AprilTagDetectionArray msg;
-    std::vector<TransformStamped> tfs;
-    assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt.tag_family, &msg, &tfs);
-    if (I.on_detections) I.on_detections(who[i], msg);
-    if (I.on_transforms) I.on_transforms(who[i], tfs);
+    assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt.tag_family, &msgs[i], &tfs[i]);
+    headers[i] = &I.slots[who[i]].info_header;
+    tf_ptrs[i] = &tfs[i];
+  }
+  std::vector<std::vector<BundlePose>> poses;
+  if (!collect_bundles(I.detector, I.opt, n, headers.data(), &poses, tf_ptrs.data())) {
+    std::fprintf(stderr, "[apriltag_node] bundle records not available: round dropped\n");
+    return 0;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    I.last_bundles[who[i]] = poses[i];
+    if (I.on_detections) I.on_detections(who[i], msgs[i]);
+    if (I.on_transforms) I.on_transforms(who[i], tfs[i]);
   }
   return n;
 }
@@ -846,6 +936,90 @@ NodeShellHarness* node_shell_create_strict(int max_tags, double size, int tile_s
   return node_shell_create_ex(max_tags, size, tile_size, tag_family, backends, decimate, 1, 0.0, err, err_len);
 }
 
+// NodeOptions::bundles through the flat view: members holds four doubles per member -- id, x, y, size
+struct NodeShellBundle {
+  char name[32];
+  const double* members;
+  uint32_t nmembers, max_hamming, min_tags, pad;
+  double min_decision_margin;
+};
+struct NodeShellTransform {
+  char child_frame_id[48];
+  char frame_id[48];
+  int32_t sec;
+  uint32_t nanosec;
+  double translation[3];
+  double rotation_xyzw[4];
+};
+struct NodeShellBundlePose {
+  char name[32];
+  uint32_t status, ntags, nskipped, pad;
+  double R[9], t[3], sq_err_sum;
+};
+
+static void set_bundle_options(NodeOptions* o, int nbundles, const NodeShellBundle* bundles) {
+  for (int b = 0; b < nbundles; b++) {
+    amd::isaac_ros::apriltag::Bundle out;
+    out.name = std::string(bundles[b].name, strnlen(bundles[b].name, sizeof(bundles[b].name)));
+    for (uint32_t m = 0; m < bundles[b].nmembers; m++) {
+      const double* v = bundles[b].members + 4 * m;
+      out.members.push_back({static_cast<uint32_t>(v[0]), v[1], v[2], v[3]});
+    }
+    out.max_hamming = bundles[b].max_hamming; out.min_tags = bundles[b].min_tags; out.min_decision_margin = bundles[b].min_decision_margin;
+    o->bundles.push_back(out);
+  }
+}
+static int copy_transforms(const std::vector<TransformStamped>& tfs, NodeShellTransform* out, int max_out) {
+  const int n = static_cast<int>(tfs.size());
+  for (int i = 0; i < n && i < max_out; i++) {
+    NodeShellTransform& o = out[i];
+    std::memset(&o, 0, sizeof(o));
+    std::strncpy(o.child_frame_id, tfs[i].child_frame_id.c_str(), sizeof(o.child_frame_id) - 1);
+    std::strncpy(o.frame_id, tfs[i].header.frame_id.c_str(), sizeof(o.frame_id) - 1);
+    o.sec = tfs[i].header.stamp.sec; o.nanosec = tfs[i].header.stamp.nanosec;
+    o.translation[0] = tfs[i].transform.translation.x; o.translation[1] = tfs[i].transform.translation.y; o.translation[2] = tfs[i].transform.translation.z;
+    o.rotation_xyzw[0] = tfs[i].transform.rotation.x; o.rotation_xyzw[1] = tfs[i].transform.rotation.y;
+    o.rotation_xyzw[2] = tfs[i].transform.rotation.z; o.rotation_xyzw[3] = tfs[i].transform.rotation.w;
+  }
+  return n;
+}
+static int copy_bundle_poses(const std::vector<amd::isaac_ros::apriltag::BundlePose>& poses, NodeShellBundlePose* out, int max_out) {
+  const int n = static_cast<int>(poses.size());
+  for (int i = 0; i < n && i < max_out; i++) {
+    NodeShellBundlePose& o = out[i];
+    std::memset(&o, 0, sizeof(o));
+    std::strncpy(o.name, poses[i].name.c_str(), sizeof(o.name) - 1);
+    o.status = poses[i].status; o.ntags = poses[i].ntags; o.nskipped = poses[i].nskipped; o.sq_err_sum = poses[i].sq_err_sum;
+    for (int k = 0; k < 9; k++) o.R[k] = poses[i].R[k];
+    for (int k = 0; k < 3; k++) o.t[k] = poses[i].t[k];
+  }
+  return n;
+}
+
+// AprilTagNode with NodeOptions::bundles (the other options at their defaults but those named)
+NodeShellHarness* node_shell_create_bundles(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                            int decimate, int nbundles, const NodeShellBundle* bundles, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    set_bundle_options(&o, nbundles, bundles);
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+// the transforms of the last published frame (tags first, then one per solved bundle), and its bundle records
+int node_shell_last_transforms(NodeShellHarness* h, NodeShellTransform* out, int max_out) { return copy_transforms(h->last_tf, out, max_out); }
+int node_shell_last_bundle_poses(NodeShellHarness* h, NodeShellBundlePose* out, int max_out) {
+  return copy_bundle_poses(h->node->last_bundle_poses(), out, max_out);
+}
+
 void node_shell_destroy(NodeShellHarness* h) { delete h; }
 
 // Feeds one image + camera_info pair.  Returns the number of detections published, -1 if the stamps
@@ -959,6 +1133,33 @@ MultiShellHarness* node_shell_multi_create_ex(int num_streams, int max_tags, dou
 MultiShellHarness* node_shell_multi_create(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
                                            const char* backends, int decimate, int auto_flush, char* err, size_t err_len) {
   return node_shell_multi_create_ex(num_streams, max_tags, size, tile_size, tag_family, backends, decimate, auto_flush, 0.0, err, err_len);
+}
+
+MultiShellHarness* node_shell_multi_create_bundles(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                   const char* backends, int decimate, int auto_flush, int nbundles,
+                                                   const NodeShellBundle* bundles, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    set_bundle_options(&o, nbundles, bundles);
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+int node_shell_multi_last_transforms(MultiShellHarness* h, int stream, NodeShellTransform* out, int max_out) {
+  return copy_transforms(h->last_tf[stream], out, max_out);
+}
+int node_shell_multi_last_bundle_poses(MultiShellHarness* h, int stream, NodeShellBundlePose* out, int max_out) {
+  return copy_bundle_poses(h->node->last_bundle_poses(static_cast<uint32_t>(stream)), out, max_out);
 }
 
 void node_shell_multi_destroy(MultiShellHarness* h) { delete h; }

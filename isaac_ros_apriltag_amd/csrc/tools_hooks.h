@@ -37,14 +37,18 @@
 //                           13 = the general projection (camera_models.h) takes the identity for the transpose of the rectification
 //                               rotation: a camera with R is rectified as if it had none
 //                           14 = the general projection takes 1 for the denominator of rational_polynomial's radial factor: k4 .. k6 are ignored
-//                           (4 .. 14 change values only: no address, index bound, launch size or loop count)
+//                           15 = k_bundle_pose pairs board corner k of a member with the record's corner p[3 - k]: every solved bundle
+//                               gets a wrong pose (a frame without tags is unaffected)
+//                           16 = k_bundle_pose without the duplicate rule: the records of a (family, id) seen twice in a frame are used
+//                           (4 .. 16 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
 //                           tests/test_fit_classes_gpu.py::test_fit_class_tests_fail_on_the_wrong_builds for 7 and 8,
 //                           tests/test_rectify_submission_gpu.py::test_the_rectify_tests_fail_on_the_wrong_builds for 9 and 10,
 //                           tests/test_resize_submission_gpu.py::test_the_resize_tests_fail_on_the_wrong_builds for 11 and 12,
-//                           tests/test_camera_models_gpu.py::test_the_camera_model_tests_fail_on_the_wrong_builds for 13 and 14)
+//                           tests/test_camera_models_gpu.py::test_the_camera_model_tests_fail_on_the_wrong_builds for 13 and 14,
+//                           tests/test_bundles_gpu.py::test_the_bundle_tests_fail_on_the_wrong_builds for 15 and 16)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -110,6 +114,18 @@
 #define RESIZE_SIZE_OF_SLOT(i, nsizes) ((void)(i), (void)(nsizes), 0u)
 #else
 #define RESIZE_SIZE_OF_SLOT(i, nsizes) ((i) % (nsizes))
+#endif
+
+// ---- k_bundle_pose: the record corner that is board corner k, and the duplicate rule ---------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 15
+#define BUNDLE_PIXEL_CORNER(k) (3 - (k))
+#else
+#define BUNDLE_PIXEL_CORNER(k) (k)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 16
+#define BUNDLE_DUPLICATE(dup) ((void)(dup), false)
+#else
+#define BUNDLE_DUPLICATE(dup) (dup)
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------

@@ -51,7 +51,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 **caps):
+                 bundles=None, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -80,6 +80,7 @@ class AprilTagDetector:
         self._L = L
         self.per_frame_sizes = False
         self.resizing = False
+        self.nbundles = 0
         try:
             if quad_sigma:
                 self.set_quad_sigma(quad_sigma)
@@ -89,6 +90,8 @@ class AprilTagDetector:
                 self.set_rectification(rectification)
             if resize:
                 self.set_resize(resize)
+            if bundles:
+                self.set_bundles(bundles)
         except Exception:
             self.close()
             raise
@@ -125,6 +128,23 @@ class AprilTagDetector:
         arr = capi.sizes(sizes)
         capi._check("amdAprilTagsSetResize", self._L.amdAprilTagsSetResize(self._h, len(arr) if arr is not None else 0, arr))
         self.resizing = arr is not None
+
+    def set_bundles(self, bundles):
+        """amdAprilTagsSetBundles: bundles is a list of {"name", "members": [(family_index, id, x, y, size)], "max_hamming",
+        "min_decision_margin", "min_tags"} (capi.bundles) -- planar boards whose pose every following submission solves per frame from
+        all kept records, behind the detector; None or [] turns it off.  bundle_poses(n) hands out the records."""
+        arr = capi.bundles(bundles)
+        capi._check("amdAprilTagsSetBundles", self._L.amdAprilTagsSetBundles(self._h, len(arr) if arr is not None else 0, arr))
+        self.nbundles = len(arr) if arr is not None else 0
+
+    def bundle_poses(self, n):
+        """amdAprilTagsGetBundlePoses: the bundle records of the first n frames of the last completed submission, a list per frame of
+        {"bundle", "status", "ntags", "nskipped", "R" (3x3), "t", "sq_err_sum"} in the order of set_bundles."""
+        out = (capi.BundlePose * max(n * self.nbundles, 1))()
+        capi._check("amdAprilTagsGetBundlePoses", self._L.amdAprilTagsGetBundlePoses(self._h, out, n))
+        return [[{"bundle": int(r.bundle), "status": int(r.status), "ntags": int(r.ntags), "nskipped": int(r.nskipped),
+                  "R": np.array(list(r.R)).reshape(3, 3), "t": np.array(list(r.t)), "sq_err_sum": float(r.sq_err_sum)}
+                 for r in out[f * self.nbundles:(f + 1) * self.nbundles]] for f in range(n)]
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -254,6 +274,15 @@ class AprilTagDetector:
         live, ret = C.c_uint32(), C.c_uint32()
         on = self._L.amdAprilTagsDebugGraphReplay(self._h, C.byref(live), C.byref(ret))
         return bool(on), int(live.value), int(ret.value)
+
+    def last_graph_nodes(self):
+        """Nodes of the captured graph the last submission replayed; 0: plain enqueues."""
+        return int(self._L.amdAprilTagsDebugLastGraphNodes(self._h))
+
+    def set_frame_skews(self, skews):
+        """amdAprilTagsSetFrameSkews: K[0][1] of batch slots 0 .. len(skews) - 1 for the submissions that follow."""
+        arr = (C.c_float * max(len(skews), 1))(*[float(v) for v in skews])
+        capi._check("amdAprilTagsSetFrameSkews", self._L.amdAprilTagsSetFrameSkews(self._h, len(skews), arr))
 
     def last_submission_path(self):
         return {capi.PATH_AUTO: "none", capi.PATH_LATENCY: "latency", capi.PATH_THROUGHPUT: "throughput"}[

@@ -15,6 +15,22 @@ class ShellDetection(C.Structure):
                 ("orientation_xyzw", C.c_double * 4), ("child_frame_id", C.c_char * 48)]
 
 
+class ShellBundle(C.Structure):
+    """NodeOptions::bundles through the flat view: members holds four doubles per member -- id, x, y, size."""
+    _fields_ = [("name", C.c_char * 32), ("members", C.POINTER(C.c_double)), ("nmembers", C.c_uint32), ("max_hamming", C.c_uint32),
+                ("min_tags", C.c_uint32), ("pad", C.c_uint32), ("min_decision_margin", C.c_double)]
+
+
+class ShellTransform(C.Structure):
+    _fields_ = [("child_frame_id", C.c_char * 48), ("frame_id", C.c_char * 48), ("sec", C.c_int32), ("nanosec", C.c_uint32),
+                ("translation", C.c_double * 3), ("rotation_xyzw", C.c_double * 4)]
+
+
+class ShellBundlePose(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("status", C.c_uint32), ("ntags", C.c_uint32), ("nskipped", C.c_uint32), ("pad", C.c_uint32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("sq_err_sum", C.c_double)]
+
+
 _lib = None
 
 
@@ -89,8 +105,49 @@ def lib():
         L.node_shell_multi_last.restype = C.c_int
         L.node_shell_multi_last.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellDetection), C.c_int, C.c_char_p, C.c_size_t,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+        L.node_shell_create_bundles.restype = C.c_void_p
+        L.node_shell_create_bundles.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                C.POINTER(ShellBundle), C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_bundles.restype = C.c_void_p
+        L.node_shell_multi_create_bundles.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                      C.c_int, C.POINTER(ShellBundle), C.c_char_p, C.c_size_t]
+        L.node_shell_last_transforms.restype = C.c_int
+        L.node_shell_last_transforms.argtypes = [C.c_void_p, C.POINTER(ShellTransform), C.c_int]
+        L.node_shell_last_bundle_poses.restype = C.c_int
+        L.node_shell_last_bundle_poses.argtypes = [C.c_void_p, C.POINTER(ShellBundlePose), C.c_int]
+        L.node_shell_multi_last_transforms.restype = C.c_int
+        L.node_shell_multi_last_transforms.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellTransform), C.c_int]
+        L.node_shell_multi_last_bundle_poses.restype = C.c_int
+        L.node_shell_multi_last_bundle_poses.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellBundlePose), C.c_int]
         _lib = L
     return _lib
+
+
+def _shell_bundles(bundles):
+    """[{"name", "members": [(id, x, y, size)], "max_hamming", "min_decision_margin", "min_tags"}] -> a ShellBundle array (kept alive
+    with its member arrays)."""
+    arr = (ShellBundle * len(bundles))()
+    keep = []
+    for b, spec in zip(arr, bundles):
+        flat = [float(v) for m in spec["members"] for v in m]
+        mem = (C.c_double * max(len(flat), 1))(*flat)
+        keep.append(mem)
+        b.name = spec.get("name", "").encode()
+        b.members, b.nmembers = C.cast(mem, C.POINTER(C.c_double)), len(spec["members"])
+        b.max_hamming, b.min_tags = int(spec.get("max_hamming", 2)), int(spec.get("min_tags", 1))
+        b.min_decision_margin = float(spec.get("min_decision_margin", 0.0))
+    arr._keep = keep
+    return arr
+
+
+def _unpack_transforms(out, n):
+    return [{"child_frame_id": t.child_frame_id.decode(), "frame_id": t.frame_id.decode(), "stamp": (t.sec, t.nanosec),
+             "translation": list(t.translation), "rotation_xyzw": list(t.rotation_xyzw)} for t in out[:n]]
+
+
+def _unpack_bundle_poses(out, n):
+    return [{"name": p.name.decode(), "status": int(p.status), "ntags": int(p.ntags), "nskipped": int(p.nskipped), "R": list(p.R),
+             "t": list(p.t), "sq_err_sum": float(p.sq_err_sum)} for p in out[:n]]
 
 
 def _unpack(out, n):
@@ -158,16 +215,25 @@ class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None):
+                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
         undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
         (NodeOptions::rectify_full): with any of the three distortion models and the rotation R of its CameraInfo.  resize
         (NodeOptions::resize_width, resize_height): (w, h) -- frames of any size are resized to it inside the submission, behind the
-        rectification, and the pose is computed with the scaled camera."""
+        rectification, and the pose is computed with the scaled camera.  bundles (NodeOptions::bundles, alone among the extensions):
+        [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
+        self.max_tags, self.num_streams = max_tags, num_streams
+        if bundles:
+            arr = _shell_bundles(bundles)
+            self._h = self._L.node_shell_multi_create_bundles(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
+                                                              decimate, 1 if auto_flush else 0, len(arr), arr, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         self._h = self._L.node_shell_multi_create_opts(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
                                                        decimate, 1 if auto_flush else 0, float(quad_sigma), int(max_width),
                                                        int(max_height), _rectify_flag(rectify), rw, rh, err, 1024)
@@ -199,6 +265,15 @@ class AprilTagMultiCameraNode:
             raise RuntimeError(err.value.decode())
         return rc == 1
 
+    def transforms(self, stream, max_out=128):
+        """The transforms of the last frame published for `stream`: the tags', then one per solved bundle."""
+        out = (ShellTransform * max_out)()
+        return _unpack_transforms(out, min(self._L.node_shell_multi_last_transforms(self._h, stream, out, max_out), max_out))
+
+    def bundle_poses(self, stream, max_out=8):
+        out = (ShellBundlePose * max_out)()
+        return _unpack_bundle_poses(out, min(self._L.node_shell_multi_last_bundle_poses(self._h, stream, out, max_out), max_out))
+
     def flush(self):
         return self._L.node_shell_multi_flush(self._h)
 
@@ -218,16 +293,25 @@ class AprilTagNode:
     """Parameters and defaults of the reference node (apriltag_node.cpp:564-568)."""
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None):
+                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None):
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
         (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
         three distortion models and the rotation R of that CameraInfo.  resize (NodeOptions::resize_width, resize_height):
         (w, h) -- the handle has that size, frames of any size are resized to it inside the submission, behind the rectification, and
-        the pose is computed with the camera scaled by w / width and h / height."""
+        the pose is computed with the camera scaled by w / width and h / height.  bundles (NodeOptions::bundles, alone among the
+        extensions): [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
+        self.max_tags = max_tags
+        if bundles:
+            arr = _shell_bundles(bundles)
+            self._h = self._L.node_shell_create_bundles(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                        len(arr), arr, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         self._h = self._L.node_shell_create_opts(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
                                                  1 if strict_cuapriltags_encodings else 0, float(quad_sigma), _rectify_flag(rectify),
                                                  rw, rh, err, 1024)
@@ -245,6 +329,15 @@ class AprilTagNode:
             self.close()
         except Exception:
             pass
+
+    def transforms(self, max_out=128):
+        """The transforms of the last published frame: the tags', then one per solved bundle."""
+        out = (ShellTransform * max_out)()
+        return _unpack_transforms(out, min(self._L.node_shell_last_transforms(self._h, out, max_out), max_out))
+
+    def bundle_poses(self, max_out=8):
+        out = (ShellBundlePose * max_out)()
+        return _unpack_bundle_poses(out, min(self._L.node_shell_last_bundle_poses(self._h, out, max_out), max_out))
 
     def on_frame(self, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0),
                  info_stamp=None, D=None, distortion_model=None, P12=None, R=None):

@@ -58,6 +58,24 @@ public:
     // rectification), in place of a ResizeNode in front of this one; the pose uses the camera scaled to that size.  0: off
     opt.resize_width = static_cast<uint32_t>(declare_parameter<int>("resize_width", 0));
     opt.resize_height = static_cast<uint32_t>(declare_parameter<int>("resize_height", 0));
+    // tag bundles (planar boards solved per frame inside the detector's submission): bundle_names lists them, bundle_members holds five
+    // numbers per member -- index into bundle_names, tag id, x, y of the tag centre on the board plane and its size, in metres.  One
+    // "bundle:<name>" transform is broadcast per solved bundle.  Empty: off
+    {
+      const std::vector<std::string> names = declare_parameter<std::vector<std::string>>("bundle_names", std::vector<std::string>());
+      const std::vector<double> members = declare_parameter<std::vector<double>>("bundle_members", std::vector<double>());
+      for (const auto & n : names) {
+        shell::Bundle b;
+        b.name = n;
+        opt.bundles.push_back(b);
+      }
+      for (size_t i = 0; i + 4 < members.size(); i += 5) {
+        const size_t which = static_cast<size_t>(members[i]);
+        if (which < opt.bundles.size()) {
+          opt.bundles[which].members.push_back({static_cast<uint32_t>(members[i + 1]), members[i + 2], members[i + 3], members[i + 4]});
+        }
+      }
+    }
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);
