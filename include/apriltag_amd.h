@@ -412,6 +412,41 @@ int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const a
  * AMDAT_INVALID_ARGUMENT: null handle or out, bundles off, nframes beyond the last submission's, a submission in flight. */
 int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose_t* out, uint32_t nframes);
 
+/* Orthogonal-iteration tag pose with both minima, inside the submission (AprilRobotics' estimate_tag_pose: the object-space iteration
+ * of Lu, Hager and Mjolsness from two starts, the lower error returned).  Off by default; amdAprilTagsID_t and
+ * amdAprilTagsDetectionEx_t carry the homography pose whether it is on or off.
+ * With the mode on, every following submission refines, in one small launch behind the last detector stage, the records it hands out
+ * (the first min(kept, max_tags / max_dets) of every frame): two independent chains of `iterations` steps on the record's four corners
+ * under the frame's intrinsics and skew and the handle's tag_size -- chain 0 from the record's homography pose (R_h, t_h), chain 1 from
+ * its mirror about the viewing ray, (2 c c^T - I) R_h diag(-1, -1, 1) with c = t_h / |t_h|, the other minimum of the planar two-fold
+ * ambiguity.  The chain with the smaller object-space error E is chosen, a tie goes to chain 0; the other is reported beside it, so
+ * that a caller with a second view can decide otherwise.  DESIGN.md section 7e has every operation (csrc/pose_refine.h states it once
+ * for device and host; tests/pose_refine_ref.py in Python).  FP64 throughout. */
+#define AMDAT_POSE_REFINED 0u          /* both chains ran: R, t, err the chosen one's, R_alt, t_alt, err_alt the other's */
+#define AMDAT_POSE_REFINED_NO_ALT 1u   /* chain 1 was degenerate: R, t, err are chain 0's, the alternative fields zero */
+#define AMDAT_POSE_DEGENERATE 2u       /* chain 0 was degenerate: R, t the homography pose, err = err_homography, the alternative fields zero */
+#define AMDAT_MAX_POSE_ITERATIONS 200u
+/* chosen: the chain R, t come from (0 or 1).  R row-major, the tag frame in the camera frame, as a record's.  err, err_alt,
+ * err_homography: E(R, t) = sum over the corners of |(I - F_k)(R P_k + t)|^2 in square metres, F_k the projector onto corner k's
+ * viewing ray, P_k = tag_size / 2 * (c_k, 0); err_homography is E(R_h, t_h). */
+typedef struct {
+  uint32_t status, chosen;
+  double R[9], t[3], err;
+  double R_alt[9], t_alt[3], err_alt;
+  double err_homography;
+} amdAprilTagsRefinedPose_t;
+/* iterations = 0 turns the mode off (the default: nothing is launched or allocated), 1 .. AMDAT_MAX_POSE_ITERATIONS turn it on;
+ * upstream runs 50.  Applies to Detect[Color], DetectBatch[Color][Ex] and SubmitBatch[Color] / WaitBatch[Ex], on both launch sets;
+ * ThresholdOnly never runs it.  Callable whenever no submission is in flight.  AMDAT_INVALID_ARGUMENT: null handle, iterations above
+ * AMDAT_MAX_POSE_ITERATIONS, a submission in flight; AMDAT_OUT_OF_MEMORY: the record block could not be allocated.  A refused call
+ * leaves the previous setting in force.  Turning the mode on or off retires the handle's captured launch graphs, against the same
+ * budget of 24 as amdAprilTagsSetQuadSigma; changing only the count does not (it lives in device memory). */
+int amdAprilTagsSetPoseRefinement(amdAprilTagsHandle handle, uint32_t iterations);
+/* The refined poses of frame `frame` of the last completed submission: out[i] belongs to the i-th detection handed out for that frame;
+ * their number through *n.  AMDAT_INVALID_ARGUMENT: null handle, out or n, the mode off in that submission, `frame` beyond its frames,
+ * capacity below the frame's count (then *n still carries the count), a submission in flight. */
+int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsRefinedPose_t* out, uint32_t capacity, uint32_t* n);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

@@ -150,6 +150,10 @@ struct NodeOptions {
   // SOLVED bundle behind the tags' -- child frame "bundle:<name>", the camera info's header, as for tags -- and keep the frame's records
   // (last_bundle_poses).  Empty (the default): off.
   std::vector<Bundle> bundles;
+  // Extension: the orthogonal-iteration tag pose with both minima (amdAprilTagsSetPoseRefinement), set once when the handle is
+  // created: this many iterations per chain, 50 being AprilRobotics' estimate_tag_pose.  With it on, the pose of every detection and
+  // its "family:id" transform are the chosen refined pose in place of the homography pose.  0 (the default): off.
+  uint32_t pose_refinement = 0;
 };
 
 class AprilTagNode {

@@ -67,6 +67,16 @@ BUNDLE_SOLVED, BUNDLE_TOO_FEW_TAGS, BUNDLE_SINGULAR = 0, 1, 2
 MAX_BUNDLES, MAX_BUNDLE_MEMBERS = 8, 1024
 
 
+class RefinedPose(C.Structure):
+    """amdAprilTagsRefinedPose_t."""
+    _fields_ = [("status", C.c_uint32), ("chosen", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double),
+                ("R_alt", C.c_double * 9), ("t_alt", C.c_double * 3), ("err_alt", C.c_double), ("err_homography", C.c_double)]
+
+
+POSE_REFINED, POSE_REFINED_NO_ALT, POSE_DEGENERATE = 0, 1, 2
+MAX_POSE_ITERATIONS = 200
+
+
 class Float2(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float)]
 
@@ -110,7 +120,7 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes",
            "amdAprilTagsSetRectification", "amdAprilTagsSetResize", "amdAprilTagsDistortionFromName",
            "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex", "amdAprilTagsSetBundles", "amdAprilTagsGetBundlePoses",
-           "amdAprilTagsDebugLastGraphNodes"]
+           "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -196,6 +206,8 @@ def lib():
     L.amdAprilTagsDebugLastGraphNodes.argtypes = [H]
     L.amdAprilTagsSetBundles.argtypes = [H, C.c_uint32, C.POINTER(Bundle)]
     L.amdAprilTagsGetBundlePoses.argtypes = [H, C.POINTER(BundlePose), C.c_uint32]
+    L.amdAprilTagsSetPoseRefinement.argtypes = [H, C.c_uint32]
+    L.amdAprilTagsGetRefinedPoses.argtypes = [H, C.c_uint32, C.POINTER(RefinedPose), C.c_uint32, C.POINTER(C.c_uint32)]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)

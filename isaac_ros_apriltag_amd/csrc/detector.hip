@@ -27,6 +27,7 @@
 #include "kernels_decode_wave.h"
 #include "kernels_filter.h"
 #include "kernels_frontend.h"
+#include "kernels_pose.h"
 #include "kernels_quad.h"
 #include "kernels_quad_small.h"
 #include "kernels_threshold.h"
@@ -275,6 +276,13 @@ struct amdAprilTagsDetector_st {
   DevBuf<BundleMemberDev> d_bundle_members;             // AMDAT_MAX_BUNDLE_MEMBERS
   DevBuf<uint16_t> d_bundle_table;                      // one entry per code of every family of the handle
   BundlePoseRec* h_bposes = nullptr;                    // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_pose writes frame * nbundles + bundle
+  // amdAprilTagsSetPoseRefinement: k_pose_refine runs behind k_reconcile while pose_iterations > 0.  The count lives in device memory
+  // (d_pose_cfg[0]), so that changing it changes no launch argument; both buffers are allocated by the first call that turns the mode on
+  uint32_t pose_iterations = 0;                         // 0: off
+  bool last_pose_refined = false;                       // the last submission refined (amdAprilTagsGetRefinedPoses) ...
+  uint32_t last_ostride = 0;                            // ... with this many record slots per frame (finish_once reads it too)
+  DevBuf<uint32_t> d_pose_cfg;
+  PoseRefineRec* h_rposes = nullptr;                    // pinned, max_batch x dcap: k_pose_refine writes frame * ostride + record, as k_reconcile does
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -511,6 +519,7 @@ static void free_all(amdAprilTagsDetector_st* D) {
   if (D->h_rdesc) hipHostFree(D->h_rdesc);
   if (D->h_zdesc) hipHostFree(D->h_zdesc);
   if (D->h_bposes) hipHostFree(D->h_bposes);
+  if (D->h_rposes) hipHostFree(D->h_rposes);
   for (auto& e : D->ev) if (e) hipEventDestroy(e);
   if (D->own_stream) hipStreamDestroy(D->own_stream);
   for (auto& a : D->aux_stream) if (a) hipStreamDestroy(a);
@@ -1095,6 +1104,43 @@ int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose
   return AMDAT_SUCCESS;
 }
 
+int amdAprilTagsSetPoseRefinement(amdAprilTagsHandle handle, uint32_t iterations) {
+  if (!handle || iterations > AMDAT_MAX_POSE_ITERATIONS || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  static_assert(AMDAT_MAX_POSE_ITERATIONS == PR_MAX_ITERATIONS, "the header's bound is the kernel's");
+  const bool on = iterations > 0;
+  if (on) {
+    DeviceGuard guard(handle->device);
+    if (!guard.ok) return AMDAT_HIP_ERROR;
+    if (!handle->d_pose_cfg && !dev_alloc(handle, handle->d_pose_cfg, 64)) return AMDAT_OUT_OF_MEMORY;
+    if (!handle->h_rposes) {
+      const size_t bytes = (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseRefineRec);
+      if (hipHostMalloc((void**)&handle->h_rposes, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+        handle->h_rposes = nullptr;
+        (void)hipGetLastError();
+        return AMDAT_OUT_OF_MEMORY;
+      }
+      memset(handle->h_rposes, 0, bytes);
+    }
+    // (no submission is in flight: nothing reads the count; it is pageable, so the copy is waited for before it goes)
+    const hipStream_t s = handle->own_stream;
+    HIP_TRY(hipMemcpyAsync(handle->d_pose_cfg, &iterations, sizeof(iterations), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (on != (handle->pose_iterations > 0)) drop_graphs(handle);   // captured with or without the launch; the count itself lives in device memory
+  handle->pose_iterations = iterations;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsRefinedPose_t* out, uint32_t capacity, uint32_t* n) {
+  if (!handle || !out || !n || handle->inflight.active || !handle->last_pose_refined || frame >= handle->last_n) return AMDAT_INVALID_ARGUMENT;
+  uint32_t k = handle->h_counters[frame].nout;
+  if (k > handle->last_ostride) k = handle->last_ostride;
+  *n = k;
+  if (capacity < k) return AMDAT_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < k; i++) out[i] = handle->h_rposes[(size_t)frame * handle->last_ostride + i].pose;
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
   if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
   if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
@@ -1470,6 +1516,9 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   if (D->nbundles)   // S10: one wave per (frame, bundle) on the kept records, straight behind k_reconcile (kernels_bundle.h)
     hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
                        D->d_bundle_head, D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
+  if (D->pose_iterations)   // S11: both minima of the records handed out, eight lanes per record, beside the bundles (kernels_pose.h)
+    hipLaunchKernelGGL(k_pose_refine, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+                       D->d_pose_cfg, D->h_rposes, ostride, P);
   mark();
   return AMDAT_SUCCESS;
 }
@@ -1661,6 +1710,14 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
     // bundles on: k_bundle_pose, the last kernel, stamps its records the same way
     for (uint32_t r = 0; r < D->launched_n * D->nbundles; r++)
       if (reinterpret_cast<volatile BundlePoseRec*>(D->h_bposes)[r].seq != D->seq) return false;
+    // pose refinement on: k_pose_refine stamps every record it hands out (the counts are final: the frames' stamps were seen above)
+    if (D->pose_iterations)
+      for (uint32_t f = 0; f < D->launched_n; f++) {
+        uint32_t k = D->h_counters[f].nout;
+        if (k > D->last_ostride) k = D->last_ostride;
+        for (uint32_t i = 0; i < k; i++)
+          if (reinterpret_cast<volatile PoseRefineRec*>(D->h_rposes)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
+      }
     return true;
   };
   if (!stamped()) {
@@ -1756,6 +1813,8 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   D->last_nbundles = D->nbundles;
   D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
+  D->last_pose_refined = D->pose_iterations > 0;
+  D->last_ostride = ostride;
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
     D->pending_hash_grow = false;
     const GrowPlan g = plan_pending_hash(caps_of(D), D->grow);
@@ -1963,6 +2022,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   fill_frames(handle, n, images, nullptr, fmt);
   handle->last_n = n;
   handle->last_nbundles = 0;        // (never solves bundles)
+  handle->last_pose_refined = false;   // (never refines poses)
   handle->last_rectified = false;   // (never rectifies)
   handle->last_resized = false;     // (never resizes)
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));

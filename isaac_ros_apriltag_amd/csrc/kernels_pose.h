@@ -1,0 +1,100 @@
+// kernels_pose.h -- S11, the orthogonal-iteration tag pose with both minima (amdAprilTagsSetPoseRefinement).  The definition is
+// pose_refine.h, instantiated here with one corner per lane: eight lanes per record -- lanes 0 .. 3 run
+// chain 0 on corners 0 .. 3, lanes 4 .. 7 run chain 1 -- and every sum over the four corners is the two-step butterfly over the
+// lanes of a quad on the DPP network (quad_perm), which leaves (x0 + x1) + (x2 + x3) on all four.  FP64 throughout, one IEEE
+// operation per operator (-ffp-contract=off).  No LDS, no barrier, no scratch.
+#pragma once
+#include "common.h"
+#include "kernels_decode.h"   // pose_from_homography_dev
+#include "pose_refine.h"
+
+// A refined record in the pinned host block: the public record and the stamp of the launch that wrote it, stored last.
+struct PoseRefineRec {
+  amdAprilTagsRefinedPose_t pose;
+  uint32_t seq;
+  uint32_t pad;
+};
+
+#define PR_LANES_PER_RECORD 8
+#define PR_RECORDS_PER_WAVE (64 / PR_LANES_PER_RECORD)
+
+template <int CTRL>
+__device__ __forceinline__ double pr_quad_perm(double x) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+
+// Lane k of a quad holds x_k: (x0 + x1) + (x2 + x3) on every lane (addition commutes, so the four lanes form the same bits).
+struct PrSumQuad {
+  __device__ __forceinline__ double operator()(const double* x) const {
+    const double a = x[0] + pr_quad_perm<0xB1>(x[0]);   // quad_perm [1, 0, 3, 2]: the lane across bit 0
+    return a + pr_quad_perm<0x4E>(a);                   // quad_perm [2, 3, 0, 1]: the lane across bit 1
+  }
+};
+
+// Waves per frame of the launch that hands out `ostride` records per frame (a host-side figure: the grid depends on no device count).
+static inline uint32_t pose_refine_waves(uint32_t ostride) {
+  const uint32_t w = (ostride + PR_RECORDS_PER_WAVE - 1) / PR_RECORDS_PER_WAVE;   // (ostride <= dcap <= 65 535: at most 8 192)
+  return w < 1u ? 1u : w;
+}
+
+// grid (frames, pose_refine_waves(host_stride)), one wave per block: wave y of a frame refines records 8 y .. 8 y + 7 of the first
+// min(nout, host_stride) -- the records k_reconcile handed out; a wave beyond them returns.  cfg[0]: the iteration count (device
+// memory: changing it changes no launch argument).  Every lane of a wave that runs stays active through the iteration (a group
+// beyond the last record repeats that record and stores nothing), so that the DPP moves always read live lanes.
+__global__ __launch_bounds__(64) void k_pose_refine(const FrameDesc* __restrict__ frames, const DetRec* __restrict__ dets_all,
+                                                    const FrameCounters* __restrict__ counters, const uint16_t* __restrict__ order_all,
+                                                    const uint32_t* __restrict__ cfg, PoseRefineRec* __restrict__ host_out,
+                                                    uint32_t host_stride, DetParams P) {
+  const int frame = (int)blockIdx.x + P.frame0;
+  uint32_t nout = counters[frame].nout;
+  if (nout > P.dcap) nout = P.dcap;
+  if (nout > host_stride) nout = host_stride;
+  uint32_t iterations = cfg[0];
+  if (iterations > PR_MAX_ITERATIONS) iterations = PR_MAX_ITERATIONS;
+  const FrameDesc fd = frames[frame];
+  const DetRec* dets = dets_all + (size_t)frame * P.dcap;
+  const uint16_t* order = order_all + (size_t)frame * P.dcap;
+  const int lane = (int)threadIdx.x;
+  const int k = lane & 3;
+  const bool second = (lane & 4) != 0;
+  const PrSumQuad sum;
+
+  const uint32_t base = blockIdx.y * PR_RECORDS_PER_WAVE;
+  if (base >= nout) return;   // (the same on every lane)
+  const uint32_t i = base + (uint32_t)(lane / PR_LANES_PER_RECORD);
+  const bool live = i < nout;
+  const DetRec* d = &dets[order[live ? i : nout - 1]];
+  double Rh[9], th[3];
+  pose_from_homography_dev(d->H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, P.tag_size, Rh, th);
+
+  const double pix[1][2] = {{d->p[k][0], d->p[k][1]}};
+  PrPoints<1> C;
+  double Gi[6];
+  pr_setup<1>(pix, k, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, P.tag_size / 2.0, 4.0, sum, &C, Gi);
+  const double Eh = pr_error<1>(C, Rh, th, sum);
+  double Rm[9], Rs[9];
+  pr_mirror_start(Rh, th, Rm);
+#pragma unroll
+  for (int e = 0; e < 9; e++) Rs[e] = second ? POSE_CHAIN1_START(Rm[e], Rh[e]) : Rh[e];
+  double R[9], t[3], E;
+  const bool ok = pr_chain<1>(C, Gi, Rs, iterations, 4.0, sum, R, t, &E);
+
+  // the record's first lane takes chain 1's result from the lane four up, forms the outcome and stores the record; the stamp goes
+  // last, behind a system-wide fence, as k_reconcile's
+  const int src = (lane & ~7) | 4;
+  double R1[9], t1[3];
+#pragma unroll
+  for (int e = 0; e < 9; e++) R1[e] = __shfl(R[e], src);
+#pragma unroll
+  for (int e = 0; e < 3; e++) t1[e] = __shfl(t[e], src);
+  const double E1 = __shfl(E, src);
+  const bool ok1 = __shfl((int)ok, src) != 0;
+  if (live && (lane & 7) == 0) {
+    PoseRefineRec* o = &host_out[(size_t)frame * host_stride + i];
+    pr_outcome(ok, R, t, E, ok1, R1, t1, E1, Rh, th, Eh, &o->pose);
+    __threadfence_system();
+    __hip_atomic_store(&o->seq, fd.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}

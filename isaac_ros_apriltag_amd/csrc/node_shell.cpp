@@ -49,6 +49,8 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetRectificationEx) set_rectification_ex = nullptr;
   decltype(&amdAprilTagsSetBundles) set_bundles = nullptr;
   decltype(&amdAprilTagsGetBundlePoses) get_bundle_poses = nullptr;
+  decltype(&amdAprilTagsSetPoseRefinement) set_pose_refinement = nullptr;
+  decltype(&amdAprilTagsGetRefinedPoses) get_refined_poses = nullptr;
 };
 
 DetectorApi& api() {
@@ -90,6 +92,8 @@ DetectorApi& api() {
   BIND(set_rectification_ex, "amdAprilTagsSetRectificationEx")
   BIND(set_bundles, "amdAprilTagsSetBundles")
   BIND(get_bundle_poses, "amdAprilTagsGetBundlePoses")
+  BIND(set_pose_refinement, "amdAprilTagsSetPoseRefinement")
+  BIND(get_refined_poses, "amdAprilTagsGetRefinedPoses")
 #undef BIND
   return a;
 }
@@ -196,6 +200,29 @@ void apply_bundles(amdAprilTagsHandle detector, const NodeOptions& opt) {
   }
   const int error = api().set_bundles(detector, static_cast<uint32_t>(abi.size()), abi.data());
   if (error != 0) throw std::runtime_error("'bundles' refused (error code " + std::to_string(error) + ")");
+}
+
+// NodeOptions::pose_refinement on a freshly created handle
+void apply_pose_refinement(amdAprilTagsHandle detector, const NodeOptions& opt) {
+  if (opt.pose_refinement == 0) return;
+  const int error = api().set_pose_refinement(detector, opt.pose_refinement);
+  if (error != 0) throw std::runtime_error("'pose_refinement' " + std::to_string(opt.pose_refinement) + " refused (error code " + std::to_string(error) + ")");
+}
+
+// NodeOptions::pose_refinement: the pose of every tag of frame `frame` of the submission that just returned becomes the chosen refined
+// one (amdAprilTagsGetRefinedPoses: record i belongs to tag i) -- translation and column-major orientation in float, as the library
+// forms them from the homography pose.  (The node runs the default corner convention: R as solved.)
+bool refine_tags(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t frame, amdAprilTagsID_t* tags, uint32_t num_detections) {
+  if (opt.pose_refinement == 0) return true;
+  std::vector<amdAprilTagsRefinedPose_t> recs(num_detections ? num_detections : 1u);
+  uint32_t n = 0;
+  if (api().get_refined_poses(detector, frame, recs.data(), num_detections, &n) != 0 || n != num_detections) return false;
+  for (uint32_t i = 0; i < n; i++) {
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) tags[i].orientation[c * 3 + r] = static_cast<float>(recs[i].R[r * 3 + c]);
+    for (int k = 0; k < 3; k++) tags[i].translation[k] = static_cast<float>(recs[i].t[k]);
+  }
+  return true;
 }
 
 Quaternion quaternion_from_colmajor(const float* o);
@@ -455,6 +482,7 @@ struct AprilTagNode::Impl {
     }
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
+    apply_pose_refinement(detector, opt);
     width = info.width;
     height = info.height;
     if (!stream && api().stream_create(&stream) != 0) throw std::runtime_error("stream creation failed");
@@ -519,6 +547,10 @@ struct AprilTagNode::Impl {
     if (error != 0) {
       // the reference logs and drops the frame (src/apriltag_node.cpp:494-497)
       std::fprintf(stderr, "[apriltag_node] Failed to run AprilTags detector (error code %d)\n", error);
+      return;
+    }
+    if (!refine_tags(detector, opt, 0, tags.data(), num_detections)) {
+      std::fprintf(stderr, "[apriltag_node] refined poses not available: frame dropped\n");
       return;
     }
     AprilTagDetectionArray msg;
@@ -624,6 +656,7 @@ struct AprilTagMultiCameraNode::Impl {
     if (mixed && api().set_per_frame_sizes(detector, 1) != 0) throw std::runtime_error("per-frame image sizes refused");
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
+    apply_pose_refinement(detector, opt);
     width = cfg.width;
     height = cfg.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
@@ -795,6 +828,10 @@ uint32_t AprilTagMultiCameraNode::Flush() {
   std::vector<const Header*> headers(n);
   std::vector<std::vector<TransformStamped>*> tf_ptrs(n);
   for (uint32_t i = 0; i < n; i++) {
+    if (!refine_tags(I.detector, I.opt, i, tags.data() + static_cast<size_t>(i) * max_tags, counts[i])) {
+      std::fprintf(stderr, "[apriltag_node] refined poses not available: round dropped\n");
+      return 0;
+    }
     assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt.tag_family, &msgs[i], &tfs[i]);
     headers[i] = &I.slots[who[i]].info_header;
     tf_ptrs[i] = &tfs[i];
@@ -1014,6 +1051,24 @@ NodeShellHarness* node_shell_create_bundles(int max_tags, double size, int tile_
     return nullptr;
   }
 }
+// AprilTagNode with NodeOptions::pose_refinement (the other options at their defaults but those named)
+NodeShellHarness* node_shell_create_refined(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                            int decimate, uint32_t pose_refinement, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
 // the transforms of the last published frame (tags first, then one per solved bundle), and its bundle records
 int node_shell_last_transforms(NodeShellHarness* h, NodeShellTransform* out, int max_out) { return copy_transforms(h->last_tf, out, max_out); }
 int node_shell_last_bundle_poses(NodeShellHarness* h, NodeShellBundlePose* out, int max_out) {
@@ -1143,6 +1198,26 @@ MultiShellHarness* node_shell_multi_create_bundles(int num_streams, int max_tags
     o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     set_bundle_options(&o, nbundles, bundles);
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+MultiShellHarness* node_shell_multi_create_refined(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                   const char* backends, int decimate, int auto_flush, uint32_t pose_refinement,
+                                                   char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
     h->node->set_auto_flush(auto_flush != 0);

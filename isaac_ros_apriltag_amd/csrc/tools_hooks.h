@@ -40,7 +40,11 @@
 //                           15 = k_bundle_pose pairs board corner k of a member with the record's corner p[3 - k]: every solved bundle
 //                               gets a wrong pose (a frame without tags is unaffected)
 //                           16 = k_bundle_pose without the duplicate rule: the records of a (family, id) seen twice in a frame are used
-//                           (4 .. 16 change values only: no address, index bound, launch size or loop count)
+//                           17 = chain 1 of the pose refinement (pose_refine.h) starts at the homography pose itself, unmirrored: the
+//                               alternative of every refined record is the chosen pose again
+//                           18 = the pose refinement does not recompute t after the last iteration: every refined record carries the
+//                               last rotation with the translation of the one before
+//                           (4 .. 18 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -48,7 +52,8 @@
 //                           tests/test_rectify_submission_gpu.py::test_the_rectify_tests_fail_on_the_wrong_builds for 9 and 10,
 //                           tests/test_resize_submission_gpu.py::test_the_resize_tests_fail_on_the_wrong_builds for 11 and 12,
 //                           tests/test_camera_models_gpu.py::test_the_camera_model_tests_fail_on_the_wrong_builds for 13 and 14,
-//                           tests/test_bundles_gpu.py::test_the_bundle_tests_fail_on_the_wrong_builds for 15 and 16)
+//                           tests/test_bundles_gpu.py::test_the_bundle_tests_fail_on_the_wrong_builds for 15 and 16,
+//                           tests/test_pose_refine_gpu.py::test_the_pose_refinement_tests_fail_on_the_wrong_builds for 17 and 18)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -126,6 +131,18 @@
 #define BUNDLE_DUPLICATE(dup) ((void)(dup), false)
 #else
 #define BUNDLE_DUPLICATE(dup) (dup)
+#endif
+
+// ---- pose_refine.h: the start of chain 1, and whether t(R) follows step `it` of `iterations` -------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 17
+#define POSE_CHAIN1_START(mirrored, unmirrored) ((void)(mirrored), (unmirrored))
+#else
+#define POSE_CHAIN1_START(mirrored, unmirrored) ((void)(unmirrored), (mirrored))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 18
+#define POSE_T_FOLLOWS_STEP(it, iterations) ((it) + 1u < (iterations))
+#else
+#define POSE_T_FOLLOWS_STEP(it, iterations) ((void)(it), (void)(iterations), true)
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------

@@ -51,7 +51,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, **caps):
+                 bundles=None, pose_refinement=0, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -81,6 +81,7 @@ class AprilTagDetector:
         self.per_frame_sizes = False
         self.resizing = False
         self.nbundles = 0
+        self.pose_refinement = 0
         try:
             if quad_sigma:
                 self.set_quad_sigma(quad_sigma)
@@ -92,6 +93,8 @@ class AprilTagDetector:
                 self.set_resize(resize)
             if bundles:
                 self.set_bundles(bundles)
+            if pose_refinement:
+                self.set_pose_refinement(pose_refinement)
         except Exception:
             self.close()
             raise
@@ -145,6 +148,31 @@ class AprilTagDetector:
         return [[{"bundle": int(r.bundle), "status": int(r.status), "ntags": int(r.ntags), "nskipped": int(r.nskipped),
                   "R": np.array(list(r.R)).reshape(3, 3), "t": np.array(list(r.t)), "sq_err_sum": float(r.sq_err_sum)}
                  for r in out[f * self.nbundles:(f + 1) * self.nbundles]] for f in range(n)]
+
+    def set_pose_refinement(self, iterations):
+        """amdAprilTagsSetPoseRefinement: every following submission refines the records it hands out by orthogonal iteration from two
+        starts, `iterations` steps each (1 .. 200; upstream's estimate_tag_pose runs 50); 0 turns it off.  The detection records keep the
+        homography pose; refined_poses(n) hands out the refined ones."""
+        capi._check("amdAprilTagsSetPoseRefinement", self._L.amdAprilTagsSetPoseRefinement(self._h, int(iterations)))
+        self.pose_refinement = int(iterations)
+
+    def refined_poses(self, n):
+        """amdAprilTagsGetRefinedPoses: the refined poses of the first n frames of the last completed submission, a list per frame,
+        aligned by index with the frame's detections, of {"status", "chosen", "R" (3x3), "t", "err", "R_alt", "t_alt", "err_alt",
+        "err_homography"}."""
+        out = []
+        for f in range(n):
+            cnt = C.c_uint32(0)
+            probe = (capi.RefinedPose * 1)()
+            rc = self._L.amdAprilTagsGetRefinedPoses(self._h, f, probe, 0, C.byref(cnt))   # the count (refused for its capacity when > 0)
+            if rc and cnt.value == 0:
+                capi._check("amdAprilTagsGetRefinedPoses", rc)
+            arr = (capi.RefinedPose * max(cnt.value, 1))()
+            capi._check("amdAprilTagsGetRefinedPoses", self._L.amdAprilTagsGetRefinedPoses(self._h, f, arr, cnt.value, C.byref(cnt)))
+            out.append([{"status": int(r.status), "chosen": int(r.chosen), "R": np.array(list(r.R)).reshape(3, 3), "t": np.array(list(r.t)),
+                         "err": float(r.err), "R_alt": np.array(list(r.R_alt)).reshape(3, 3), "t_alt": np.array(list(r.t_alt)),
+                         "err_alt": float(r.err_alt), "err_homography": float(r.err_homography)} for r in arr[:cnt.value]])
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

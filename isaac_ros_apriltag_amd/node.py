@@ -111,6 +111,11 @@ def lib():
         L.node_shell_multi_create_bundles.restype = C.c_void_p
         L.node_shell_multi_create_bundles.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                                       C.c_int, C.POINTER(ShellBundle), C.c_char_p, C.c_size_t]
+        L.node_shell_create_refined.restype = C.c_void_p
+        L.node_shell_create_refined.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_refined.restype = C.c_void_p
+        L.node_shell_multi_create_refined.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32,
+                                                      C.c_char_p, C.c_size_t]
         L.node_shell_last_transforms.restype = C.c_int
         L.node_shell_last_transforms.argtypes = [C.c_void_p, C.POINTER(ShellTransform), C.c_int]
         L.node_shell_last_bundle_poses.restype = C.c_int
@@ -215,18 +220,28 @@ class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None):
+                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None, pose_refinement=0):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
         undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
         (NodeOptions::rectify_full): with any of the three distortion models and the rotation R of its CameraInfo.  resize
         (NodeOptions::resize_width, resize_height): (w, h) -- frames of any size are resized to it inside the submission, behind the
         rectification, and the pose is computed with the scaled camera.  bundles (NodeOptions::bundles, alone among the extensions):
-        [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'."""
+        [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'.
+        pose_refinement (NodeOptions::pose_refinement, alone among the extensions): iterations of the orthogonal-iteration pose -- the
+        detections' poses and the tags' transforms are the chosen refined pose."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags, self.num_streams = max_tags, num_streams
+        if pose_refinement:
+            if bundles or quad_sigma or max_width or max_height or rectify or resize:
+                raise ValueError("pose_refinement is served alone by this view: not with bundles, quad_sigma, max_width / max_height, rectify or resize")
+            self._h = self._L.node_shell_multi_create_refined(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
+                                                              decimate, 1 if auto_flush else 0, int(pose_refinement), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if bundles:
             arr = _shell_bundles(bundles)
             self._h = self._L.node_shell_multi_create_bundles(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
@@ -293,18 +308,29 @@ class AprilTagNode:
     """Parameters and defaults of the reference node (apriltag_node.cpp:564-568)."""
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None):
+                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None, pose_refinement=0):
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
         (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
         three distortion models and the rotation R of that CameraInfo.  resize (NodeOptions::resize_width, resize_height):
         (w, h) -- the handle has that size, frames of any size are resized to it inside the submission, behind the rectification, and
         the pose is computed with the camera scaled by w / width and h / height.  bundles (NodeOptions::bundles, alone among the
-        extensions): [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'."""
+        extensions): [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'.
+        pose_refinement (NodeOptions::pose_refinement, alone among the extensions): iterations of the orthogonal-iteration pose -- the
+        detections' poses and the tags' transforms are the chosen refined pose."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags = max_tags
+        if pose_refinement:
+            if bundles or quad_sigma or rectify or resize or strict_cuapriltags_encodings:
+                raise ValueError("pose_refinement is served alone by this view: not with bundles, quad_sigma, rectify, resize or "
+                                 "strict_cuapriltags_encodings")
+            self._h = self._L.node_shell_create_refined(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                        int(pose_refinement), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if bundles:
             arr = _shell_bundles(bundles)
             self._h = self._L.node_shell_create_bundles(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,

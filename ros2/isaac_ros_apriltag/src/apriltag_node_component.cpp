@@ -76,6 +76,9 @@ public:
         }
       }
     }
+    // the orthogonal-iteration tag pose with both minima (AprilRobotics' estimate_tag_pose) inside the detector's submission: this many
+    // iterations per chain (50 upstream); the published poses and transforms are then the chosen refined pose.  0: off
+    opt.pose_refinement = static_cast<uint32_t>(declare_parameter<int>("pose_refinement_iterations", 0));
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);
