@@ -118,6 +118,12 @@ struct DetParams {
   FamilyDev fam[AT_MAX_FAMILIES];
 };
 
+// colour -> gray with the fixed-point BT.601 weights cv_bridge/OpenCV use for the reference's mono8 test input
+// (test/isaac_ros_apriltag_mono8_test.py): the one statement of amdAprilTagsConvertToMono8, the conversion launch and the front kernels
+__host__ __device__ __forceinline__ uint32_t gray_bt601(uint32_t r, uint32_t g, uint32_t b) {
+  return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
+}
+
 __device__ __forceinline__ uint32_t pack_point(int x, int y, int gx, int gy) {
   return ((uint32_t)x << 18) | ((uint32_t)y << 4) | ((uint32_t)(gx / 255 + 1) << 2) | (uint32_t)(gy / 255 + 1);
 }

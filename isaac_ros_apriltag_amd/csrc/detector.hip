@@ -152,6 +152,13 @@ struct DevAlloc {
 template <class T> struct DevBuf : DevAlloc {
   operator T*() const { return static_cast<T*>(p); }
 };
+// A pinned host block the handle owns (host_alloc); free_all releases every one that was allocated.
+struct HostAlloc {
+  void* p = nullptr;
+};
+template <class T> struct HostBuf : HostAlloc {
+  operator T*() const { return static_cast<T*>(p); }
+};
 }  // namespace
 
 // Scratch of one k_fit_quads class (launch_plan.h: FqClassSpec); k_fit_small keeps its moments in LDS and has none.
@@ -216,9 +223,10 @@ struct amdAprilTagsDetector_st {
   uint32_t lcap_div = 0;             // long-record capacity = point capacity / lcap_div (alloc_point_buffers; halves when the long records overflow)
   bool unusable = false;             // a capacity change failed twice (grown and original size): buffers are gone, every later call reports it
   // pinned host buffers
-  FrameDesc* h_frames = nullptr;
-  FrameCounters* h_counters = nullptr;
-  DetRec* h_out = nullptr;
+  HostBuf<FrameDesc> h_frames;
+  HostBuf<FrameCounters> h_counters;
+  HostBuf<DetRec> h_out;
+  std::vector<HostAlloc*> host_owned;   // every pinned holder that has had an allocation (host_alloc): what free_all releases
   // profiling
   bool profiling = false;
   bool fq_counters = false;  // per-phase cycle counters inside k_fit_quads (profiling level 2; perturbs timing)
@@ -254,19 +262,17 @@ struct amdAprilTagsDetector_st {
   QsTaps qs = {};
   // amdAprilTagsSetPerFrameSizes: every frame of a submission brings its own size, up to the handle's (check_images, fill_frames)
   bool per_frame_sizes = false;
-  // amdAprilTagsSetRectification: frame i of a submission is undistorted with rect_models[i % size] into slot i of the rectified plane
-  // (d_conv: a rectified submission never takes the conversion launch) by k_rectify_frames, and the pipeline sees that slot as a mono8 frame
+  // The front stage.  amdAprilTagsSetRectification: frame i of a submission is undistorted with rect_models[i % size] into slot i of
+  // the front plane (d_conv: such a submission never takes the conversion launch) by k_rectify_frames, and the pipeline sees that slot
+  // as a mono8 frame.  amdAprilTagsSetResize: frame i, at any source size, is resized to resize_sizes[i % size] into the same slot by
+  // k_resize_frames -- through the rectification where that is on, in place of k_rectify_frames -- and detected there
   std::vector<amdAprilTagsCameraModelEx_t> rect_models; // empty: off (amdAprilTagsSetRectification stores plumb_bob, R = I)
   bool rect_general = false;                            // some model needs the general projection: the front launch is the _general kernel
-  RectDesc* h_rdesc = nullptr;                          // pinned, one per batch slot: k_prologue uploads them with the frame descriptors
-  DevBuf<RectDesc> d_rdesc;
-  std::vector<amdAprilTagsImageInput_t> rect_imgs;      // the plane's slots as the mono8 images of the submission (fill_rect)
-  bool last_rectified = false;                          // the last submission rectified (AMDAT_DBG_RECTIFIED)
-  // amdAprilTagsSetResize: frame i of a submission, at any source size, is resized to resize_sizes[i % size] into slot i of the same
-  // plane by k_resize_frames -- through the rectification where that is on, in place of k_rectify_frames -- and detected there
   std::vector<amdAprilTagsSize_t> resize_sizes;         // empty: off
-  ResizeDesc* h_zdesc = nullptr;                        // pinned, one per batch slot, uploaded by k_prologue
-  DevBuf<ResizeDesc> d_zdesc;
+  HostBuf<FrontDesc> h_front;                           // pinned, one per batch slot: k_prologue uploads them with the frame descriptors
+  DevBuf<FrontDesc> d_front;
+  std::vector<amdAprilTagsImageInput_t> front_imgs;     // the plane's slots as the mono8 images of the submission (fill_front)
+  bool last_rectified = false;                          // the last submission formed the rectified plane (AMDAT_DBG_RECTIFIED)
   bool last_resized = false;                            // the last submission resized (AMDAT_DBG_RESIZED)
   // amdAprilTagsSetBundles: k_bundle_pose runs behind k_reconcile while nbundles > 0.  The device layout (bundle_layout.h) is allocated
   // once, at its largest size, by the first call that turns the feature on, so that a later layout changes no launch argument
@@ -275,14 +281,14 @@ struct amdAprilTagsDetector_st {
   DevBuf<BundleHeadDev> d_bundle_head;
   DevBuf<BundleMemberDev> d_bundle_members;             // AMDAT_MAX_BUNDLE_MEMBERS
   DevBuf<uint16_t> d_bundle_table;                      // one entry per code of every family of the handle
-  BundlePoseRec* h_bposes = nullptr;                    // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_pose writes frame * nbundles + bundle
+  HostBuf<BundlePoseRec> h_bposes;                      // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_pose writes frame * nbundles + bundle
   // amdAprilTagsSetPoseRefinement: k_pose_refine runs behind k_reconcile while pose_iterations > 0.  The count lives in device memory
   // (d_pose_cfg[0]), so that changing it changes no launch argument; both buffers are allocated by the first call that turns the mode on
   uint32_t pose_iterations = 0;                         // 0: off
   bool last_pose_refined = false;                       // the last submission refined (amdAprilTagsGetRefinedPoses) ...
   uint32_t last_ostride = 0;                            // ... with this many record slots per frame (finish_once reads it too)
   DevBuf<uint32_t> d_pose_cfg;
-  PoseRefineRec* h_rposes = nullptr;                    // pinned, max_batch x dcap: k_pose_refine writes frame * ostride + record, as k_reconcile does
+  HostBuf<PoseRefineRec> h_rposes;                      // pinned, max_batch x dcap: k_pose_refine writes frame * ostride + record, as k_reconcile does
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -300,20 +306,22 @@ __global__ void k_debug_math(int op, uint32_t n, const double* a, const double* 
   else out[i] = div_by(a[i], b[i], shared_recip(b[i]));   // the line fit's shared-reciprocal division
 }
 
-// colour -> mono8 with the fixed-point BT.601 weights cv_bridge/OpenCV use for the reference's mono8
-// test input (test/isaac_ros_apriltag_mono8_test.py): Y = (4899 R + 9617 G + 1868 B + 8192) >> 14
+// colour -> mono8 (gray_bt601, common.h): four adjacent pixels of row blockIdx.y per thread, the body of both kernels below
 template <int NCH, int RIDX, int BIDX>
-__global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ src, size_t spitch, uint8_t* __restrict__ dst,
-                                                  size_t dpitch, uint32_t w, uint32_t h) {
+__device__ __forceinline__ void to_mono8_row(const uint8_t* __restrict__ src, size_t spitch, uint8_t* __restrict__ dst, size_t dpitch,
+                                             uint32_t w, uint32_t h) {
   const uint32_t x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
   const uint32_t y = blockIdx.y;
   if (x4 >= w || y >= h) return;
   const uint8_t* s = src + (size_t)y * spitch + (size_t)x4 * NCH;
   uint8_t* d = dst + (size_t)y * dpitch + x4;
-  for (uint32_t k = 0; k < 4 && x4 + k < w; k++) {
-    const uint32_t R = s[k * NCH + RIDX], G = s[k * NCH + 1], B = s[k * NCH + BIDX];
-    d[k] = (uint8_t)((4899u * R + 9617u * G + 1868u * B + 8192u) >> 14);
-  }
+  for (uint32_t k = 0; k < 4 && x4 + k < w; k++) d[k] = (uint8_t)gray_bt601(s[k * NCH + RIDX], s[k * NCH + 1], s[k * NCH + BIDX]);
+}
+
+template <int NCH, int RIDX, int BIDX>
+__global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ src, size_t spitch, uint8_t* __restrict__ dst,
+                                                  size_t dpitch, uint32_t w, uint32_t h) {
+  to_mono8_row<NCH, RIDX, BIDX>(src, spitch, dst, dpitch, w, h);
 }
 
 // The same conversion for the frames of a colour submission that does not take the fused loader of k_threshold (decimate > 1,
@@ -322,16 +330,7 @@ __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ sr
 template <int NCH, int RIDX, int BIDX>
 __global__ __launch_bounds__(256) void k_to_mono8_frames(const FrameDesc* __restrict__ frames) {
   const FrameDesc fd = frames[blockIdx.z];
-  const uint32_t w = (uint32_t)fd.W0, h = (uint32_t)fd.H0;
-  const uint32_t x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  const uint32_t y = blockIdx.y;
-  if (x4 >= w || y >= h) return;
-  const uint8_t* s = fd.src + (size_t)y * fd.src_pitch + (size_t)x4 * NCH;
-  uint8_t* d = const_cast<uint8_t*>(fd.img) + (size_t)y * fd.pitch + x4;
-  for (uint32_t k = 0; k < 4 && x4 + k < w; k++) {
-    const uint32_t R = s[k * NCH + RIDX], G = s[k * NCH + 1], B = s[k * NCH + BIDX];
-    d[k] = (uint8_t)((4899u * R + 9617u * G + 1868u * B + 8192u) >> 14);
-  }
+  to_mono8_row<NCH, RIDX, BIDX>(fd.src, fd.src_pitch, const_cast<uint8_t*>(fd.img), fd.pitch, (uint32_t)fd.W0, (uint32_t)fd.H0);
 }
 
 // quad_sigma's taps, computed on the host once per setting: ksz = (int)(4 |sigma|) made odd, h = ksz / 2,
@@ -509,17 +508,21 @@ static bool dev_regrow(amdAprilTagsDetector_st* D, DevAlloc& b, size_t bytes) {
   return true;
 }
 
+// The same for pinned host memory the kernels read (descriptors) and write (records, counters + stamp) over the bus: COHERENT
+// (fine-grained) mapped memory, stated rather than left to the runtime's default -- the host reads it right after a stream wait, not
+// after a device-wide one -- and zeroed.  Not counted in device_bytes.  A failed allocation leaves nothing behind, as dev_alloc's.
+static bool host_alloc(amdAprilTagsDetector_st* D, HostAlloc& b, size_t bytes) {
+  if (hipHostMalloc(&b.p, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return false; }
+  memset(b.p, 0, bytes);
+  D->host_owned.push_back(&b);
+  return true;
+}
+
 static void free_all(amdAprilTagsDetector_st* D) {
   for (auto& g : D->graphs) if (g.exec) hipGraphExecDestroy(g.exec);
   for (hipGraphExec_t e : D->retired_graphs) hipGraphExecDestroy(e);
   for (DevAlloc* b : D->owned) dev_free(D, *b);   // (d_counters and d_ptprof point into d_workctl's and d_fqprof's allocations)
-  if (D->h_frames) hipHostFree(D->h_frames);
-  if (D->h_counters) hipHostFree(D->h_counters);
-  if (D->h_out) hipHostFree(D->h_out);
-  if (D->h_rdesc) hipHostFree(D->h_rdesc);
-  if (D->h_zdesc) hipHostFree(D->h_zdesc);
-  if (D->h_bposes) hipHostFree(D->h_bposes);
-  if (D->h_rposes) hipHostFree(D->h_rposes);
+  for (HostAlloc* b : D->host_owned) hipHostFree(b->p);
   for (auto& e : D->ev) if (e) hipEventDestroy(e);
   if (D->own_stream) hipStreamDestroy(D->own_stream);
   for (auto& a : D->aux_stream) if (a) hipStreamDestroy(a);
@@ -766,14 +769,8 @@ int amdCreateAprilTagsDetectorEx(amdAprilTagsHandle* handle, const amdAprilTagsC
                hipStreamSynchronize(D->own_stream) != hipSuccess)) ok = false;   // (`fams` is pageable: waited for before it goes)
     P.fam[i].codes = D->d_codes[i];
   }
-  // pinned blocks the kernels read (descriptors) and write (records, counters + stamp) over the bus: COHERENT (fine-grained) host
-  // memory, stated rather than left to the runtime's default -- the host reads them right after a stream wait, not after a
-  // device-wide one
-  const unsigned host_flags = hipHostMallocCoherent | hipHostMallocMapped;
-  if (ok && hipHostMalloc((void**)&D->h_frames, B * sizeof(FrameDesc), host_flags) != hipSuccess) ok = false;
-  if (ok && hipHostMalloc((void**)&D->h_counters, B * sizeof(FrameCounters), host_flags) != hipSuccess) ok = false;
-  if (ok && hipHostMalloc((void**)&D->h_out, B * (size_t)P.dcap * sizeof(DetRec), host_flags) != hipSuccess) ok = false;
-  if (ok) memset(D->h_counters, 0, B * sizeof(FrameCounters));
+  ok = ok && host_alloc(D, D->h_frames, B * sizeof(FrameDesc)) && host_alloc(D, D->h_counters, B * sizeof(FrameCounters)) &&
+       host_alloc(D, D->h_out, B * (size_t)P.dcap * sizeof(DetRec));
   for (auto& e : D->ev) if (ok && hipEventCreate(&e) != hipSuccess) ok = false;
   // Side streams.  The persistent grids of the fit's classes each hold the whole chip's wave slots, so which class's workgroups
   // are placed first decides who runs beside whom.  A handle sized for throughput (more than eight frames per submission) gets
@@ -925,24 +922,22 @@ int amdAprilTagsSetPerFrameSizes(amdAprilTagsHandle handle, int enable) {
   return AMDAT_SUCCESS;
 }
 
-// What the first call that turns rectification on allocates: the rectified plane (max_batch full-size mono8 frames: d_conv, with its
-// pitch) and the descriptor blocks of k_rectify_frames.
-static int ensure_rect_buffers(amdAprilTagsDetector_st* D) {
+// The handle's full-size mono8 plane, max_batch slots at conv_pitch: the front plane of rectified and resized submissions, and the
+// plane of colour submissions that take the conversion launch (no submission is both).
+static int ensure_conv_plane(amdAprilTagsDetector_st* D) {
+  if (D->d_conv) return AMDAT_SUCCESS;
+  D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
+  return dev_alloc(D, D->d_conv, D->cfg.max_batch * D->conv_pitch * D->cfg.height) ? AMDAT_SUCCESS : AMDAT_OUT_OF_MEMORY;
+}
+static uint8_t* conv_slot(const amdAprilTagsDetector_st* D, uint32_t i) { return D->d_conv + (size_t)i * D->conv_pitch * D->cfg.height; }
+
+// What the first call that turns rectification or the resize on allocates: the front plane and the descriptor blocks of the front kernels.
+static int ensure_front_buffers(amdAprilTagsDetector_st* D) {
   const size_t B = D->cfg.max_batch;
-  if (!D->d_conv) {
-    D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
-    if (!dev_alloc(D, D->d_conv, B * D->conv_pitch * D->cfg.height)) return AMDAT_OUT_OF_MEMORY;
-  }
-  if (!D->d_rdesc && !dev_alloc(D, D->d_rdesc, B * sizeof(RectDesc))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_rdesc) {
-    if (hipHostMalloc((void**)&D->h_rdesc, B * sizeof(RectDesc), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-      D->h_rdesc = nullptr;
-      (void)hipGetLastError();
-      return AMDAT_OUT_OF_MEMORY;
-    }
-    memset(D->h_rdesc, 0, B * sizeof(RectDesc));
-  }
-  D->rect_imgs.resize(B);
+  { const int rc = ensure_conv_plane(D); if (rc) return rc; }
+  if (!D->d_front && !dev_alloc(D, D->d_front, B * sizeof(FrontDesc))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->h_front && !host_alloc(D, D->h_front, B * sizeof(FrontDesc))) return AMDAT_OUT_OF_MEMORY;
+  D->front_imgs.resize(B);
   return AMDAT_SUCCESS;
 }
 
@@ -1012,32 +1007,11 @@ int amdAprilTagsSetRectificationEx(amdAprilTagsHandle handle, uint32_t ncams, co
   if (on != !handle->rect_models.empty()) {
     DeviceGuard guard(handle->device);
     if (!guard.ok) return AMDAT_HIP_ERROR;
-    if (on) { const int rc = ensure_rect_buffers(handle); if (rc) return rc; }
+    if (on) { const int rc = ensure_front_buffers(handle); if (rc) return rc; }
     drop_graphs(handle);   // captured with or without the rectification launch; the models themselves travel through the descriptors
   }
   handle->rect_models.assign(cams, cams + ncams);
   handle->rect_general = general;   // (which of the two front kernels a submission launches: a launch parameter, like the models no graph's concern -- see enqueue_submission)
-  return AMDAT_SUCCESS;
-}
-
-// What the first call that turns the resize on allocates: the plane rectification uses (d_conv) and the descriptor blocks of
-// k_resize_frames.
-static int ensure_resize_buffers(amdAprilTagsDetector_st* D) {
-  const size_t B = D->cfg.max_batch;
-  if (!D->d_conv) {
-    D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
-    if (!dev_alloc(D, D->d_conv, B * D->conv_pitch * D->cfg.height)) return AMDAT_OUT_OF_MEMORY;
-  }
-  if (!D->d_zdesc && !dev_alloc(D, D->d_zdesc, B * sizeof(ResizeDesc))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_zdesc) {
-    if (hipHostMalloc((void**)&D->h_zdesc, B * sizeof(ResizeDesc), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-      D->h_zdesc = nullptr;
-      (void)hipGetLastError();
-      return AMDAT_OUT_OF_MEMORY;
-    }
-    memset(D->h_zdesc, 0, B * sizeof(ResizeDesc));
-  }
-  D->rect_imgs.resize(B);
   return AMDAT_SUCCESS;
 }
 
@@ -1050,7 +1024,7 @@ int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdA
   if (on != !handle->resize_sizes.empty()) {
     DeviceGuard guard(handle->device);
     if (!guard.ok) return AMDAT_HIP_ERROR;
-    if (on) { const int rc = ensure_resize_buffers(handle); if (rc) return rc; }
+    if (on) { const int rc = ensure_front_buffers(handle); if (rc) return rc; }
     drop_graphs(handle);   // captured with or without the resize launch; the sizes themselves travel through the descriptors
   }
   handle->resize_sizes.assign(sizes, sizes + nsizes);
@@ -1062,15 +1036,7 @@ static int ensure_bundle_buffers(amdAprilTagsDetector_st* D, size_t table_entrie
   if (!D->d_bundle_head && !dev_alloc(D, D->d_bundle_head, sizeof(BundleHeadDev))) return AMDAT_OUT_OF_MEMORY;
   if (!D->d_bundle_members && !dev_alloc(D, D->d_bundle_members, AMDAT_MAX_BUNDLE_MEMBERS * sizeof(BundleMemberDev))) return AMDAT_OUT_OF_MEMORY;
   if (!D->d_bundle_table && !dev_alloc(D, D->d_bundle_table, table_entries * sizeof(uint16_t))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_bposes) {
-    const size_t bytes = (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(BundlePoseRec);
-    if (hipHostMalloc((void**)&D->h_bposes, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-      D->h_bposes = nullptr;
-      (void)hipGetLastError();
-      return AMDAT_OUT_OF_MEMORY;
-    }
-    memset(D->h_bposes, 0, bytes);
-  }
+  if (!D->h_bposes && !host_alloc(D, D->h_bposes, (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(BundlePoseRec))) return AMDAT_OUT_OF_MEMORY;
   return AMDAT_SUCCESS;
 }
 
@@ -1112,15 +1078,8 @@ int amdAprilTagsSetPoseRefinement(amdAprilTagsHandle handle, uint32_t iterations
     DeviceGuard guard(handle->device);
     if (!guard.ok) return AMDAT_HIP_ERROR;
     if (!handle->d_pose_cfg && !dev_alloc(handle, handle->d_pose_cfg, 64)) return AMDAT_OUT_OF_MEMORY;
-    if (!handle->h_rposes) {
-      const size_t bytes = (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseRefineRec);
-      if (hipHostMalloc((void**)&handle->h_rposes, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-        handle->h_rposes = nullptr;
-        (void)hipGetLastError();
-        return AMDAT_OUT_OF_MEMORY;
-      }
-      memset(handle->h_rposes, 0, bytes);
-    }
+    if (!handle->h_rposes && !host_alloc(handle, handle->h_rposes, (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseRefineRec)))
+      return AMDAT_OUT_OF_MEMORY;
     // (no submission is in flight: nothing reads the count; it is pageable, so the copy is waited for before it goes)
     const hipStream_t s = handle->own_stream;
     HIP_TRY(hipMemcpyAsync(handle->d_pose_cfg, &iterations, sizeof(iterations), hipMemcpyHostToDevice, s));
@@ -1226,12 +1185,7 @@ static int ensure_gray_plane(amdAprilTagsDetector_st* D) {
 // setter has allocated: no plane here.)
 static int ensure_colour_plane(amdAprilTagsDetector_st* D, uint32_t fmt, bool filt = false) {
   if (fmt == AMDAT_ENC_MONO8 || (filt && D->P.decimate == 1)) return AMDAT_SUCCESS;
-  const size_t B = D->cfg.max_batch;
-  if (colour_fused(D, fmt)) return ensure_gray_plane(D);
-  if (D->d_conv) return AMDAT_SUCCESS;
-  D->conv_pitch = ((size_t)D->cfg.width + 63) & ~(size_t)63;
-  const size_t bytes = B * D->conv_pitch * D->cfg.height;
-  return dev_alloc(D, D->d_conv, bytes) ? AMDAT_SUCCESS : AMDAT_OUT_OF_MEMORY;
+  return colour_fused(D, fmt) ? ensure_gray_plane(D) : ensure_conv_plane(D);
 }
 
 static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images,
@@ -1249,7 +1203,7 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
       D->h_frames[i].src = nullptr; D->h_frames[i].src_pitch = 0;
     } else {   // every stage behind the threshold pass (or the conversion launch) reads the handle's gray plane
       const bool fused = colour_fused(D, fmt);
-      D->h_frames[i].img = fused ? D->d_gray + (size_t)i * D->P.H * D->P.WS : D->d_conv + (size_t)i * D->conv_pitch * D->cfg.height;
+      D->h_frames[i].img = fused ? D->d_gray + (size_t)i * D->P.H * D->P.WS : conv_slot(D, i);
       D->h_frames[i].pitch = fused ? (uint32_t)D->P.WS : (uint32_t)D->conv_pitch;
       D->h_frames[i].src = images[i].dev_ptr;
       D->h_frames[i].src_pitch = (uint32_t)images[i].pitch;
@@ -1270,50 +1224,27 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
   }
 }
 
-// Rectification on: the descriptors of k_rectify_frames for the caller's frames (encoding fmt), and the plane's slots as the mono8
-// images the rest of the submission is filled from.
-static const amdAprilTagsImageInput_t* fill_rect(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
-  const uint32_t ncams = (uint32_t)D->rect_models.size();
-  for (uint32_t i = 0; i < n; i++) {
-    const amdAprilTagsCameraModelEx_t& m = D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)];   // (tools_hooks.h: i % ncams)
-    RectDesc& r = D->h_rdesc[i];
-    r.src = images[i].dev_ptr;
-    r.src_pitch = (uint32_t)images[i].pitch;
-    r.dst = D->d_conv + (size_t)i * D->conv_pitch * D->cfg.height;
-    r.dst_pitch = (uint32_t)D->conv_pitch;
-    r.fmt = fmt;
-    r.W0 = (int32_t)images[i].width; r.H0 = (int32_t)images[i].height;
-    camera_model_params(m, r.model, r.gen);
-    D->rect_imgs[i] = images[i];
-    D->rect_imgs[i].dev_ptr = r.dst;
-    D->rect_imgs[i].pitch = D->conv_pitch;
-  }
-  return D->rect_imgs.data();
-}
-
-// Resize on: the descriptors of k_resize_frames for the caller's frames (encoding fmt; with their camera models where rectification
-// is on too), and the plane's slots at the target sizes as the mono8 images the rest of the submission is filled from.
-static const amdAprilTagsImageInput_t* fill_resize(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
+// Rectification or resize on: the descriptors of the front kernel for the caller's frames (encoding fmt) -- each slot's target size,
+// which is its own where the resize is off, and its camera where rectification is on -- and the plane's slots at those sizes as the
+// mono8 images the rest of the submission is filled from.
+static const amdAprilTagsImageInput_t* fill_front(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
   const uint32_t nsizes = (uint32_t)D->resize_sizes.size(), ncams = (uint32_t)D->rect_models.size();
   for (uint32_t i = 0; i < n; i++) {
-    const amdAprilTagsSize_t& t = D->resize_sizes[RESIZE_SIZE_OF_SLOT(i, nsizes)];   // (tools_hooks.h: i % nsizes)
-    ResizeDesc& z = D->h_zdesc[i];
-    z.src = images[i].dev_ptr;
-    z.src_pitch = (uint32_t)images[i].pitch;
-    z.dst = D->d_conv + (size_t)i * D->conv_pitch * D->cfg.height;
-    z.dst_pitch = (uint32_t)D->conv_pitch;
-    z.fmt = fmt;
-    z.SW = (int32_t)images[i].width; z.SH = (int32_t)images[i].height;
-    z.DW = (int32_t)t.width; z.DH = (int32_t)t.height;
-    z.rectify = ncams ? 1u : 0u;
-    if (ncams) {
-      camera_model_params(D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)], z.model, z.gen);
-    }
-    D->rect_imgs[i].width = t.width; D->rect_imgs[i].height = t.height;
-    D->rect_imgs[i].dev_ptr = z.dst;
-    D->rect_imgs[i].pitch = D->conv_pitch;
+    amdAprilTagsSize_t t = {images[i].width, images[i].height};
+    if (nsizes) t = D->resize_sizes[RESIZE_SIZE_OF_SLOT(i, nsizes)];   // (tools_hooks.h: i % nsizes)
+    FrontDesc& f = D->h_front[i];
+    f.src = images[i].dev_ptr;
+    f.src_pitch = (uint32_t)images[i].pitch;
+    f.dst = conv_slot(D, i);
+    f.dst_pitch = (uint32_t)D->conv_pitch;
+    f.fmt = fmt;
+    f.SW = (int32_t)images[i].width; f.SH = (int32_t)images[i].height;
+    f.DW = (int32_t)t.width; f.DH = (int32_t)t.height;
+    f.rectify = ncams ? 1u : 0u;
+    if (ncams) camera_model_params(D->rect_models[RECT_MODEL_OF_SLOT(i, ncams)], f.model, f.gen);   // (tools_hooks.h: i % ncams)
+    D->front_imgs[i] = {t.width, t.height, f.dst, D->conv_pitch};
   }
-  return D->rect_imgs.data();
+  return D->front_imgs.data();
 }
 
 // The quad_sigma filter of a submission: each frame's working image (decimate 1: `src`, mono8 or colour; otherwise `img` sampled at the
@@ -1401,10 +1332,10 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
 // and frame counters to zero (one block per frame)
 __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ host_frames, uint32_t* __restrict__ frames,
                                                  uint32_t* __restrict__ workctl, uint32_t* __restrict__ counters, int fd_words, int fc_words,
-                                                 const uint32_t* __restrict__ host_rdesc, uint32_t* __restrict__ rdesc, int rd_words) {
+                                                 const uint32_t* __restrict__ host_front, uint32_t* __restrict__ front, int front_words) {
   const int frame = (int)blockIdx.x, t = (int)threadIdx.x;
   for (int i = t; i < fd_words; i += 64) frames[frame * fd_words + i] = host_frames[frame * fd_words + i];
-  for (int i = t; i < rd_words; i += 64) rdesc[frame * rd_words + i] = host_rdesc[frame * rd_words + i];   // (rectification off: no words)
+  for (int i = t; i < front_words; i += 64) front[frame * front_words + i] = host_front[frame * front_words + i];   // (no front stage: no words)
   for (int i = t; i < fc_words; i += 64) counters[frame * fc_words + i] = 0u;
   if (frame == 0 && t < 32) workctl[t] = 0u;
 }
@@ -1532,12 +1463,11 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
   // descriptor upload + clears in one small kernel (it reads the pinned descriptor block over the bus itself): a copy
   // command and a fill command ahead of the first kernel cost a one-frame call about 15 us, this launch 4
   static_assert(sizeof(FrameDesc) % 4 == 0 && sizeof(FrameDesc) <= 256 && sizeof(FrameCounters) % 4 == 0 && sizeof(FrameCounters) <= 256, "k_prologue: one word per thread");
-  hipLaunchKernelGGL(k_prologue, dim3(n), dim3(64), 0, s, reinterpret_cast<const uint32_t*>(D->h_frames),
+  hipLaunchKernelGGL(k_prologue, dim3(n), dim3(64), 0, s, static_cast<const uint32_t*>(D->h_frames.p),
                      static_cast<uint32_t*>(D->d_frames.p), D->d_workctl, reinterpret_cast<uint32_t*>(D->d_counters),
                      (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4),
-                     resize ? reinterpret_cast<const uint32_t*>(D->h_zdesc) : reinterpret_cast<const uint32_t*>(D->h_rdesc),
-                     resize ? static_cast<uint32_t*>(D->d_zdesc.p) : static_cast<uint32_t*>(D->d_rdesc.p),
-                     resize ? (int)(sizeof(ResizeDesc) / 4) : rect ? (int)(sizeof(RectDesc) / 4) : 0);
+                     static_cast<const uint32_t*>(D->h_front.p), static_cast<uint32_t*>(D->d_front.p),
+                     resize || rect ? (int)(sizeof(FrontDesc) / 4) : 0);
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
@@ -1548,10 +1478,10 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
   const bool general = D->rect_general && !D->rect_models.empty();
   if (resize)
     hipLaunchKernelGGL(general ? k_resize_frames_general : k_resize_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
-                       D->d_zdesc);
+                       D->d_front);
   else if (rect)
     hipLaunchKernelGGL(general ? k_rectify_frames_general : k_rectify_frames, dim3((D->cfg.width + RF_BW - 1) / RF_BW, (D->cfg.height + RF_BH - 1) / RF_BH, n), dim3(256), 0, s,
-                       D->d_rdesc);
+                       D->d_front);
   mark();
   {
     const int rc = issue_pipeline(D, n, ostride, s, fmt, mark);
@@ -1706,17 +1636,17 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
   // there the call fails instead of handing out an earlier launch's records.
   auto stamped = [&]() {
     for (uint32_t f = 0; f < D->launched_n; f++)
-      if (reinterpret_cast<volatile FrameCounters*>(D->h_counters)[f].seq != D->seq) return false;
+      if (static_cast<volatile FrameCounters*>(D->h_counters)[f].seq != D->seq) return false;
     // bundles on: k_bundle_pose, the last kernel, stamps its records the same way
     for (uint32_t r = 0; r < D->launched_n * D->nbundles; r++)
-      if (reinterpret_cast<volatile BundlePoseRec*>(D->h_bposes)[r].seq != D->seq) return false;
+      if (static_cast<volatile BundlePoseRec*>(D->h_bposes)[r].seq != D->seq) return false;
     // pose refinement on: k_pose_refine stamps every record it hands out (the counts are final: the frames' stamps were seen above)
     if (D->pose_iterations)
       for (uint32_t f = 0; f < D->launched_n; f++) {
         uint32_t k = D->h_counters[f].nout;
         if (k > D->last_ostride) k = D->last_ostride;
         for (uint32_t i = 0; i < k; i++)
-          if (reinterpret_cast<volatile PoseRefineRec*>(D->h_rposes)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
+          if (static_cast<volatile PoseRefineRec*>(D->h_rposes)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
       }
     return true;
   };
@@ -1800,11 +1730,8 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
   D->last_resized = !D->resize_sizes.empty();
   D->last_rectified = !D->last_resized && !D->rect_models.empty();   // (resized: the rectified plane is never formed)
-  if (D->last_resized) {   // from here on a mono8 submission of the plane's slots at their target sizes
-    images = fill_resize(D, n, images, fmt);
-    fmt = AMDAT_ENC_MONO8;
-  } else if (D->last_rectified) {   // from here on a mono8 submission of the rectified plane's slots
-    images = fill_rect(D, n, images, fmt);
+  if (D->last_resized || D->last_rectified) {   // from here on a mono8 submission of the front plane's slots at their target sizes
+    images = fill_front(D, n, images, fmt);
     fmt = AMDAT_ENC_MONO8;
   }
   { const int crc = ensure_colour_plane(D, fmt, filt); if (crc) return crc; }
@@ -2170,22 +2097,14 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       if (host_dst) memcpy(host_dst, tmp.data(), npx < capacity ? npx : capacity);
       return AMDAT_SUCCESS;
     }
-    case AMDAT_DBG_RECTIFIED: {   // W0 x H0 dense: the frame's slot of the rectified plane
-      if (handle->rect_models.empty() || !handle->last_rectified) return AMDAT_INVALID_ARGUMENT;
-      const RectDesc& r = handle->h_rdesc[frame];
-      const size_t n0 = (size_t)r.W0 * r.H0;
+    case AMDAT_DBG_RECTIFIED:
+    case AMDAT_DBG_RESIZED: {   // DW x DH dense: the frame's slot of the front plane, where the last submission formed that plane
+      if (what == AMDAT_DBG_RESIZED ? handle->resize_sizes.empty() || !handle->last_resized : handle->rect_models.empty() || !handle->last_rectified)
+        return AMDAT_INVALID_ARGUMENT;
+      const FrontDesc& f = handle->h_front[frame];
+      const size_t n0 = (size_t)f.DW * f.DH;
       tmp.resize(n0);
-      HIP_TRY(hipMemcpy2D(tmp.data(), r.W0, r.dst, r.dst_pitch, r.W0, r.H0, hipMemcpyDeviceToHost));
-      *bytes = n0;
-      if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
-      return AMDAT_SUCCESS;
-    }
-    case AMDAT_DBG_RESIZED: {   // DW x DH dense: the frame's slot of the plane
-      if (handle->resize_sizes.empty() || !handle->last_resized) return AMDAT_INVALID_ARGUMENT;
-      const ResizeDesc& z = handle->h_zdesc[frame];
-      const size_t n0 = (size_t)z.DW * z.DH;
-      tmp.resize(n0);
-      HIP_TRY(hipMemcpy2D(tmp.data(), z.DW, z.dst, z.dst_pitch, z.DW, z.DH, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy2D(tmp.data(), f.DW, f.dst, f.dst_pitch, f.DW, f.DH, hipMemcpyDeviceToHost));
       *bytes = n0;
       if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
       return AMDAT_SUCCESS;

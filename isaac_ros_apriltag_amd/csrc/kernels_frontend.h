@@ -146,21 +146,25 @@ __global__ __launch_bounds__(256) void k_rectify_mono8_ex(const uint8_t* __restr
   dst[(size_t)y * dpitch + x] = out;
 }
 
-// ---- rectification inside the submission (amdAprilTagsSetRectification) -----------------------------------------------------------------
+// ---- the front stage of a submission: rectification (amdAprilTagsSetRectification) and resize (amdAprilTagsSetResize) ----------------
 // One descriptor per batch slot, written by the host for every submission and uploaded by k_prologue beside the FrameDescs: the
-// caller's frame (mono8 or interleaved colour, any base address and pitch), its own size, its camera, and the slot of the handle's
-// rectified plane it becomes.  Everything behind this launch sees a mono8 submission whose images are those slots.
-struct RectDesc {
+// caller's frame (mono8 or interleaved colour, any base address and pitch) at its own size SW x SH, its camera, the size DW x DH it
+// is detected at, and the slot of the handle's front plane it becomes.  Everything behind the front launch sees a mono8 submission
+// whose images are those slots.  The slot is S = resize(G), G the frame's gray plane at the source size: convert(frame), or
+// rectify(convert(frame)) with `rectify` set (section 7b's statement with w = SW, h = SH and `model`).  A rectify-only slot has
+// DW = SW, DH = SH and `rectify` set: k_rectify_frames writes G itself; k_resize_frames never writes G (a tap of the resize that
+// falls on G is computed where it is needed).
+struct FrontDesc {
   const uint8_t* src;
-  uint8_t* dst;          // 4-byte aligned, dst_pitch a multiple of 4 and >= W0 rounded up to 4: whole dwords are stored
+  uint8_t* dst;          // 4-byte aligned, dst_pitch a multiple of 4 and >= DW rounded up to 4: whole dwords are stored
   uint32_t src_pitch, dst_pitch;
   uint32_t fmt;          // amdAprilTagsEncoding of `src`
-  int32_t W0, H0;
-  uint32_t pad;
+  int32_t SW, SH, DW, DH;
+  uint32_t rectify;      // 0: G = convert(frame); 1: G = rectify(convert(frame)) with `model`
   RectifyParams model;
-  CamGeneral gen;        // gen.general: the slot's camera is not plumb_bob with R = I (k_rectify_frames_general switches on it, as on fmt)
+  CamGeneral gen;        // gen.general: the slot's camera is not plumb_bob with R = I (the _general kernels switch on it, as on fmt)
 };
-static_assert(sizeof(RectDesc) % 4 == 0, "k_prologue copies RectDesc one word per thread");
+static_assert(sizeof(FrontDesc) == 64 * 4, "k_prologue copies FrontDesc one word per thread");
 
 // The gray value of source pixel x of a row: mono8 as it stands, colour through the fixed-point BT.601 statement of
 // amdAprilTagsConvertToMono8 (k_to_mono8), so that R = rectify(convert(frame)).
@@ -168,8 +172,7 @@ template <int NCH, int RIDX, int BIDX, class Row>
 __device__ __forceinline__ uint32_t rect_gray(Row row, int x) {
   if (NCH == 1) return row[x];
   const Row p = row + (size_t)x * NCH;
-  const uint32_t r = p[RIDX], g = p[1], b = p[BIDX];
-  return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14;
+  return gray_bt601(p[RIDX], p[1], p[BIDX]);
 }
 
 #define RF_PX 4     // adjacent output pixels of a thread per row: one dword store
@@ -180,8 +183,8 @@ __device__ __forceinline__ uint32_t rect_gray(Row row, int x) {
 // A block of 256 threads covers RF_BW x RF_BH output pixels of frame blockIdx.z: a wave is 256 pixels wide, a thread RF_PX
 // columns by RF_ROWS rows.  The taps are gathered through the cache (neighbouring lanes read neighbouring source bytes).
 template <int NCH, int RIDX, int BIDX, bool GEN>
-__device__ __forceinline__ void rectify_frame_tile(const RectDesc& d) {
-  const int w = d.W0, h = d.H0;
+__device__ __forceinline__ void rectify_frame_tile(const FrontDesc& d) {
+  const int w = d.SW, h = d.SH;
   const int x4 = (int)blockIdx.x * RF_BW + (int)(threadIdx.x & 63) * RF_PX;
   const int ya = (int)blockIdx.y * RF_BH + (int)(threadIdx.x >> 6) * RF_ROWS;
   if (x4 >= w || ya >= h) return;
@@ -215,7 +218,7 @@ __device__ __forceinline__ void rectify_frame_tile(const RectDesc& d) {
 }
 
 template <bool GEN>
-__device__ __forceinline__ void rectify_frame_fmt(const RectDesc& d) {
+__device__ __forceinline__ void rectify_frame_fmt(const FrontDesc& d) {
   switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
     case 0: rectify_frame_tile<1, 0, 0, GEN>(d); break;
     case 1: rectify_frame_tile<3, 0, 2, GEN>(d); break;
@@ -226,38 +229,22 @@ __device__ __forceinline__ void rectify_frame_fmt(const RectDesc& d) {
 }
 
 // every slot's camera is plumb_bob with R = I
-__global__ __launch_bounds__(256) void k_rectify_frames(const RectDesc* __restrict__ descs) {
-  const RectDesc& d = descs[blockIdx.z];
-  if ((int)blockIdx.x * RF_BW >= d.W0 || (int)blockIdx.y * RF_BH >= d.H0) return;   // blocks beyond this frame's extent
+__global__ __launch_bounds__(256) void k_rectify_frames(const FrontDesc* __restrict__ descs) {
+  const FrontDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x * RF_BW >= d.SW || (int)blockIdx.y * RF_BH >= d.SH) return;   // blocks beyond this frame's extent
   rectify_frame_fmt<false>(d);
 }
 
 // Some slot's camera is of another kind or has a rotation: the same launch, with the general projection for the slots that say so.
 // (A kernel of its own, chosen by the host per submission, so that k_rectify_frames keeps its registers and occupancy.)
-__global__ __launch_bounds__(256) void k_rectify_frames_general(const RectDesc* __restrict__ descs) {
-  const RectDesc& d = descs[blockIdx.z];
-  if ((int)blockIdx.x * RF_BW >= d.W0 || (int)blockIdx.y * RF_BH >= d.H0) return;
+__global__ __launch_bounds__(256) void k_rectify_frames_general(const FrontDesc* __restrict__ descs) {
+  const FrontDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x * RF_BW >= d.SW || (int)blockIdx.y * RF_BH >= d.SH) return;
   if (d.gen.general) rectify_frame_fmt<true>(d);
   else rectify_frame_fmt<false>(d);
 }
 
-// ---- resize inside the submission (amdAprilTagsSetResize), fused with the rectification where that is on -----------------------------
-// One descriptor per batch slot, uploaded by k_prologue as RectDesc is: the caller's frame at its own size SW x SH, the target size
-// DW x DH of the slot, and the slot of the handle's plane (the one rectification uses) the resized frame S becomes.  S is
-// resize(G), G the frame's gray plane at the source size: convert(frame), or rectify(convert(frame)) with `rectify` set (section 7b's
-// statement with w = SW, h = SH and `model`).  G is never written: a tap of the resize that falls on G is computed where it is needed.
-struct ResizeDesc {
-  const uint8_t* src;
-  uint8_t* dst;          // 4-byte aligned, dst_pitch a multiple of 4 and >= DW rounded up to 4: whole dwords are stored
-  uint32_t src_pitch, dst_pitch;
-  uint32_t fmt;          // amdAprilTagsEncoding of `src`
-  int32_t SW, SH, DW, DH;
-  uint32_t rectify;      // 0: G = convert(frame); 1: G = rectify(convert(frame)) with `model`
-  RectifyParams model;
-  CamGeneral gen;        // as in RectDesc
-};
-static_assert(sizeof(ResizeDesc) % 4 == 0, "k_prologue copies ResizeDesc one word per thread");
-
+// ---- resize inside the submission, fused with the rectification where that is on ---------------------------------------------------
 // G(x, y) with rectification on, x's and y's terms of the projection given: the rectified value, 0 where it maps outside the source
 template <int NCH, int RIDX, int BIDX, bool GEN, class Src>
 __device__ __forceinline__ uint32_t rectified_gray(Src src, uint32_t pitch, const typename Proj<GEN>::Col& c, const typename Proj<GEN>::Row& r,
@@ -273,7 +260,7 @@ __device__ __forceinline__ uint32_t rectified_gray(Src src, uint32_t pitch, cons
 // column alone -- the resize position, and with RECT the projection terms of its two source columns -- is formed once for the rows;
 // what depends on the row alone once for the pixels.
 template <int NCH, int RIDX, int BIDX, bool RECT, bool GEN>
-__device__ __forceinline__ void resize_frame_tile(const ResizeDesc& d) {
+__device__ __forceinline__ void resize_frame_tile(const FrontDesc& d) {
   const int sw = d.SW, sh = d.SH, dw = d.DW, dh = d.DH;
   const int x4 = (int)blockIdx.x * RF_BW + (int)(threadIdx.x & 63) * RF_PX;
   const int ya = (int)blockIdx.y * RF_BH + (int)(threadIdx.x >> 6) * RF_ROWS;
@@ -321,7 +308,7 @@ __device__ __forceinline__ void resize_frame_tile(const ResizeDesc& d) {
 }
 
 template <bool RECT, bool GEN>
-__device__ __forceinline__ void resize_frame_fmt(const ResizeDesc& d) {
+__device__ __forceinline__ void resize_frame_fmt(const FrontDesc& d) {
   switch (d.fmt) {   // amdAprilTagsEncoding: mono8, rgb8, bgr8, rgba8, bgra8
     case 0: resize_frame_tile<1, 0, 0, RECT, GEN>(d); break;
     case 1: resize_frame_tile<3, 0, 2, RECT, GEN>(d); break;
@@ -331,16 +318,16 @@ __device__ __forceinline__ void resize_frame_fmt(const ResizeDesc& d) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_resize_frames(const ResizeDesc* __restrict__ descs) {
-  const ResizeDesc& d = descs[blockIdx.z];
+__global__ __launch_bounds__(256) void k_resize_frames(const FrontDesc* __restrict__ descs) {
+  const FrontDesc& d = descs[blockIdx.z];
   if ((int)blockIdx.x * RF_BW >= d.DW || (int)blockIdx.y * RF_BH >= d.DH) return;   // blocks beyond this frame's target extent
   if (d.rectify) resize_frame_fmt<true, false>(d);
   else resize_frame_fmt<false, false>(d);
 }
 
 // as k_rectify_frames_general: chosen by the host when some slot's camera needs the general projection
-__global__ __launch_bounds__(256) void k_resize_frames_general(const ResizeDesc* __restrict__ descs) {
-  const ResizeDesc& d = descs[blockIdx.z];
+__global__ __launch_bounds__(256) void k_resize_frames_general(const FrontDesc* __restrict__ descs) {
+  const FrontDesc& d = descs[blockIdx.z];
   if ((int)blockIdx.x * RF_BW >= d.DW || (int)blockIdx.y * RF_BH >= d.DH) return;
   if (d.rectify && d.gen.general) resize_frame_fmt<true, true>(d);
   else if (d.rectify) resize_frame_fmt<true, false>(d);
