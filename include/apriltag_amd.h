@@ -371,8 +371,8 @@ int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdA
  * A bundle is a planar board: members (family_index, id, x, y, size) with the tag centre (x, y) on the board plane in metres, size the
  * black-border edge in metres (the meaning of tag_size) and the tag axes parallel to the board axes -- corner k of a record,
  * p[k] = H(c_k) with c = (-1, 1), (1, 1), (1, -1), (-1, -1), is the board point (x + size / 2 * c_k.x, y + size / 2 * c_k.y).
- * family_index indexes the handle's family list, as amdAprilTagsDetectionEx_t.family does.  Members with in-plane quarter turns and
- * non-planar bundles are not served. */
+ * family_index indexes the handle's family list, as amdAprilTagsDetectionEx_t.family does.  Members turned in the plane and
+ * non-planar bundles go through amdAprilTagsSetBundlesEx below. */
 typedef struct { uint32_t family_index; uint32_t id; double x, y, size; } amdAprilTagsBundleMember_t;
 typedef struct {
   const amdAprilTagsBundleMember_t* members;
@@ -411,6 +411,57 @@ int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const a
 /* The bundle records of the last completed submission: nframes x nbundles, frame-major (out[f * nbundles + b]).
  * AMDAT_INVALID_ARGUMENT: null handle or out, bundles off, nframes beyond the last submission's, a submission in flight. */
 int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose_t* out, uint32_t nframes);
+
+/* Rigid 3-D tag bundles: cubes, rigs and boards with turned tags, solved as one rigid body per frame inside the submission.
+ * Every member carries a full pose in the bundle frame, as apriltag_ros' bundles do: R (row-major) and t give the TAG frame in the
+ * BUNDLE frame, size is the black-border edge in metres.  Corner k of a record, p[k] = H(c_k) with the c_k of amdAprilTagsSetBundles,
+ * is the bundle point R * (size / 2 * c_k.x, size / 2 * c_k.y, 0) + t.
+ * R must be a rotation as it stands: a member with max |R R^T - I| > 1e-6 or det R <= 0 is refused; the library repairs nothing. */
+typedef struct { uint32_t family_index; uint32_t id; double R[9]; double t[3]; double size; } amdAprilTagsBundleMemberEx_t;
+#define AMDAT_MAX_RIGID_BUNDLE_MEMBERS 64u   /* per bundle: one lane of the solving wave holds one tag */
+typedef struct {
+  const amdAprilTagsBundleMemberEx_t* members;
+  uint32_t nmembers;             /* 1 .. AMDAT_MAX_RIGID_BUNDLE_MEMBERS */
+  uint32_t max_hamming;          /* the gates and min_tags of amdAprilTagsBundle_t */
+  float min_decision_margin;
+  uint32_t min_tags;
+  uint32_t iterations;           /* 1 .. AMDAT_MAX_POSE_ITERATIONS steps of each of the two chains */
+  char name[32];                 /* at most 31 characters and the terminator: the node shell's child frame is "bundle:<name>" */
+} amdAprilTagsBundleEx_t;
+#define AMDAT_BUNDLE_DEGENERATE 3u   /* both chains were degenerate: R, t are the seed start, err its E, everything else zero */
+/* One record per (frame, bundle).  status: AMDAT_BUNDLE_SOLVED, AMDAT_BUNDLE_TOO_FEW_TAGS (every field behind nskipped zero) or
+ * AMDAT_BUNDLE_DEGENERATE.  ntags, nskipped as amdAprilTagsBundlePose_t's.  seed: the index, in the frame's canonical order, of the
+ * used record with the largest pixel area, whose homography pose starts both chains.  chosen: the chain R, t, err and sq_err_sum
+ * come from (0: from the seed's homography pose, 1: from its mirror about the viewing ray); the other chain's result is in the
+ * *_alt fields, which are zero where that chain was degenerate.  R (row-major), t: the bundle frame in the camera frame.  err:
+ * the object-space error E = sum over the 4 * ntags corners of |(I - F_j)(R P_j + t)|^2 in square metres; sq_err_sum: the sum of
+ * the squared pixel reprojection errors of the same corners, as amdAprilTagsBundlePose_t's. */
+typedef struct {
+  uint32_t bundle, status, ntags, nskipped, seed, chosen;
+  double R[9], t[3], err, sq_err_sum;
+  double R_alt[9], t_alt[3], err_alt, sq_err_sum_alt;
+} amdAprilTagsBundlePoseEx_t;
+/* nbundles = 0 turns the mode off (the default: nothing is launched or allocated).  Otherwise every following submission solves, in
+ * one small launch behind the last detector stage, one pose per frame and bundle from ALL kept records of the frame: classification,
+ * gates and the duplicate rule are amdAprilTagsSetBundles'; the pose is the object-space iteration of Lu, Hager and Mjolsness over
+ * the 4 * ntags general 3-D points, run as two chains of `iterations` steps with no early exit, the lower E chosen and a tie going to
+ * chain 0 (DESIGN.md section 7f has every operation; csrc/rigid_pose.h states it once for device and host, tests/rigid_bundle_ref.py
+ * in Python).  A non-coplanar used set has one minimum; a coplanar one (a single face in view) keeps the planar two-fold ambiguity,
+ * which the alternative reports.  FP64 throughout.  Composes with the other settings as amdAprilTagsSetBundles does, and runs beside
+ * amdAprilTagsSetPoseRefinement.
+ * The later of amdAprilTagsSetBundles / amdAprilTagsSetBundlesEx holds: one kind of bundle is on at a time, and turning one on
+ * turns the other off.
+ * Callable whenever no submission is in flight.  AMDAT_INVALID_ARGUMENT: everything amdAprilTagsSetBundles refuses (with the member
+ * total bounded by AMDAT_MAX_BUNDLES * AMDAT_MAX_RIGID_BUNDLE_MEMBERS), more than AMDAT_MAX_RIGID_BUNDLE_MEMBERS members in a
+ * bundle, a non-finite entry of R or t, an R with max |R R^T - I| > 1e-6 or det R <= 0, iterations = 0 or above
+ * AMDAT_MAX_POSE_ITERATIONS; AMDAT_OUT_OF_MEMORY: the device buffers could not be allocated.  A refused call leaves the previous
+ * setting in force.  A change of kind (planar <-> rigid) or on <-> off retires the handle's captured launch graphs, against the same
+ * budget of 24 as amdAprilTagsSetQuadSigma; a change of layout, iteration count or gates does not (they live in device memory). */
+int amdAprilTagsSetBundlesEx(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundleEx_t* bundles);
+/* The rigid bundle records of the last completed submission: nframes x nbundles, frame-major (out[f * nbundles + b]).
+ * AMDAT_INVALID_ARGUMENT: null handle or out, the last submission did not run this mode, nframes beyond the last submission's, a
+ * submission in flight. */
+int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePoseEx_t* out, uint32_t nframes);
 
 /* Orthogonal-iteration tag pose with both minima, inside the submission (AprilRobotics' estimate_tag_pose: the object-space iteration
  * of Lu, Hager and Mjolsness from two starts, the lower error returned).  Off by default; amdAprilTagsID_t and

@@ -110,6 +110,27 @@ struct BundlePose {
   double sq_err_sum = 0;            // squared pixel reprojection errors of the 4 * ntags corners, summed
 };
 
+// A rigid 3-D tag bundle (amdAprilTagsSetBundlesEx): a cube, a rig, a board with turned tags.  Every member carries its pose in the
+// bundle frame as apriltag_ros' bundles do -- the tag centre (x, y, z) in metres and the orientation as a quaternion (qw, qx, qy, qz),
+// which the shell divides by its norm before it forms the rotation -- and its black-border edge.
+struct RigidBundleMember { uint32_t id = 0; double x = 0, y = 0, z = 0; double qw = 1, qx = 0, qy = 0, qz = 0; double size = 0; };
+struct RigidBundle {
+  std::string name;                 // at most 31 characters: the TF child frame is "bundle:<name>"
+  std::vector<RigidBundleMember> members;   // at most 64
+  uint32_t max_hamming = 2;
+  double min_decision_margin = 0;
+  uint32_t min_tags = 1;
+  uint32_t iterations = 50;         // steps of each of the two chains
+};
+// The detector's record of one rigid bundle for one frame (amdAprilTagsBundlePoseEx_t): status 0 solved, 1 too few tags, 3 degenerate.
+struct RigidBundlePose {
+  std::string name;
+  uint32_t status = 0, ntags = 0, nskipped = 0, seed = 0, chosen = 0;
+  std::array<double, 9> R{}, R_alt{};   // row-major
+  std::array<double, 3> t{}, t_alt{};
+  double err = 0, sq_err_sum = 0, err_alt = 0, sq_err_sum_alt = 0;
+};
+
 // Parameters declared in the constructor of the reference node (src/apriltag_node.cpp:564-568).
 struct NodeOptions {
   int max_tags = 64;
@@ -150,6 +171,10 @@ struct NodeOptions {
   // SOLVED bundle behind the tags' -- child frame "bundle:<name>", the camera info's header, as for tags -- and keep the frame's records
   // (last_bundle_poses).  Empty (the default): off.
   std::vector<Bundle> bundles;
+  // Extension: rigid 3-D tag bundles, set once when the handle is created (amdAprilTagsSetBundlesEx), in place of `bundles` (one kind
+  // at a time: both set is an error).  Both nodes append one TransformStamped per SOLVED bundle behind the tags', from the chosen
+  // pose -- child frame "bundle:<name>" -- and keep the frame's records (last_rigid_bundle_poses).  Empty (the default): off.
+  std::vector<RigidBundle> rigid_bundles;
   // Extension: the orthogonal-iteration tag pose with both minima (amdAprilTagsSetPoseRefinement), set once when the handle is
   // created: this many iterations per chain, 50 being AprilRobotics' estimate_tag_pose.  With it on, the pose of every detection and
   // its "family:id" transform are the chosen refined pose in place of the homography pose.  0 (the default): off.
@@ -178,6 +203,8 @@ class AprilTagNode {
   bool initialized() const;
   // NodeOptions::bundles: the records of the last published frame, one per bundle in the options' order (empty: bundles off)
   const std::vector<BundlePose>& last_bundle_poses() const;
+  // NodeOptions::rigid_bundles: the same for the rigid kind
+  const std::vector<RigidBundlePose>& last_rigid_bundle_poses() const;
 
  private:
   struct Impl;
@@ -219,6 +246,7 @@ class AprilTagMultiCameraNode {
   const NodeOptions& options() const;
   // NodeOptions::bundles: the records of the last frame published for `stream`, one per bundle in the options' order
   const std::vector<BundlePose>& last_bundle_poses(uint32_t stream) const;
+  const std::vector<RigidBundlePose>& last_rigid_bundle_poses(uint32_t stream) const;
 
  private:
   struct Impl;

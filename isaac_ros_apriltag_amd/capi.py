@@ -67,6 +67,28 @@ BUNDLE_SOLVED, BUNDLE_TOO_FEW_TAGS, BUNDLE_SINGULAR = 0, 1, 2
 MAX_BUNDLES, MAX_BUNDLE_MEMBERS = 8, 1024
 
 
+class BundleMemberEx(C.Structure):
+    """amdAprilTagsBundleMemberEx_t: tag (family_index, id) with its pose (R row-major, t) in the bundle frame and its border edge."""
+    _fields_ = [("family_index", C.c_uint32), ("id", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("size", C.c_double)]
+
+
+class BundleEx(C.Structure):
+    """amdAprilTagsBundleEx_t."""
+    _fields_ = [("members", C.POINTER(BundleMemberEx)), ("nmembers", C.c_uint32), ("max_hamming", C.c_uint32),
+                ("min_decision_margin", C.c_float), ("min_tags", C.c_uint32), ("iterations", C.c_uint32), ("name", C.c_char * 32)]
+
+
+class BundlePoseEx(C.Structure):
+    """amdAprilTagsBundlePoseEx_t."""
+    _fields_ = [("bundle", C.c_uint32), ("status", C.c_uint32), ("ntags", C.c_uint32), ("nskipped", C.c_uint32), ("seed", C.c_uint32),
+                ("chosen", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double), ("sq_err_sum", C.c_double),
+                ("R_alt", C.c_double * 9), ("t_alt", C.c_double * 3), ("err_alt", C.c_double), ("sq_err_sum_alt", C.c_double)]
+
+
+BUNDLE_DEGENERATE = 3
+MAX_RIGID_BUNDLE_MEMBERS = 64
+
+
 class RefinedPose(C.Structure):
     """amdAprilTagsRefinedPose_t."""
     _fields_ = [("status", C.c_uint32), ("chosen", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double),
@@ -120,7 +142,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetQuadSigma", "amdAprilTagsDebugQuadSigmaTaps", "amdAprilTagsSetPerFrameSizes",
            "amdAprilTagsSetRectification", "amdAprilTagsSetResize", "amdAprilTagsDistortionFromName",
            "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex", "amdAprilTagsSetBundles", "amdAprilTagsGetBundlePoses",
-           "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses"]
+           "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses",
+           "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -206,6 +229,8 @@ def lib():
     L.amdAprilTagsDebugLastGraphNodes.argtypes = [H]
     L.amdAprilTagsSetBundles.argtypes = [H, C.c_uint32, C.POINTER(Bundle)]
     L.amdAprilTagsGetBundlePoses.argtypes = [H, C.POINTER(BundlePose), C.c_uint32]
+    L.amdAprilTagsSetBundlesEx.argtypes = [H, C.c_uint32, C.POINTER(BundleEx)]
+    L.amdAprilTagsGetBundlePosesEx.argtypes = [H, C.POINTER(BundlePoseEx), C.c_uint32]
     L.amdAprilTagsSetPoseRefinement.argtypes = [H, C.c_uint32]
     L.amdAprilTagsGetRefinedPoses.argtypes = [H, C.c_uint32, C.POINTER(RefinedPose), C.c_uint32, C.POINTER(C.c_uint32)]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -346,6 +371,36 @@ def bundles(specs):
         b.max_hamming = int(spec.get("max_hamming", 2))
         b.min_decision_margin = float(spec.get("min_decision_margin", 0.0))
         b.min_tags = int(spec.get("min_tags", 1))
+        name = spec.get("name", "").encode()
+        if len(name) > 31:
+            raise ValueError("a bundle name has at most 31 characters")
+        b.name = name
+    arr._keep = keep
+    return arr
+
+
+def bundles_ex(specs):
+    """[{"name", "iterations" (50), "members": [(family_index, id, R (3 x 3), t (3), size)], "max_hamming" (2), "min_decision_margin"
+    (0.0), "min_tags" (1)}] -> a ctypes array of amdAprilTagsBundleEx_t (None for an empty list); the member arrays it points into are
+    kept alive on the array."""
+    specs = list(specs or [])
+    if not specs:
+        return None
+    arr = (BundleEx * len(specs))()
+    keep = []
+    for b, spec in zip(arr, specs):
+        mem = list(spec["members"])
+        m = (BundleMemberEx * max(len(mem), 1))()
+        for dst, (fam, tid, R, t, size) in zip(m, mem):
+            dst.family_index, dst.id, dst.size = int(fam), int(tid), float(size)
+            dst.R = (C.c_double * 9)(*[float(v) for v in np.asarray(R, dtype=np.float64).reshape(-1)])
+            dst.t = (C.c_double * 3)(*[float(v) for v in np.asarray(t, dtype=np.float64).reshape(-1)])
+        keep.append(m)
+        b.members, b.nmembers = C.cast(m, C.POINTER(BundleMemberEx)), len(mem)
+        b.max_hamming = int(spec.get("max_hamming", 2))
+        b.min_decision_margin = float(spec.get("min_decision_margin", 0.0))
+        b.min_tags = int(spec.get("min_tags", 1))
+        b.iterations = int(spec.get("iterations", 50))
         name = spec.get("name", "").encode()
         if len(name) > 31:
             raise ValueError("a bundle name has at most 31 characters")

@@ -21,6 +21,7 @@
 #include "../../include/apriltag_amd_families.h"
 #include "common.h"
 #include "kernels_bundle.h"
+#include "kernels_rigid.h"
 #include "kernels_cc.h"
 #include "kernels_cluster.h"
 #include "kernels_decode.h"
@@ -282,6 +283,14 @@ struct amdAprilTagsDetector_st {
   DevBuf<BundleMemberDev> d_bundle_members;             // AMDAT_MAX_BUNDLE_MEMBERS
   DevBuf<uint16_t> d_bundle_table;                      // one entry per code of every family of the handle
   HostBuf<BundlePoseRec> h_bposes;                      // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_pose writes frame * nbundles + bundle
+  // amdAprilTagsSetBundlesEx: k_bundle_rigid runs behind k_reconcile while nrigid > 0 (then nbundles is 0: one kind is on at a time).  The
+  // device layout (rigid_layout.h) is allocated once, at its largest size, by the first call that turns the mode on
+  uint32_t nrigid = 0;                                  // 0: off
+  uint32_t last_nrigid = 0;                             // of the last submission (amdAprilTagsGetBundlePosesEx)
+  DevBuf<RigidHeadDev> d_rigid_head;
+  DevBuf<RigidMemberDev> d_rigid_members;               // RIGID_MAX_MEMBERS
+  DevBuf<uint16_t> d_rigid_table;                       // one entry per code of every family of the handle
+  HostBuf<RigidPoseRec> h_xposes;                       // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_rigid writes frame * nrigid + bundle
   // amdAprilTagsSetPoseRefinement: k_pose_refine runs behind k_reconcile while pose_iterations > 0.  The count lives in device memory
   // (d_pose_cfg[0]), so that changing it changes no launch argument; both buffers are allocated by the first call that turns the mode on
   uint32_t pose_iterations = 0;                         // 0: off
@@ -1058,8 +1067,11 @@ int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const a
     if (!L.table.empty()) HIP_TRY(hipMemcpyAsync(handle->d_bundle_table, L.table.data(), L.table.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
-  if (on != (handle->nbundles > 0)) drop_graphs(handle);   // captured with or without the bundle launch; the layout itself lives in device memory
+  // captured with or without the bundle launch, or with the other kind's (turning this kind on turns the rigid kind off); the layout
+  // itself lives in device memory
+  if (on != (handle->nbundles > 0) || (on && handle->nrigid > 0)) drop_graphs(handle);
   handle->nbundles = nbundles;
+  if (on) handle->nrigid = 0;
   return AMDAT_SUCCESS;
 }
 
@@ -1067,6 +1079,48 @@ int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose
   if (!handle || !out || handle->inflight.active || handle->last_nbundles == 0 || nframes > handle->last_n) return AMDAT_INVALID_ARGUMENT;
   const size_t n = (size_t)nframes * handle->last_nbundles;
   for (size_t i = 0; i < n; i++) out[i] = handle->h_bposes[i].pose;
+  return AMDAT_SUCCESS;
+}
+
+// What the first call that turns rigid bundles on allocates: the device layout at its largest size and the pinned record block.
+static int ensure_rigid_buffers(amdAprilTagsDetector_st* D, size_t table_entries) {
+  if (!D->d_rigid_head && !dev_alloc(D, D->d_rigid_head, sizeof(RigidHeadDev))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->d_rigid_members && !dev_alloc(D, D->d_rigid_members, RIGID_MAX_MEMBERS * sizeof(RigidMemberDev))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->d_rigid_table && !dev_alloc(D, D->d_rigid_table, table_entries * sizeof(uint16_t))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->h_xposes && !host_alloc(D, D->h_xposes, (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(RigidPoseRec))) return AMDAT_OUT_OF_MEMORY;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetBundlesEx(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundleEx_t* bundles) {
+  if (!handle || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  static_assert(AMDAT_MAX_RIGID_BUNDLE_MEMBERS == RG_SLOTS, "the header's bound is the kernel's: one lane holds one tag");
+  uint32_t ncodes[AT_MAX_FAMILIES] = {};
+  for (int i = 0; i < handle->P.nfam; i++) ncodes[i] = handle->P.fam[i].ncodes;
+  RigidLayout L;
+  { const int rc = rigid_layout_build((uint32_t)handle->P.nfam, ncodes, nbundles, bundles, &L); if (rc) return rc; }
+  const bool on = nbundles > 0;
+  DeviceGuard guard(handle->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  if (on) {
+    { const int rc = ensure_rigid_buffers(handle, L.table.size()); if (rc) return rc; }
+    // (no submission is in flight: nothing reads the layout; `L` is pageable, so the copies are waited for before it goes)
+    const hipStream_t s = handle->own_stream;
+    HIP_TRY(hipMemcpyAsync(handle->d_rigid_head, &L.head, sizeof(L.head), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(handle->d_rigid_members, L.members.data(), L.members.size() * sizeof(RigidMemberDev), hipMemcpyHostToDevice, s));
+    if (!L.table.empty()) HIP_TRY(hipMemcpyAsync(handle->d_rigid_table, L.table.data(), L.table.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  // captured with or without the launch, or with the planar kind's (turning this kind on turns the planar kind off)
+  if (on != (handle->nrigid > 0) || (on && handle->nbundles > 0)) drop_graphs(handle);
+  handle->nrigid = nbundles;
+  if (on) handle->nbundles = 0;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePoseEx_t* out, uint32_t nframes) {
+  if (!handle || !out || handle->inflight.active || handle->last_nrigid == 0 || nframes > handle->last_n) return AMDAT_INVALID_ARGUMENT;
+  const size_t n = (size_t)nframes * handle->last_nrigid;
+  for (size_t i = 0; i < n; i++) out[i] = handle->h_xposes[i].pose;
   return AMDAT_SUCCESS;
 }
 
@@ -1447,6 +1501,9 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   if (D->nbundles)   // S10: one wave per (frame, bundle) on the kept records, straight behind k_reconcile (kernels_bundle.h)
     hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
                        D->d_bundle_head, D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
+  if (D->nrigid)   // S12: two waves per (frame, bundle), one chain each, in the planar kind's place (kernels_rigid.h)
+    hipLaunchKernelGGL(k_bundle_rigid, dim3(n, AMDAT_MAX_BUNDLES), dim3(128), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+                       D->d_rigid_head, D->d_rigid_members, D->d_rigid_table, D->h_xposes, P);
   if (D->pose_iterations)   // S11: both minima of the records handed out, eight lanes per record, beside the bundles (kernels_pose.h)
     hipLaunchKernelGGL(k_pose_refine, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
                        D->d_pose_cfg, D->h_rposes, ostride, P);
@@ -1640,6 +1697,8 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
     // bundles on: k_bundle_pose, the last kernel, stamps its records the same way
     for (uint32_t r = 0; r < D->launched_n * D->nbundles; r++)
       if (static_cast<volatile BundlePoseRec*>(D->h_bposes)[r].seq != D->seq) return false;
+    for (uint32_t r = 0; r < D->launched_n * D->nrigid; r++)   // rigid bundles on: k_bundle_rigid's records
+      if (static_cast<volatile RigidPoseRec*>(D->h_xposes)[r].seq != D->seq) return false;
     // pose refinement on: k_pose_refine stamps every record it hands out (the counts are final: the frames' stamps were seen above)
     if (D->pose_iterations)
       for (uint32_t f = 0; f < D->launched_n; f++) {
@@ -1738,6 +1797,7 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
   D->last_n = n;
   D->last_nbundles = D->nbundles;
+  D->last_nrigid = D->nrigid;
   D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
   D->last_pose_refined = D->pose_iterations > 0;
@@ -1949,6 +2009,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   fill_frames(handle, n, images, nullptr, fmt);
   handle->last_n = n;
   handle->last_nbundles = 0;        // (never solves bundles)
+  handle->last_nrigid = 0;
   handle->last_pose_refined = false;   // (never refines poses)
   handle->last_rectified = false;   // (never rectifies)
   handle->last_resized = false;     // (never resizes)

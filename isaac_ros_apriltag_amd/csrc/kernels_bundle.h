@@ -11,9 +11,12 @@
 #define BP_STRIDE 45    // doubles per record's partial in LDS: odd, so that the lanes of a wave land on distinct banks
 
 // What record i of the frame's canonical order is to bundle b: 0 none of its members, 1 used, 2 skipped (a gate or the duplicate rule).
+// One statement for both kinds of bundle: Head, Member, Gates are bundle_layout.h's structs for k_bundle_pose and rigid_layout.h's
+// for k_bundle_rigid, which carry the fields read here under the same names.
+template <class Head, class Member, class Gates>
 __device__ __forceinline__ int bundle_classify(uint32_t i, uint32_t nout, const DetRec* __restrict__ dets, const uint16_t* __restrict__ order,
-                                               const BundleHeadDev* __restrict__ head, const BundleMemberDev* __restrict__ members,
-                                               const uint16_t* __restrict__ table, uint32_t b, const BundleDev& B, uint32_t* member) {
+                                               const Head* __restrict__ head, const Member* __restrict__ members,
+                                               const uint16_t* __restrict__ table, uint32_t b, const Gates& B, uint32_t* member) {
   const DetRec* d = &dets[order[i]];
   const uint32_t fam = (uint32_t)d->family, id = (uint32_t)d->id;
   if (fam >= BUNDLE_MAX_FAMILIES || id >= head->fam_ncodes[fam]) return 0;

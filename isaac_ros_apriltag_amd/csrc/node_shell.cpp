@@ -49,6 +49,8 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetRectificationEx) set_rectification_ex = nullptr;
   decltype(&amdAprilTagsSetBundles) set_bundles = nullptr;
   decltype(&amdAprilTagsGetBundlePoses) get_bundle_poses = nullptr;
+  decltype(&amdAprilTagsSetBundlesEx) set_bundles_ex = nullptr;
+  decltype(&amdAprilTagsGetBundlePosesEx) get_bundle_poses_ex = nullptr;
   decltype(&amdAprilTagsSetPoseRefinement) set_pose_refinement = nullptr;
   decltype(&amdAprilTagsGetRefinedPoses) get_refined_poses = nullptr;
 };
@@ -92,6 +94,8 @@ DetectorApi& api() {
   BIND(set_rectification_ex, "amdAprilTagsSetRectificationEx")
   BIND(set_bundles, "amdAprilTagsSetBundles")
   BIND(get_bundle_poses, "amdAprilTagsGetBundlePoses")
+  BIND(set_bundles_ex, "amdAprilTagsSetBundlesEx")
+  BIND(get_bundle_poses_ex, "amdAprilTagsGetBundlePosesEx")
   BIND(set_pose_refinement, "amdAprilTagsSetPoseRefinement")
   BIND(get_refined_poses, "amdAprilTagsGetRefinedPoses")
 #undef BIND
@@ -202,6 +206,40 @@ void apply_bundles(amdAprilTagsHandle detector, const NodeOptions& opt) {
   if (error != 0) throw std::runtime_error("'bundles' refused (error code " + std::to_string(error) + ")");
 }
 
+// NodeOptions::rigid_bundles on a freshly created handle (family_index 0): the member's quaternion, divided by its norm, as a rotation
+void apply_rigid_bundles(amdAprilTagsHandle detector, const NodeOptions& opt) {
+  if (opt.rigid_bundles.empty()) return;
+  if (!opt.bundles.empty()) throw std::runtime_error("'bundles' and 'rigid_bundles' are both set: one kind of bundle is on at a time");
+  std::vector<std::vector<amdAprilTagsBundleMemberEx_t>> members(opt.rigid_bundles.size());
+  std::vector<amdAprilTagsBundleEx_t> abi(opt.rigid_bundles.size());
+  for (size_t b = 0; b < opt.rigid_bundles.size(); b++) {
+    const RigidBundle& in = opt.rigid_bundles[b];
+    if (in.name.size() > 31) throw std::runtime_error("'rigid_bundles': the name '" + in.name + "' has more than 31 characters");
+    for (const RigidBundleMember& m : in.members) {
+      const double n = std::sqrt(m.qw * m.qw + m.qx * m.qx + m.qy * m.qy + m.qz * m.qz);
+      if (!(n > 0.0)) throw std::runtime_error("'rigid_bundles': tag " + std::to_string(m.id) + " of '" + in.name + "' has a zero quaternion");
+      const double w = m.qw / n, x = m.qx / n, y = m.qy / n, z = m.qz / n;
+      amdAprilTagsBundleMemberEx_t o = {};
+      o.family_index = 0u; o.id = m.id; o.size = m.size;
+      o.R[0] = 1 - 2 * (y * y + z * z); o.R[1] = 2 * (x * y - z * w);     o.R[2] = 2 * (x * z + y * w);
+      o.R[3] = 2 * (x * y + z * w);     o.R[4] = 1 - 2 * (x * x + z * z); o.R[5] = 2 * (y * z - x * w);
+      o.R[6] = 2 * (x * z - y * w);     o.R[7] = 2 * (y * z + x * w);     o.R[8] = 1 - 2 * (x * x + y * y);
+      o.t[0] = m.x; o.t[1] = m.y; o.t[2] = m.z;
+      members[b].push_back(o);
+    }
+    abi[b] = {};
+    abi[b].members = members[b].data();
+    abi[b].nmembers = static_cast<uint32_t>(members[b].size());
+    abi[b].max_hamming = in.max_hamming;
+    abi[b].min_decision_margin = static_cast<float>(in.min_decision_margin);
+    abi[b].min_tags = in.min_tags;
+    abi[b].iterations = in.iterations;
+    std::strncpy(abi[b].name, in.name.c_str(), sizeof(abi[b].name) - 1);
+  }
+  const int error = api().set_bundles_ex(detector, static_cast<uint32_t>(abi.size()), abi.data());
+  if (error != 0) throw std::runtime_error("'rigid_bundles' refused (error code " + std::to_string(error) + ")");
+}
+
 // NodeOptions::pose_refinement on a freshly created handle
 void apply_pose_refinement(amdAprilTagsHandle detector, const NodeOptions& opt) {
   if (opt.pose_refinement == 0) return;
@@ -244,6 +282,42 @@ bool collect_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, uint32
       p.status = r.status; p.ntags = r.ntags; p.nskipped = r.nskipped; p.sq_err_sum = r.sq_err_sum;
       for (int i = 0; i < 9; i++) p.R[i] = r.R[i];
       for (int i = 0; i < 3; i++) p.t[i] = r.t[i];
+      (*poses)[f].push_back(p);
+      if (r.status != AMDAT_BUNDLE_SOLVED) continue;
+      TransformStamped tf;
+      tf.header = *headers[f];
+      tf.child_frame_id = "bundle:" + p.name;
+      tf.transform.translation.x = r.t[0];
+      tf.transform.translation.y = r.t[1];
+      tf.transform.translation.z = r.t[2];
+      float o[9];   // column-major float, the form a tag's orientation has
+      for (int rr = 0; rr < 3; rr++)
+        for (int c = 0; c < 3; c++) o[c * 3 + rr] = static_cast<float>(r.R[rr * 3 + c]);
+      tf.transform.rotation = quaternion_from_colmajor(o);
+      tfs[f]->push_back(tf);
+    }
+  }
+  return true;
+}
+
+// The same for NodeOptions::rigid_bundles: the records of amdAprilTagsGetBundlePosesEx, and one transform per solved bundle from the
+// chosen pose.
+bool collect_rigid_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t nframes, const Header* const* headers,
+                           std::vector<std::vector<RigidBundlePose>>* poses, std::vector<TransformStamped>* const* tfs) {
+  const size_t nb = opt.rigid_bundles.size();
+  poses->assign(nframes, std::vector<RigidBundlePose>());
+  if (nb == 0) return true;
+  std::vector<amdAprilTagsBundlePoseEx_t> recs(static_cast<size_t>(nframes) * nb);
+  if (api().get_bundle_poses_ex(detector, recs.data(), nframes) != 0) return false;
+  for (uint32_t f = 0; f < nframes; f++) {
+    for (size_t b = 0; b < nb; b++) {
+      const amdAprilTagsBundlePoseEx_t& r = recs[f * nb + b];
+      RigidBundlePose p;
+      p.name = opt.rigid_bundles[b].name;
+      p.status = r.status; p.ntags = r.ntags; p.nskipped = r.nskipped; p.seed = r.seed; p.chosen = r.chosen;
+      p.err = r.err; p.sq_err_sum = r.sq_err_sum; p.err_alt = r.err_alt; p.sq_err_sum_alt = r.sq_err_sum_alt;
+      for (int i = 0; i < 9; i++) { p.R[i] = r.R[i]; p.R_alt[i] = r.R_alt[i]; }
+      for (int i = 0; i < 3; i++) { p.t[i] = r.t[i]; p.t_alt[i] = r.t_alt[i]; }
       (*poses)[f].push_back(p);
       if (r.status != AMDAT_BUNDLE_SOLVED) continue;
       TransformStamped tf;
@@ -448,6 +522,7 @@ struct AprilTagNode::Impl {
   // exactly {CUDA}: the reference runs cuAprilTags, which decodes tag36h11 only (src/apriltag_node.cpp:429-432)
   bool cuapriltags_mode = false;
   std::vector<BundlePose> last_bundles;   // NodeOptions::bundles: the records of the last published frame
+  std::vector<RigidBundlePose> last_rigid;   // NodeOptions::rigid_bundles: the same
 
   void Initialize(const Image& image, const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
@@ -482,6 +557,7 @@ struct AprilTagNode::Impl {
     }
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
+    apply_rigid_bundles(detector, opt);
     apply_pose_refinement(detector, opt);
     width = info.width;
     height = info.height;
@@ -565,6 +641,12 @@ struct AprilTagNode::Impl {
         return;
       }
       last_bundles = poses[0];
+      std::vector<std::vector<RigidBundlePose>> rigid;
+      if (!collect_rigid_bundles(detector, opt, 1, &hdr, &rigid, &out)) {
+        std::fprintf(stderr, "[apriltag_node] rigid bundle records not available: frame dropped\n");
+        return;
+      }
+      last_rigid = rigid[0];
     }
     if (on_detections) on_detections(msg);
     if (on_transforms) on_transforms(tfs);
@@ -593,6 +675,7 @@ void AprilTagNode::set_transforms_callback(TransformsCallback cb) { impl_->on_tr
 const NodeOptions& AprilTagNode::options() const { return impl_->opt; }
 bool AprilTagNode::initialized() const { return impl_->initialized; }
 const std::vector<BundlePose>& AprilTagNode::last_bundle_poses() const { return impl_->last_bundles; }
+const std::vector<RigidBundlePose>& AprilTagNode::last_rigid_bundle_poses() const { return impl_->last_rigid; }
 
 bool AprilTagNode::CameraImageCallback(const Image& image, const CameraInfo& camera_info) {
   if (image.header.stamp.sec != camera_info.header.stamp.sec || image.header.stamp.nanosec != camera_info.header.stamp.nanosec)
@@ -626,6 +709,7 @@ struct AprilTagMultiCameraNode::Impl {
   };
   std::vector<Slot> slots;
   std::vector<std::vector<BundlePose>> last_bundles;   // per stream (NodeOptions::bundles)
+  std::vector<std::vector<RigidBundlePose>> last_rigid;   // per stream (NodeOptions::rigid_bundles)
 
   void Initialize(const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
@@ -656,6 +740,7 @@ struct AprilTagMultiCameraNode::Impl {
     if (mixed && api().set_per_frame_sizes(detector, 1) != 0) throw std::runtime_error("per-frame image sizes refused");
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
+    apply_rigid_bundles(detector, opt);
     apply_pose_refinement(detector, opt);
     width = cfg.width;
     height = cfg.height;
@@ -736,6 +821,7 @@ AprilTagMultiCameraNode::AprilTagMultiCameraNode(const NodeOptions& options, uin
   impl_->S = num_streams;
   impl_->slots.resize(num_streams);
   impl_->last_bundles.resize(num_streams);
+  impl_->last_rigid.resize(num_streams);
   impl_->family_enum = validate_family(options, &impl_->cuapriltags_mode);
 }
 
@@ -753,6 +839,7 @@ void AprilTagMultiCameraNode::set_transforms_callback(TransformsCallback cb) { i
 void AprilTagMultiCameraNode::set_auto_flush(bool on) { impl_->auto_flush = on; }
 uint32_t AprilTagMultiCameraNode::num_streams() const { return impl_->S; }
 const std::vector<BundlePose>& AprilTagMultiCameraNode::last_bundle_poses(uint32_t stream) const { return impl_->last_bundles.at(stream); }
+const std::vector<RigidBundlePose>& AprilTagMultiCameraNode::last_rigid_bundle_poses(uint32_t stream) const { return impl_->last_rigid.at(stream); }
 const NodeOptions& AprilTagMultiCameraNode::options() const { return impl_->opt; }
 
 bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& image, const CameraInfo& camera_info) {
@@ -841,8 +928,14 @@ uint32_t AprilTagMultiCameraNode::Flush() {
     std::fprintf(stderr, "[apriltag_node] bundle records not available: round dropped\n");
     return 0;
   }
+  std::vector<std::vector<RigidBundlePose>> rigid;
+  if (!collect_rigid_bundles(I.detector, I.opt, n, headers.data(), &rigid, tf_ptrs.data())) {
+    std::fprintf(stderr, "[apriltag_node] rigid bundle records not available: round dropped\n");
+    return 0;
+  }
   for (uint32_t i = 0; i < n; i++) {
     I.last_bundles[who[i]] = poses[i];
+    I.last_rigid[who[i]] = rigid[i];
     if (I.on_detections) I.on_detections(who[i], msgs[i]);
     if (I.on_transforms) I.on_transforms(who[i], tfs[i]);
   }
@@ -1006,6 +1099,44 @@ static void set_bundle_options(NodeOptions* o, int nbundles, const NodeShellBund
     o->bundles.push_back(out);
   }
 }
+// NodeOptions::rigid_bundles through the flat view: members holds nine doubles per member -- id, x, y, z, qw, qx, qy, qz, size
+struct NodeShellRigidBundle {
+  char name[32];
+  const double* members;
+  uint32_t nmembers, max_hamming, min_tags, iterations;
+  double min_decision_margin;
+};
+struct NodeShellRigidBundlePose {
+  char name[32];
+  uint32_t status, ntags, nskipped, seed, chosen, pad;
+  double R[9], t[3], err, sq_err_sum, R_alt[9], t_alt[3], err_alt, sq_err_sum_alt;
+};
+static void set_rigid_bundle_options(NodeOptions* o, int nbundles, const NodeShellRigidBundle* bundles) {
+  for (int b = 0; b < nbundles; b++) {
+    amd::isaac_ros::apriltag::RigidBundle out;
+    out.name = std::string(bundles[b].name, strnlen(bundles[b].name, sizeof(bundles[b].name)));
+    for (uint32_t m = 0; m < bundles[b].nmembers; m++) {
+      const double* v = bundles[b].members + 9 * m;
+      out.members.push_back({static_cast<uint32_t>(v[0]), v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]});
+    }
+    out.max_hamming = bundles[b].max_hamming; out.min_tags = bundles[b].min_tags; out.min_decision_margin = bundles[b].min_decision_margin;
+    out.iterations = bundles[b].iterations;
+    o->rigid_bundles.push_back(out);
+  }
+}
+static int copy_rigid_bundle_poses(const std::vector<amd::isaac_ros::apriltag::RigidBundlePose>& poses, NodeShellRigidBundlePose* out, int max_out) {
+  const int n = static_cast<int>(poses.size());
+  for (int i = 0; i < n && i < max_out; i++) {
+    NodeShellRigidBundlePose& o = out[i];
+    std::memset(&o, 0, sizeof(o));
+    std::strncpy(o.name, poses[i].name.c_str(), sizeof(o.name) - 1);
+    o.status = poses[i].status; o.ntags = poses[i].ntags; o.nskipped = poses[i].nskipped; o.seed = poses[i].seed; o.chosen = poses[i].chosen;
+    o.err = poses[i].err; o.sq_err_sum = poses[i].sq_err_sum; o.err_alt = poses[i].err_alt; o.sq_err_sum_alt = poses[i].sq_err_sum_alt;
+    for (int k = 0; k < 9; k++) { o.R[k] = poses[i].R[k]; o.R_alt[k] = poses[i].R_alt[k]; }
+    for (int k = 0; k < 3; k++) { o.t[k] = poses[i].t[k]; o.t_alt[k] = poses[i].t_alt[k]; }
+  }
+  return n;
+}
 static int copy_transforms(const std::vector<TransformStamped>& tfs, NodeShellTransform* out, int max_out) {
   const int n = static_cast<int>(tfs.size());
   for (int i = 0; i < n && i < max_out; i++) {
@@ -1050,6 +1181,27 @@ NodeShellHarness* node_shell_create_bundles(int max_tags, double size, int tile_
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+// AprilTagNode with NodeOptions::rigid_bundles (the other options at their defaults but those named)
+NodeShellHarness* node_shell_create_rigid_bundles(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                                  int decimate, int nbundles, const NodeShellRigidBundle* bundles, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    set_rigid_bundle_options(&o, nbundles, bundles);
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+int node_shell_last_rigid_bundle_poses(NodeShellHarness* h, NodeShellRigidBundlePose* out, int max_out) {
+  return copy_rigid_bundle_poses(h->node->last_rigid_bundle_poses(), out, max_out);
 }
 // AprilTagNode with NodeOptions::pose_refinement (the other options at their defaults but those named)
 NodeShellHarness* node_shell_create_refined(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
@@ -1209,6 +1361,29 @@ MultiShellHarness* node_shell_multi_create_bundles(int num_streams, int max_tags
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+MultiShellHarness* node_shell_multi_create_rigid_bundles(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                         const char* backends, int decimate, int auto_flush, int nbundles,
+                                                         const NodeShellRigidBundle* bundles, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    set_rigid_bundle_options(&o, nbundles, bundles);
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+int node_shell_multi_last_rigid_bundle_poses(MultiShellHarness* h, int stream, NodeShellRigidBundlePose* out, int max_out) {
+  return copy_rigid_bundle_poses(h->node->last_rigid_bundle_poses(static_cast<uint32_t>(stream)), out, max_out);
 }
 MultiShellHarness* node_shell_multi_create_refined(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
                                                    const char* backends, int decimate, int auto_flush, uint32_t pose_refinement,

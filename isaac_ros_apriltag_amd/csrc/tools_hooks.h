@@ -44,7 +44,11 @@
 //                               alternative of every refined record is the chosen pose again
 //                           18 = the pose refinement does not recompute t after the last iteration: every refined record carries the
 //                               last rotation with the translation of the one before
-//                           (4 .. 18 change values only: no address, index bound, launch size or loop count)
+//                           19 = the object points of a rigid bundle (rigid_layout.h) ignore the member's R: every member is taken
+//                               as axis-parallel to the bundle frame
+//                           20 = the means of the rigid bundle's iteration (rigid_pose.h) are divided by 4, section 7e's per-tag
+//                               count, instead of 4 * ntags: wrong wherever two or more tags are used
+//                           (4 .. 20 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -53,7 +57,8 @@
 //                           tests/test_resize_submission_gpu.py::test_the_resize_tests_fail_on_the_wrong_builds for 11 and 12,
 //                           tests/test_camera_models_gpu.py::test_the_camera_model_tests_fail_on_the_wrong_builds for 13 and 14,
 //                           tests/test_bundles_gpu.py::test_the_bundle_tests_fail_on_the_wrong_builds for 15 and 16,
-//                           tests/test_pose_refine_gpu.py::test_the_pose_refinement_tests_fail_on_the_wrong_builds for 17 and 18)
+//                           tests/test_pose_refine_gpu.py::test_the_pose_refinement_tests_fail_on_the_wrong_builds for 17 and 18,
+//                           tests/test_rigid_bundles_gpu.py::test_the_rigid_bundle_tests_fail_on_the_wrong_builds for 19 and 20)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -143,6 +148,18 @@
 #define POSE_T_FOLLOWS_STEP(it, iterations) ((it) + 1u < (iterations))
 #else
 #define POSE_T_FOLLOWS_STEP(it, iterations) ((void)(it), (void)(iterations), true)
+#endif
+
+// ---- rigid bundles: entry j of a member's rotation in its object points (rigid_layout.h), and the divisor of the means (rigid_pose.h) --
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 19
+#define RIGID_MEMBER_R(R, j) ((void)(R), ((j) % 4 == 0 ? 1.0 : 0.0))
+#else
+#define RIGID_MEMBER_R(R, j) ((R)[j])
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 20
+#define RIGID_NPTS(n) ((void)(n), 4.0)
+#else
+#define RIGID_NPTS(n) (n)
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------

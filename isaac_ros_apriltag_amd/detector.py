@@ -51,7 +51,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, pose_refinement=0, **caps):
+                 bundles=None, pose_refinement=0, bundles_ex=None, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -81,6 +81,7 @@ class AprilTagDetector:
         self.per_frame_sizes = False
         self.resizing = False
         self.nbundles = 0
+        self.nbundles_ex = 0
         self.pose_refinement = 0
         try:
             if quad_sigma:
@@ -93,6 +94,8 @@ class AprilTagDetector:
                 self.set_resize(resize)
             if bundles:
                 self.set_bundles(bundles)
+            if bundles_ex:
+                self.set_bundles_ex(bundles_ex)
             if pose_refinement:
                 self.set_pose_refinement(pose_refinement)
         except Exception:
@@ -139,6 +142,8 @@ class AprilTagDetector:
         arr = capi.bundles(bundles)
         capi._check("amdAprilTagsSetBundles", self._L.amdAprilTagsSetBundles(self._h, len(arr) if arr is not None else 0, arr))
         self.nbundles = len(arr) if arr is not None else 0
+        if self.nbundles:
+            self.nbundles_ex = 0   # (one kind is on at a time: the later call holds)
 
     def bundle_poses(self, n):
         """amdAprilTagsGetBundlePoses: the bundle records of the first n frames of the last completed submission, a list per frame of
@@ -148,6 +153,29 @@ class AprilTagDetector:
         return [[{"bundle": int(r.bundle), "status": int(r.status), "ntags": int(r.ntags), "nskipped": int(r.nskipped),
                   "R": np.array(list(r.R)).reshape(3, 3), "t": np.array(list(r.t)), "sq_err_sum": float(r.sq_err_sum)}
                  for r in out[f * self.nbundles:(f + 1) * self.nbundles]] for f in range(n)]
+
+    def set_bundles_ex(self, bundles):
+        """amdAprilTagsSetBundlesEx: bundles is a list of {"name", "iterations", "members": [(family_index, id, R, t, size)],
+        "max_hamming", "min_decision_margin", "min_tags"} (capi.bundles_ex) -- rigid 3-D bundles (cubes, rigs, boards with turned tags),
+        every member with its pose (R, t) in the bundle frame, solved per frame as one rigid body from all kept records; None or []
+        turns it off.  Turning it on turns set_bundles' planar kind off.  bundle_poses_ex(n) hands out the records."""
+        arr = capi.bundles_ex(bundles)
+        capi._check("amdAprilTagsSetBundlesEx", self._L.amdAprilTagsSetBundlesEx(self._h, len(arr) if arr is not None else 0, arr))
+        self.nbundles_ex = len(arr) if arr is not None else 0
+        if self.nbundles_ex:
+            self.nbundles = 0
+
+    def bundle_poses_ex(self, n):
+        """amdAprilTagsGetBundlePosesEx: the rigid bundle records of the first n frames of the last completed submission, a list per
+        frame of {"bundle", "status", "ntags", "nskipped", "seed", "chosen", "R" (3x3), "t", "err", "sq_err_sum", "R_alt", "t_alt",
+        "err_alt", "sq_err_sum_alt"} in the order of set_bundles_ex."""
+        out = (capi.BundlePoseEx * max(n * self.nbundles_ex, 1))()
+        capi._check("amdAprilTagsGetBundlePosesEx", self._L.amdAprilTagsGetBundlePosesEx(self._h, out, n))
+        return [[{"bundle": int(r.bundle), "status": int(r.status), "ntags": int(r.ntags), "nskipped": int(r.nskipped), "seed": int(r.seed),
+                  "chosen": int(r.chosen), "R": np.array(list(r.R)).reshape(3, 3), "t": np.array(list(r.t)), "err": float(r.err),
+                  "sq_err_sum": float(r.sq_err_sum), "R_alt": np.array(list(r.R_alt)).reshape(3, 3), "t_alt": np.array(list(r.t_alt)),
+                  "err_alt": float(r.err_alt), "sq_err_sum_alt": float(r.sq_err_sum_alt)}
+                 for r in out[f * self.nbundles_ex:(f + 1) * self.nbundles_ex]] for f in range(n)]
 
     def set_pose_refinement(self, iterations):
         """amdAprilTagsSetPoseRefinement: every following submission refines the records it hands out by orthogonal iteration from two

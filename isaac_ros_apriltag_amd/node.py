@@ -21,6 +21,19 @@ class ShellBundle(C.Structure):
                 ("min_tags", C.c_uint32), ("pad", C.c_uint32), ("min_decision_margin", C.c_double)]
 
 
+class ShellRigidBundle(C.Structure):
+    """NodeOptions::rigid_bundles through the flat view: members holds nine doubles per member -- id, x, y, z, qw, qx, qy, qz, size."""
+    _fields_ = [("name", C.c_char * 32), ("members", C.POINTER(C.c_double)), ("nmembers", C.c_uint32), ("max_hamming", C.c_uint32),
+                ("min_tags", C.c_uint32), ("iterations", C.c_uint32), ("min_decision_margin", C.c_double)]
+
+
+class ShellRigidBundlePose(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("status", C.c_uint32), ("ntags", C.c_uint32), ("nskipped", C.c_uint32), ("seed", C.c_uint32),
+                ("chosen", C.c_uint32), ("pad", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double),
+                ("sq_err_sum", C.c_double), ("R_alt", C.c_double * 9), ("t_alt", C.c_double * 3), ("err_alt", C.c_double),
+                ("sq_err_sum_alt", C.c_double)]
+
+
 class ShellTransform(C.Structure):
     _fields_ = [("child_frame_id", C.c_char * 48), ("frame_id", C.c_char * 48), ("sec", C.c_int32), ("nanosec", C.c_uint32),
                 ("translation", C.c_double * 3), ("rotation_xyzw", C.c_double * 4)]
@@ -124,6 +137,16 @@ def lib():
         L.node_shell_multi_last_transforms.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellTransform), C.c_int]
         L.node_shell_multi_last_bundle_poses.restype = C.c_int
         L.node_shell_multi_last_bundle_poses.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellBundlePose), C.c_int]
+        L.node_shell_create_rigid_bundles.restype = C.c_void_p
+        L.node_shell_create_rigid_bundles.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                      C.POINTER(ShellRigidBundle), C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_rigid_bundles.restype = C.c_void_p
+        L.node_shell_multi_create_rigid_bundles.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                            C.c_int, C.POINTER(ShellRigidBundle), C.c_char_p, C.c_size_t]
+        L.node_shell_last_rigid_bundle_poses.restype = C.c_int
+        L.node_shell_last_rigid_bundle_poses.argtypes = [C.c_void_p, C.POINTER(ShellRigidBundlePose), C.c_int]
+        L.node_shell_multi_last_rigid_bundle_poses.restype = C.c_int
+        L.node_shell_multi_last_rigid_bundle_poses.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellRigidBundlePose), C.c_int]
         _lib = L
     return _lib
 
@@ -143,6 +166,30 @@ def _shell_bundles(bundles):
         b.min_decision_margin = float(spec.get("min_decision_margin", 0.0))
     arr._keep = keep
     return arr
+
+
+def _shell_rigid_bundles(bundles):
+    """[{"name", "iterations", "members": [(id, (x, y, z), (qw, qx, qy, qz), size)], "max_hamming", "min_decision_margin", "min_tags"}] ->
+    a ShellRigidBundle array (kept alive with its member arrays)."""
+    arr = (ShellRigidBundle * len(bundles))()
+    keep = []
+    for b, spec in zip(arr, bundles):
+        flat = [float(v) for (tid, xyz, q, size) in spec["members"] for v in (tid,) + tuple(xyz) + tuple(q) + (size,)]
+        mem = (C.c_double * max(len(flat), 1))(*flat)
+        keep.append(mem)
+        b.name = spec.get("name", "").encode()
+        b.members, b.nmembers = C.cast(mem, C.POINTER(C.c_double)), len(spec["members"])
+        b.max_hamming, b.min_tags = int(spec.get("max_hamming", 2)), int(spec.get("min_tags", 1))
+        b.iterations = int(spec.get("iterations", 50))
+        b.min_decision_margin = float(spec.get("min_decision_margin", 0.0))
+    arr._keep = keep
+    return arr
+
+
+def _unpack_rigid_bundle_poses(out, n):
+    return [{"name": p.name.decode(), "status": int(p.status), "ntags": int(p.ntags), "nskipped": int(p.nskipped), "seed": int(p.seed),
+             "chosen": int(p.chosen), "R": list(p.R), "t": list(p.t), "err": float(p.err), "sq_err_sum": float(p.sq_err_sum),
+             "R_alt": list(p.R_alt), "t_alt": list(p.t_alt), "err_alt": float(p.err_alt), "sq_err_sum_alt": float(p.sq_err_sum_alt)} for p in out[:n]]
 
 
 def _unpack_transforms(out, n):
@@ -220,7 +267,8 @@ class AprilTagMultiCameraNode:
     """S camera streams on one GPU, one detector submission per round (include/apriltag_node_shell.hpp)."""
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None, pose_refinement=0):
+                 auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None, pose_refinement=0,
+                 rigid_bundles=None):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
         undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
@@ -229,11 +277,23 @@ class AprilTagMultiCameraNode:
         rectification, and the pose is computed with the scaled camera.  bundles (NodeOptions::bundles, alone among the extensions):
         [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'.
         pose_refinement (NodeOptions::pose_refinement, alone among the extensions): iterations of the orthogonal-iteration pose -- the
-        detections' poses and the tags' transforms are the chosen refined pose."""
+        detections' poses and the tags' transforms are the chosen refined pose.  rigid_bundles (NodeOptions::rigid_bundles, alone among
+        the extensions): [{"name", "iterations", "members": [(id, (x, y, z), (qw, qx, qy, qz), size)], ...}] -- one "bundle:<name>"
+        transform per solved rigid bundle, from the chosen pose."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags, self.num_streams = max_tags, num_streams
+        if rigid_bundles:
+            if bundles or pose_refinement or quad_sigma or max_width or max_height or rectify or resize:
+                raise ValueError("rigid_bundles is served alone by this view: not with bundles, pose_refinement, quad_sigma, max_width / "
+                                 "max_height, rectify or resize")
+            arr = _shell_rigid_bundles(rigid_bundles)
+            self._h = self._L.node_shell_multi_create_rigid_bundles(num_streams, max_tags, size, tile_size, tag_family.encode(),
+                                                                    backends.encode(), decimate, 1 if auto_flush else 0, len(arr), arr, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if pose_refinement:
             if bundles or quad_sigma or max_width or max_height or rectify or resize:
                 raise ValueError("pose_refinement is served alone by this view: not with bundles, quad_sigma, max_width / max_height, rectify or resize")
@@ -289,6 +349,10 @@ class AprilTagMultiCameraNode:
         out = (ShellBundlePose * max_out)()
         return _unpack_bundle_poses(out, min(self._L.node_shell_multi_last_bundle_poses(self._h, stream, out, max_out), max_out))
 
+    def rigid_bundle_poses(self, stream, max_out=8):
+        out = (ShellRigidBundlePose * max_out)()
+        return _unpack_rigid_bundle_poses(out, min(self._L.node_shell_multi_last_rigid_bundle_poses(self._h, stream, out, max_out), max_out))
+
     def flush(self):
         return self._L.node_shell_multi_flush(self._h)
 
@@ -308,7 +372,8 @@ class AprilTagNode:
     """Parameters and defaults of the reference node (apriltag_node.cpp:564-568)."""
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
-                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None, pose_refinement=0):
+                 strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None, pose_refinement=0,
+                 rigid_bundles=None):
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
         (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
@@ -317,11 +382,23 @@ class AprilTagNode:
         the pose is computed with the camera scaled by w / width and h / height.  bundles (NodeOptions::bundles, alone among the
         extensions): [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'.
         pose_refinement (NodeOptions::pose_refinement, alone among the extensions): iterations of the orthogonal-iteration pose -- the
-        detections' poses and the tags' transforms are the chosen refined pose."""
+        detections' poses and the tags' transforms are the chosen refined pose.  rigid_bundles (NodeOptions::rigid_bundles, alone among
+        the extensions): [{"name", "iterations", "members": [(id, (x, y, z), (qw, qx, qy, qz), size)], ...}] -- one "bundle:<name>"
+        transform per solved rigid bundle, from the chosen pose."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags = max_tags
+        if rigid_bundles:
+            if bundles or pose_refinement or quad_sigma or rectify or resize or strict_cuapriltags_encodings:
+                raise ValueError("rigid_bundles is served alone by this view: not with bundles, pose_refinement, quad_sigma, rectify, resize "
+                                 "or strict_cuapriltags_encodings")
+            arr = _shell_rigid_bundles(rigid_bundles)
+            self._h = self._L.node_shell_create_rigid_bundles(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                              len(arr), arr, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if pose_refinement:
             if bundles or quad_sigma or rectify or resize or strict_cuapriltags_encodings:
                 raise ValueError("pose_refinement is served alone by this view: not with bundles, quad_sigma, rectify, resize or "
@@ -364,6 +441,10 @@ class AprilTagNode:
     def bundle_poses(self, max_out=8):
         out = (ShellBundlePose * max_out)()
         return _unpack_bundle_poses(out, min(self._L.node_shell_last_bundle_poses(self._h, out, max_out), max_out))
+
+    def rigid_bundle_poses(self, max_out=8):
+        out = (ShellRigidBundlePose * max_out)()
+        return _unpack_rigid_bundle_poses(out, min(self._L.node_shell_last_rigid_bundle_poses(self._h, out, max_out), max_out))
 
     def on_frame(self, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0),
                  info_stamp=None, D=None, distortion_model=None, P12=None, R=None):

@@ -76,6 +76,26 @@ public:
         }
       }
     }
+    // rigid 3-D tag bundles (cubes, rigs, boards with turned tags, solved per frame as one rigid body): rigid_bundle_names lists them,
+    // rigid_bundle_members holds ten numbers per member -- index into rigid_bundle_names, tag id, x, y, z of the tag centre in the
+    // bundle frame in metres, its orientation qw, qx, qy, qz, and its size.  One "bundle:<name>" transform is broadcast per solved
+    // bundle.  In place of bundle_names / bundle_members: one kind at a time.  Empty: off
+    {
+      const std::vector<std::string> names = declare_parameter<std::vector<std::string>>("rigid_bundle_names", std::vector<std::string>());
+      const std::vector<double> members = declare_parameter<std::vector<double>>("rigid_bundle_members", std::vector<double>());
+      for (const auto & n : names) {
+        shell::RigidBundle b;
+        b.name = n;
+        opt.rigid_bundles.push_back(b);
+      }
+      for (size_t i = 0; i + 9 < members.size(); i += 10) {
+        const size_t which = static_cast<size_t>(members[i]);
+        if (which < opt.rigid_bundles.size()) {
+          opt.rigid_bundles[which].members.push_back({static_cast<uint32_t>(members[i + 1]), members[i + 2], members[i + 3], members[i + 4],
+                                                      members[i + 5], members[i + 6], members[i + 7], members[i + 8], members[i + 9]});
+        }
+      }
+    }
     // the orthogonal-iteration tag pose with both minima (AprilRobotics' estimate_tag_pose) inside the detector's submission: this many
     // iterations per chain (50 upstream); the published poses and transforms are then the chosen refined pose.  0: off
     opt.pose_refinement = static_cast<uint32_t>(declare_parameter<int>("pose_refinement_iterations", 0));
