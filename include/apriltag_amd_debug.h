@@ -74,14 +74,24 @@ typedef enum {
   AMDAT_DBG_RECTIFIED = 9, /* u8  W0*H0 dense (the frame's INPUT size): its rectified plane of the last submission
                             * (amdAprilTagsSetRectification); AMDAT_INVALID_ARGUMENT when rectification is off -- and when
                             * amdAprilTagsSetResize is on as well: the resize samples the rectification in place, that plane is never formed */
-  AMDAT_DBG_RESIZED = 10   /* u8  dw*dh dense (the frame's TARGET size): its slot of the last submission (amdAprilTagsSetResize);
+  AMDAT_DBG_RESIZED = 10,  /* u8  dw*dh dense (the frame's TARGET size): its slot of the last submission (amdAprilTagsSetResize);
                             * AMDAT_INVALID_ARGUMENT when the last submission did not resize */
+  AMDAT_DBG_DETS = 11      /* amdAprilTagsDetectionEx_t x min(ndets, max_detections): the frame's decoded records as k_decode_wave wrote
+                            * them, BEFORE reconcile -- family, id, hamming, decision_margin, H, c, p; R and t are zero; the order is
+                            * arbitrary (atomic slots).  AMDAT_DBG_COUNTS' ndets counts every decoded quad, beyond the capacity too */
 } amdAprilTagsDebugBuffer;
 /* Copies an intermediate buffer of frame `frame` of the last submission to host memory.  w, h: the FRAME's own working size (with
  * amdAprilTagsSetPerFrameSizes on, the size that frame was submitted with; the planes are dense w x h whatever the handle's size).
  * Returns the number of bytes the buffer holds through *bytes (copy truncated to capacity). */
 int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsDebugBuffer what,
                           void* host_dst, size_t capacity, size_t* bytes);
+/* k_reconcile alone on records the caller chooses (the layout AMDAT_DBG_DETS hands out; R and t are ignored): n <= max_detections
+ * records go into batch slot 0's list, the kernel runs on the handle's own stream with the handle's intrinsics, skew and tag size,
+ * and the call waits.  The kept records come back in their final order, R and t filled: min(*nout, capacity) of them, the kept count
+ * through *nout.  n above max_detections: AMDAT_INVALID_ARGUMENT.  The last submission's buffers cannot be inspected afterwards
+ * (amdAprilTagsDebugCopy and the getters refuse until the next submission); the handle itself stays usable. */
+int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
+                               amdAprilTagsDetectionEx_t* records_out, uint32_t capacity, uint32_t* nout);
 /* Device-arithmetic self check: op 0 = sqrt(f64), 1 = a/b (f64), 2 = sqrtf(f32 bits in low word),
  * 3 = a/b (f32), 4 = a/b (f64) through the shared-reciprocal sequence the line fit uses, 5 = square root of the
  * integer a < 2^18 through the line-fit weights' f32-seeded sequence, 6 = atan_s(a), the arctangent of the equidistant camera model

@@ -17,6 +17,13 @@ SLOT_TAG36H10, SLOT_CUSTOM0 = 3, 4   # registrable slots: 3 (tag36h10: no built-
 (DBG_GRAY, DBG_THRESH, DBG_LABEL, DBG_CSIZE, DBG_CLUSTERS, DBG_POINTS, DBG_QUADS, DBG_COUNTS) = range(8)
 DBG_RECTIFIED = 9   # u8 W0 x H0: the frame's rectified plane (amdAprilTagsSetRectification)
 DBG_RESIZED = 10    # u8 dw x dh: the frame's resized plane (amdAprilTagsSetResize)
+DBG_DETS = 11       # DET_DTYPE x min(ndets, max_detections): the frame's decoded records before reconcile, in no order
+# the records of the stage buffers as numpy sees them (include/apriltag_amd_debug.h; DET_DTYPE is amdAprilTagsDetectionEx_t)
+CLUSTER_DTYPE = np.dtype([("key", "<u8"), ("start", "<u4"), ("count", "<u4")])
+QUAD_DTYPE = np.dtype([("p", "<f4", (4, 2)), ("reversed_border", "<i4"), ("pad", "<u4"), ("key", "<u8")])
+DET_DTYPE = np.dtype([("family", "<i4"), ("id", "<i4"), ("hamming", "<i4"), ("decision_margin", "<f4"), ("H", "<f8", (9,)),
+                      ("c", "<f8", (2,)), ("p", "<f8", (4, 2)), ("R", "<f8", (9,)), ("t", "<f8", (3,))])
+FLAG_DETS_OVERFLOW = 0x10   # AMDAT_FLAG_DETS_OVERFLOW
 
 STATUS = {0: "AMDAT_SUCCESS", 1: "AMDAT_INVALID_ARGUMENT", 2: "AMDAT_UNSUPPORTED", 3: "AMDAT_HIP_ERROR",
           4: "AMDAT_SIZE_MISMATCH", 5: "AMDAT_OUT_OF_MEMORY", 6: "AMDAT_BATCH_TOO_LARGE"}
@@ -115,6 +122,9 @@ class DetectionEx(C.Structure):
                 ("t", C.c_double * 3)]
 
 
+assert DET_DTYPE.itemsize == C.sizeof(DetectionEx)
+
+
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("tile_size", C.c_uint32), ("decimate", C.c_uint32),
                 ("num_families", C.c_uint32), ("families", C.c_int * 4), ("intrinsics", Intrinsics),
@@ -143,7 +153,7 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetRectification", "amdAprilTagsSetResize", "amdAprilTagsDistortionFromName",
            "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex", "amdAprilTagsSetBundles", "amdAprilTagsGetBundlePoses",
            "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses",
-           "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx"]
+           "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx", "amdAprilTagsDebugReconcile"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -233,6 +243,7 @@ def lib():
     L.amdAprilTagsGetBundlePosesEx.argtypes = [H, C.POINTER(BundlePoseEx), C.c_uint32]
     L.amdAprilTagsSetPoseRefinement.argtypes = [H, C.c_uint32]
     L.amdAprilTagsGetRefinedPoses.argtypes = [H, C.c_uint32, C.POINTER(RefinedPose), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.amdAprilTagsDebugReconcile.argtypes = [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)

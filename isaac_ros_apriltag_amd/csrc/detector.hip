@@ -2191,6 +2191,10 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       src = handle->d_quads + (size_t)frame * P.qcap;
       sz = (size_t)(fc.nquads < P.qcap ? fc.nquads : P.qcap) * sizeof(QuadRec);
       break;
+    case AMDAT_DBG_DETS:   // as k_decode_wave wrote them: atomic slots, R and t zero (ndets counts every attempt, the list holds dcap)
+      src = handle->d_dets + (size_t)frame * P.dcap;
+      sz = (size_t)(fc.ndets < P.dcap ? fc.ndets : P.dcap) * sizeof(DetRec);
+      break;
     case AMDAT_DBG_FQPROF:
       src = handle->d_fqprof; sz = (64 + 8) * 8;
       break;
@@ -2204,6 +2208,50 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
   }
   *bytes = sz;
   if (host_dst && sz) HIP_TRY(hipMemcpy(host_dst, src, sz < capacity ? sz : capacity, hipMemcpyDeviceToHost));
+  return AMDAT_SUCCESS;
+}
+
+// k_reconcile alone, on records the caller chooses: they go into batch slot 0's record list with that slot's ndets, the slot's
+// descriptor carries the handle's intrinsics and a fresh sequence number, and the kept records come back through the pinned buffer
+// as after a submission.  Nothing of the last submission can be inspected afterwards (its slot 0 is overwritten): last_n is 0 until
+// the next one, whose prologue rewrites descriptors and counters anyway.
+int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
+                               amdAprilTagsDetectionEx_t* records_out, uint32_t capacity, uint32_t* nout) {
+  if (!handle || !nout || handle->inflight.active || (n && !records_in) || (capacity && !records_out)) return AMDAT_INVALID_ARGUMENT;
+  if (n > handle->P.dcap) return AMDAT_INVALID_ARGUMENT;
+  if (handle->unusable) return AMDAT_OUT_OF_MEMORY;
+  amdAprilTagsDetector_st* D = handle;
+  DeviceGuard guard(D->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  const hipStream_t s = D->own_stream;
+  HIP_TRY(hipDeviceSynchronize());
+  D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_rectified = false; D->last_resized = false;
+  FrameDesc fd;
+  memset(&fd, 0, sizeof(fd));
+  fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;
+  fd.cx = (double)D->cfg.intrinsics.cx; fd.cy = (double)D->cfg.intrinsics.cy;
+  fd.skew = (double)(D->frame_skew.empty() ? D->cfg.skew : D->frame_skew[0]);
+  fd.seq = ++D->seq;
+  FrameCounters fc;
+  memset(&fc, 0, sizeof(fc));
+  fc.ndets = n;
+  HIP_TRY(hipMemcpyAsync(D->d_frames, &fd, sizeof(fd), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(D->d_counters, &fc, sizeof(fc), hipMemcpyHostToDevice, s));
+  if (n) HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
+  DetParams P = D->P;
+  P.frame0 = 0;
+  hipLaunchKernelGGL(k_reconcile, dim3(1), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, P.dcap,
+                     D->h_counters, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  if (static_cast<volatile FrameCounters*>(D->h_counters)[0].seq != fd.seq) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (static_cast<volatile FrameCounters*>(D->h_counters)[0].seq != fd.seq) return AMDAT_HIP_ERROR;
+  }
+  const uint32_t nk = D->h_counters[0].nout;
+  *nout = nk;
+  const uint32_t k = nk < capacity ? nk : capacity;
+  if (k) memcpy(records_out, D->h_out, (size_t)k * sizeof(DetRec));
   return AMDAT_SUCCESS;
 }
 

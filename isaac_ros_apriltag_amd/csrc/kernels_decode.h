@@ -91,8 +91,8 @@ __device__ bool quads_overlap_dev(const double (*a)[2], const double (*b)[2]) {
   for (int i = 0; i < 4; i++)
     for (int j = 0; j < 4; j++)
       if (segments_intersect_dev(a[i], a[(i + 1) & 3], b[j], b[(j + 1) & 3])) return true;
-  if (point_in_quad_dev(a, b[0])) return true;
-  if (point_in_quad_dev(b, a[0])) return true;
+  if (QO_CONTAINMENT(point_in_quad_dev(a, b[0]))) return true;   // (tools_hooks.h: the test itself in the product build)
+  if (QO_CONTAINMENT(point_in_quad_dev(b, a[0]))) return true;
   return false;
 }
 // strict "a precedes b" in the canonical preference order
@@ -100,7 +100,7 @@ __device__ bool det_before_dev(const DetRec* a, const DetRec* b) {
   if (a->family != b->family) return a->family < b->family;
   if (a->id != b->id) return a->id < b->id;
   if (a->hamming != b->hamming) return a->hamming < b->hamming;
-  if (a->decision_margin != b->decision_margin) return a->decision_margin > b->decision_margin;
+  if (a->decision_margin != b->decision_margin) return DET_MARGIN_BEFORE(a->decision_margin, b->decision_margin);   // (tools_hooks.h: a > b)
   for (int i = 0; i < 4; i++)
     for (int k = 0; k < 2; k++)
       if (a->p[i][k] != b->p[i][k]) return a->p[i][k] < b->p[i][k];

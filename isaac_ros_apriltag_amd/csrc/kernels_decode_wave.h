@@ -94,8 +94,8 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
           const double x0 = alpha * pax + (1 - alpha) * pbx;
           const double y0 = alpha * pay + (1 - alpha) * pby;
           double Mn = 0, Mcount = 0;  // exact sums: integer weights times multiples of 0.25
-          // the image gathers of DW_KB steps are issued together (their addresses do not depend on each other); a step
-          // outside the image reads pixel 0 and is not counted
+          // the image gathers of DW_KB steps are issued together (their addresses do not depend on each other); a read
+          // outside the image takes pixel 0 instead, and a step with such a read is not counted
           for (int k0 = 0; k0 < steps; k0 += DW_KB) {
             int g1[DW_KB], g2[DW_KB];
             bool in[DW_KB];
@@ -106,13 +106,15 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
               const int y1 = (int)(y0 + (n + 1.0) * ny);
               const int x2 = (int)(x0 + (n - 1.0) * nx);
               const int y2 = (int)(y0 + (n - 1.0) * ny);
-              in[u] = (k0 + u < steps) && !(x1 < 0 || x1 >= w || y1 < 0 || y1 >= h) && !(x2 < 0 || x2 >= w || y2 < 0 || y2 >= h);
-              g1[u] = im[in[u] ? (size_t)y1 * pitch + x1 : (size_t)0];
-              g2[u] = im[in[u] ? (size_t)y2 * pitch + x2 : (size_t)0];
+              const bool live = k0 + u < steps;
+              const bool in1 = live && !(x1 < 0 || x1 >= w || y1 < 0 || y1 >= h), in2 = live && !(x2 < 0 || x2 >= w || y2 < 0 || y2 >= h);
+              in[u] = in1 && in2;
+              g1[u] = im[in1 ? (size_t)y1 * pitch + x1 : (size_t)0];
+              g2[u] = im[in2 ? (size_t)y2 * pitch + x2 : (size_t)0];
             }
 #pragma unroll
             for (int u = 0; u < DW_KB; u++) {
-              if (!in[u] || g1[u] < g2[u]) continue;
+              if (!DW_STEP_COUNTED(in[u], k0 + u, steps) || g1[u] < g2[u]) continue;   // (tools_hooks.h: in[u] in the product build)
               const double n = -range + 0.25 * (k0 + u);
               const double weight = (double)((g2[u] - g1[u]) * (g2[u] - g1[u]));
               Mn += weight * n;
@@ -330,7 +332,7 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
           const int ob = __shfl_xor(best, off, 64), oi = __shfl_xor(bid, off, 64);
-          if (ob < best || (ob == best && oi < bid)) { best = ob; bid = oi; }
+          if (ob < best || (ob == best && DW_TIE_TAKES(oi, bid))) { best = ob; bid = oi; }   // (tools_hooks.h: oi < bid, the scan's first)
         }
         if (best <= P.max_hamming) { id = bid; hamming = best; rotation = r; found = true; }
         else {   // pattern rotated by 90 degrees: bit i takes the value of bit rot_src[i]

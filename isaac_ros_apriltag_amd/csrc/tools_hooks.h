@@ -48,7 +48,14 @@
 //                               as axis-parallel to the bundle frame
 //                           20 = the means of the rigid bundle's iteration (rigid_pose.h) are divided by 4, section 7e's per-tag
 //                               count, instead of 4 * ntags: wrong wherever two or more tags are used
-//                           (4 .. 20 change values only: no address, index bound, launch size or loop count)
+//                           21 = the edge refinement (k_decode_wave) counts a step of the normal search with a read outside the image, with
+//                               pixel 0's value in that read's place: wrong only where a tag's side lies within a few pixels of the frame edge
+//                           22 = the code scan's wave reduction (k_decode_wave) keeps the HIGHER index at equal distance: wrong only where
+//                               two codes of a family are equally near the word read (tag16h5 at max_hamming 3)
+//                           23 = quads_overlap_dev (k_reconcile) without its two containment tests: a duplicate strictly inside another
+//                               record of its id survives
+//                           24 = det_before_dev (k_reconcile) compares decision margins ascending
+//                           (4 .. 24 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -58,7 +65,8 @@
 //                           tests/test_camera_models_gpu.py::test_the_camera_model_tests_fail_on_the_wrong_builds for 13 and 14,
 //                           tests/test_bundles_gpu.py::test_the_bundle_tests_fail_on_the_wrong_builds for 15 and 16,
 //                           tests/test_pose_refine_gpu.py::test_the_pose_refinement_tests_fail_on_the_wrong_builds for 17 and 18,
-//                           tests/test_rigid_bundles_gpu.py::test_the_rigid_bundle_tests_fail_on_the_wrong_builds for 19 and 20)
+//                           tests/test_rigid_bundles_gpu.py::test_the_rigid_bundle_tests_fail_on_the_wrong_builds for 19 and 20,
+//                           tests/test_decode_stage_gpu.py::test_the_decode_stage_tests_fail_on_the_wrong_builds for 21 .. 24)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -160,6 +168,31 @@
 #define RIGID_NPTS(n) ((void)(n), 4.0)
 #else
 #define RIGID_NPTS(n) (n)
+#endif
+
+// ---- k_decode_wave: whether step k of `steps` of the normal search enters the sums (in: both reads lie inside the image), and whether
+// ---- index oi replaces index bid at equal distance in the code scan's reduction -----------------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 21
+#define DW_STEP_COUNTED(in, k, steps) ((void)(in), (k) < (steps))
+#else
+#define DW_STEP_COUNTED(in, k, steps) (in)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 22
+#define DW_TIE_TAKES(oi, bid) ((oi) > (bid))
+#else
+#define DW_TIE_TAKES(oi, bid) ((oi) < (bid))
+#endif
+
+// ---- k_reconcile: a containment test of quads_overlap_dev, and "margin a goes before margin b" of det_before_dev ------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 23
+#define QO_CONTAINMENT(inside) ((void)(inside), false)
+#else
+#define QO_CONTAINMENT(inside) (inside)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 24
+#define DET_MARGIN_BEFORE(a, b) ((a) < (b))
+#else
+#define DET_MARGIN_BEFORE(a, b) ((a) > (b))
 #endif
 
 // ---- k_points -----------------------------------------------------------------------------------------------------------

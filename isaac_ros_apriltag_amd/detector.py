@@ -379,7 +379,19 @@ class AprilTagDetector:
         if what in (capi.DBG_LABEL, capi.DBG_CSIZE, capi.DBG_POINTS, capi.DBG_COUNTS):
             return buf.view(np.uint32)
         if what == capi.DBG_CLUSTERS:
-            return buf.view(np.dtype([("key", "<u8"), ("start", "<u4"), ("count", "<u4")]))
+            return buf.view(capi.CLUSTER_DTYPE)
         if what == capi.DBG_QUADS:
-            return buf.view(np.dtype([("p", "<f4", (4, 2)), ("reversed_border", "<i4"), ("pad", "<u4"), ("key", "<u8")]))
+            return buf.view(capi.QUAD_DTYPE)
+        if what == capi.DBG_DETS:
+            return buf.view(capi.DET_DTYPE)
         return buf
+
+    def debug_reconcile(self, records):
+        """amdAprilTagsDebugReconcile: k_reconcile alone on `records` (capi.DET_DTYPE; at most max_detections of them); the kept records
+        in their final order, R and t filled.  The last submission's stage buffers cannot be read afterwards."""
+        rec = np.array(records, dtype=capi.DET_DTYPE, order="C", copy=True).reshape(-1)
+        out = np.zeros(max(len(rec), 1), dtype=capi.DET_DTYPE)
+        nout = C.c_uint32()
+        capi._check("amdAprilTagsDebugReconcile",
+                    self._L.amdAprilTagsDebugReconcile(self._h, len(rec), rec.ctypes.data, out.ctypes.data, len(out), C.byref(nout)))
+        return out[:min(nout.value, len(out))].copy()

@@ -11,6 +11,7 @@
 #include "apriltag_oracle.h"
 
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <pthread.h>
 #include <string.h>
@@ -1412,6 +1413,23 @@ void ato_pose_from_homography(const double H[9], double fx, double fy, double cx
 /* full pipeline -- the CPU stand-in for one cuAprilTagsDetect call                             */
 /* (src/apriltag_node.cpp:491-493)                                                              */
 /* ------------------------------------------------------------------------------------------- */
+/* S8 + S9 on a list of decoded records: the canonical order, the overlap rule among records of one (family, id) -- a record goes
+ * if an already KEPT one of its family and id overlaps it --, then the pose of every kept record.  In place; returns the kept count. */
+int ato_reconcile(const ato_params_t* prm, ato_detection_t* dets, int n) {
+  if (n < 0) return -1;
+  qsort(dets, (size_t)n, sizeof(ato_detection_t), det_cmp);
+  int nk = 0;
+  for (int i = 0; i < n; i++) {
+    int dead = 0;
+    for (int j = 0; j < nk && !dead; j++)
+      if (dets[j].family == dets[i].family && dets[j].id == dets[i].id && quads_overlap(dets[j].p, dets[i].p)) dead = 1;
+    if (!dead) dets[nk++] = dets[i];
+  }
+  for (int i = 0; i < nk; i++)
+    ato_pose_from_homography_ex(dets[i].H, prm->fx, prm->fy, prm->cx, prm->cy, prm->skew, prm->tag_size, prm->variant, dets[i].R, dets[i].t);
+  return nk;
+}
+
 static int quad_key_cmp(const void* a, const void* b) {
   const ato_quad_t* x = (const ato_quad_t*)a; const ato_quad_t* y = (const ato_quad_t*)b;
   return (x->key > y->key) - (x->key < y->key);
@@ -1533,18 +1551,15 @@ int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, cons
       }
     }
   }
-  /* reconcile + order */
-  qsort(dets, nd, sizeof(ato_detection_t), det_cmp);
-  size_t nk = 0;
-  for (size_t i = 0; i < nd; i++) {
-    int dead = 0;
-    for (size_t j = 0; j < nk && !dead; j++)
-      if (dets[j].family == dets[i].family && dets[j].id == dets[i].id && quads_overlap(dets[j].p, dets[i].p)) dead = 1;
-    if (!dead) dets[nk++] = dets[i];
+  /* the pre-reconcile list, for the dump: a copy in the canonical order */
+  ato_detection_t* dets_raw = NULL;
+  const size_t nd_raw = nd;
+  if (dump) {
+    dets_raw = (ato_detection_t*)malloc((nd ? nd : 1) * sizeof(ato_detection_t));
+    memcpy(dets_raw, dets, nd * sizeof(ato_detection_t));
+    qsort(dets_raw, nd, sizeof(ato_detection_t), det_cmp);
   }
-  nd = nk;
-  for (size_t i = 0; i < nd; i++)
-    ato_pose_from_homography_ex(dets[i].H, prm->fx, prm->fy, prm->cx, prm->cy, prm->skew, prm->tag_size, prm->variant, dets[i].R, dets[i].t);
+  nd = (size_t)ato_reconcile(prm, dets, (int)nd);
 
   int nout = (int)(nd < (size_t)max_det ? nd : (size_t)max_det);
   for (int i = 0; i < nout; i++) out[i] = dets[i];
@@ -1553,6 +1568,7 @@ int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, cons
     dump->w = w; dump->h = h; dump->gray = gray; dump->thr = thr; dump->label = label; dump->csize = csize;
     dump->nclusters = (uint32_t)nc; dump->clusters = clusters; dump->npoints = (uint32_t)npk; dump->points = ptsbuf;
     dump->nquads = (uint32_t)nq; dump->quads = quads; dump->ndet = (uint32_t)nd; dump->dets = dets;
+    dump->ndet_raw = (uint32_t)nd_raw; dump->dets_raw = dets_raw;
   } else {
     free(gray); free(thr); free(label); free(csize); free(clusters); free(ptsbuf); free(quads); free(dets);
   }
@@ -1561,7 +1577,7 @@ int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, cons
 
 void ato_dump_free(ato_dump_t* d) {
   free(d->gray); free(d->thr); free(d->label); free(d->csize); free(d->clusters); free(d->points); free(d->quads);
-  free(d->dets);
+  free(d->dets); free(d->dets_raw);
   memset(d, 0, sizeof(*d));
 }
 
@@ -1614,4 +1630,34 @@ void ato_rectify_mono8(const uint8_t* src, int spitch, uint8_t* dst, int dpitch,
       }
       dst[(size_t)y * dpitch + x] = out;
     }
+}
+
+/* ------------------------------------------------------------------------------------------- */
+/* the symbols of the library as it was before ato_dump_t held dets_raw (apriltag_oracle.h)      */
+/* ------------------------------------------------------------------------------------------- */
+#undef ato_detect
+#undef ato_dump_free
+#define ATO_DUMP_V1_BYTES offsetof(ato_dump_t, ndet_raw)   /* the struct those callers allocate ends after `dets` */
+int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, const uint8_t* image, int width, int height, int pitch,
+               ato_detection_t* out, int max_det, void* dump_v1);
+void ato_dump_free(void* dump_v1);
+
+int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam, const uint8_t* image, int width, int height, int pitch,
+               ato_detection_t* out, int max_det, void* dump_v1) {
+  ato_dump_t full;
+  memset(&full, 0, sizeof(full));
+  int n = ato_detect_v2(prm, fams, nfam, image, width, height, pitch, out, max_det, dump_v1 ? &full : NULL);
+  if (n >= 0 && dump_v1) {
+    free(full.dets_raw);
+    memcpy(dump_v1, &full, ATO_DUMP_V1_BYTES);
+  }
+  return n;
+}
+
+void ato_dump_free(void* dump_v1) {
+  ato_dump_t full;
+  memset(&full, 0, sizeof(full));
+  memcpy(&full, dump_v1, ATO_DUMP_V1_BYTES);
+  ato_dump_free_v2(&full);
+  memset(dump_v1, 0, ATO_DUMP_V1_BYTES);
 }

@@ -123,6 +123,8 @@ typedef struct {
   ato_quad_t* quads;            /* after fit (working-image coords scaled back to full-res), sorted by key */
   uint32_t ndet;
   ato_detection_t* dets;        /* final detections (after reconcile + sort) */
+  uint32_t ndet_raw;
+  ato_detection_t* dets_raw;    /* the decoded records BEFORE reconcile, in the canonical order (det_cmp); R and t are zero */
 } ato_dump_t;
 
 void ato_default_params(ato_params_t* p);
@@ -140,12 +142,22 @@ int ato_quad_sigma(uint8_t* im, int w, int h, double quad_sigma);
 void ato_threshold(const uint8_t* im, int w, int h, int tile, int min_diff, uint8_t* out);
 void ato_connected_components(const uint8_t* thr, int w, int h, uint32_t* label, uint32_t* csize);
 
+/* ato_dump_t grew by ndet_raw / dets_raw.  The two entry points that take one are therefore exported under a suffixed symbol, and
+ * the library keeps the unsuffixed symbols for a caller built against the shorter struct (a binding older than the library it
+ * loads): those fill and free everything up to `dets` and never touch a byte beyond it (apriltag_oracle.c, at its end). */
+#define ato_detect ato_detect_v2
+#define ato_dump_free ato_dump_free_v2
+
 /* Full pipeline. image is mono8 pitch-linear. Returns number of detections written (<= max_det),
  * or a negative error code. dump may be NULL. */
 int ato_detect(const ato_params_t* prm, const ato_family_t* fams, int nfam,
                const uint8_t* image, int width, int height, int pitch,
                ato_detection_t* out, int max_det, ato_dump_t* dump);
 void ato_dump_free(ato_dump_t* d);
+/* The tail of ato_detect on its own: sorts n decoded records into the canonical preference order, drops every record that an already
+ * kept one of the same family and id overlaps, and fills R and t of the kept ones (prm: fx, fy, cx, cy, skew, tag_size, variant).
+ * In place; returns the number kept (they lead dets[]), or a negative error code. */
+int ato_reconcile(const ato_params_t* prm, ato_detection_t* dets, int n);
 
 /* Front steps (resize / rectify of mono8 frames), same fixed-point definitions as the HIP kernels in
  * isaac_ros_apriltag_amd/csrc/kernels_frontend.h. */

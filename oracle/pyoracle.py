@@ -51,7 +51,8 @@ class Dump(C.Structure):
                 ("csize", C.POINTER(C.c_uint32)), ("nclusters", C.c_uint32),
                 ("clusters", C.POINTER(Cluster)), ("npoints", C.c_uint32),
                 ("points", C.POINTER(C.c_uint32)), ("nquads", C.c_uint32), ("quads", C.POINTER(Quad)),
-                ("ndet", C.c_uint32), ("dets", C.POINTER(Detection))]
+                ("ndet", C.c_uint32), ("dets", C.POINTER(Detection)),
+                ("ndet_raw", C.c_uint32), ("dets_raw", C.POINTER(Detection))]
 
 
 def build():
@@ -81,10 +82,13 @@ def lib():
         _lib.ato_custom_family.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.c_uint32, C.c_uint32,
                                            C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(Family)]
         _lib.ato_custom_family.restype = C.c_int
-        _lib.ato_detect.argtypes = [C.POINTER(Params), C.POINTER(Family), C.c_int, C.c_void_p, C.c_int,
-                                    C.c_int, C.c_int, C.POINTER(Detection), C.c_int, C.POINTER(Dump)]
-        _lib.ato_detect.restype = C.c_int
-        _lib.ato_dump_free.argtypes = [C.POINTER(Dump)]
+        # Dump holds dets_raw: the _v2 symbols (apriltag_oracle.h).  The unsuffixed ones serve a binding with the shorter struct
+        _lib.ato_detect_v2.argtypes = [C.POINTER(Params), C.POINTER(Family), C.c_int, C.c_void_p, C.c_int,
+                                       C.c_int, C.c_int, C.POINTER(Detection), C.c_int, C.POINTER(Dump)]
+        _lib.ato_detect_v2.restype = C.c_int
+        _lib.ato_dump_free_v2.argtypes = [C.POINTER(Dump)]
+        _lib.ato_reconcile.argtypes = [C.POINTER(Params), C.POINTER(Detection), C.c_int]
+        _lib.ato_reconcile.restype = C.c_int
         _lib.ato_threshold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.ato_connected_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ato_decimate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -211,6 +215,31 @@ def pose_from_homography(H, fx, fy, cx, cy, tag_size, skew=0.0, variant=0):
     return np.array(list(R)).reshape(3, 3), np.array(list(t))
 
 
+# one decoded record as the library lays it out (include/apriltag_amd.h: amdAprilTagsDetectionEx_t; ato_detection_t is the same)
+RECORD_DTYPE = np.dtype([("family", "<i4"), ("id", "<i4"), ("hamming", "<i4"), ("decision_margin", "<f4"), ("H", "<f8", (9,)),
+                         ("c", "<f8", (2,)), ("p", "<f8", (4, 2)), ("R", "<f8", (9,)), ("t", "<f8", (3,))])
+assert RECORD_DTYPE.itemsize == C.sizeof(Detection)
+
+
+def _records_of(ptr, n):
+    out = np.zeros(n, dtype=RECORD_DTYPE)
+    if n:
+        C.memmove(out.ctypes.data, ptr, n * RECORD_DTYPE.itemsize)
+    return out
+
+
+def reconcile(records, params=None):
+    """ato_reconcile on a numpy array of RECORD_DTYPE: the kept records in the canonical order, R and t filled (a new array)."""
+    prm = params if params is not None else default_params()
+    rec = np.array(records, dtype=RECORD_DTYPE, order="C", copy=True).reshape(-1)
+    buf = (Detection * max(len(rec), 1))()
+    C.memmove(buf, rec.ctypes.data, rec.nbytes)
+    nk = lib().ato_reconcile(C.byref(prm), buf, len(rec))
+    if nk < 0:
+        raise RuntimeError("ato_reconcile failed with %d" % nk)
+    return np.frombuffer(bytes(buf), dtype=RECORD_DTYPE)[:nk].copy()
+
+
 def detect(img, families=("tag36h11",), params=None, max_det=1024, want_dump=False):
     """Runs the full CPU restatement on one mono8 frame.
 
@@ -225,8 +254,8 @@ def detect(img, families=("tag36h11",), params=None, max_det=1024, want_dump=Fal
     families = [f.name.decode() if isinstance(f, Family) else f for f in families]
     out = (Detection * max_det)()
     dump = Dump() if want_dump else None
-    n = lib().ato_detect(C.byref(prm), fams, len(families), img.ctypes.data, w, h, img.strides[0], out, max_det,
-                         C.byref(dump) if want_dump else None)
+    n = lib().ato_detect_v2(C.byref(prm), fams, len(families), img.ctypes.data, w, h, img.strides[0], out, max_det,
+                            C.byref(dump) if want_dump else None)
     if n < 0:
         raise RuntimeError("ato_detect failed with %d" % n)
     dets = [_det_to_dict(out[i], list(families)) for i in range(n)]
@@ -247,6 +276,8 @@ def detect(img, families=("tag36h11",), params=None, max_det=1024, want_dump=Fal
                        "p": np.array([[dump.quads[i].p[k][0], dump.quads[i].p[k][1]] for k in range(4)],
                                      dtype=np.float32)} for i in range(dump.nquads)],
             "ndet_total": int(dump.ndet),
+            # the decoded records before reconcile, in the canonical order: RECORD_DTYPE (family: the index into `families`; R, t zero)
+            "dets_raw": _records_of(dump.dets_raw, dump.ndet_raw),
         }
-        lib().ato_dump_free(C.byref(dump))
+        lib().ato_dump_free_v2(C.byref(dump))
     return dets, d

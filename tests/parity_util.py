@@ -15,11 +15,36 @@ def oracle_params(K, decimate=1, tag_size=0.22, tile_size=4, **more):
                              tag_size=f32(tag_size), tile_size=tile_size, **more)
 
 
-def compare_stages(det, frame_idx, img, families, K, decimate=1, tag_size=0.22, verbose=False, tile_size=4, **more):
+def record_order(rec):
+    """Indices of the records `rec` (capi.DET_DTYPE / pyoracle.RECORD_DTYPE) in the canonical preference order: family, id, lower
+    hamming, higher margin, then the corner coordinates."""
+    return sorted(range(len(rec)), key=lambda i: (int(rec["family"][i]), int(rec["id"][i]), int(rec["hamming"][i]),
+                                                  -float(rec["decision_margin"][i])) + tuple(rec["p"][i].reshape(-1).tolist()))
+
+
+def compare_records(grec, orec):
+    """The decoded records BEFORE reconcile (AMDAT_DBG_DETS against the oracle's dump["dets_raw"]), both sides in the canonical order:
+    counts, then every field exactly; the library's R and t are still zero there."""
+    if len(grec) != len(orec):
+        return ["records: gpu %d vs oracle %d" % (len(grec), len(orec))]
+    g, o = grec[record_order(grec)], orec[record_order(orec)]
+    for i in range(len(g)):
+        for k in ("family", "id", "hamming", "decision_margin", "H", "c", "p"):
+            if not np.array_equal(g[k][i], o[k][i]):
+                return ["records: record %d (oracle id %d) field %s differs: %s vs %s" % (i, int(o["id"][i]), k, g[k][i].tolist(), o[k][i].tolist())]
+        if g["R"][i].any() or g["t"][i].any():
+            return ["records: record %d carries a pose before reconcile" % i]
+    return []
+
+
+def compare_stages(det, frame_idx, img, families, K, decimate=1, tag_size=0.22, verbose=False, tile_size=4, oracle=None, records=True,
+                   **more):
     """Returns a list of mismatch strings (empty = bit-exact parity on every stage).  more: decode parameters the handle was created
-    with beside the defaults (oracle_params)."""
+    with beside the defaults (oracle_params).  oracle: (detections, dump) of this very frame and these parameters, where the caller
+    has them already (a frame compared on both launch sets).  records=False: through the quads only -- for a stand-in frame that gives
+    the oracle the library's working image but not the pixels its decode stage reads (quad_sigma at decimate > 1)."""
     errs = []
-    odets, dump = po.detect(img, families=families, params=oracle_params(K, decimate, tag_size, tile_size, **more), want_dump=True)
+    odets, dump = oracle or po.detect(img, families=families, params=oracle_params(K, decimate, tag_size, tile_size, **more), want_dump=True)
     w, h = dump["w"], dump["h"]
     gray = det.debug(frame_idx, capi.DBG_GRAY).reshape(h, w)
     if not np.array_equal(gray, dump["gray"]):
@@ -62,6 +87,8 @@ def compare_stages(det, frame_idx, img, families, K, decimate=1, tag_size=0.22, 
             if int(q["key"][gi]) != o["key"] or not np.array_equal(q["p"][gi], o["p"]):
                 errs.append("quad key %x differs: %s vs %s" % (o["key"], q["p"][gi].tolist(), o["p"].tolist()))
                 break
+    if records:
+        errs += compare_records(det.debug(frame_idx, capi.DBG_DETS), dump["dets_raw"])
     if verbose:
         print("   stages: clusters %d points %d quads %d dets(oracle) %d" % (len(okeys), len(dump["points"]), len(oq), len(odets)))
     return errs, odets

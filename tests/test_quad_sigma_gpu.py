@@ -122,7 +122,7 @@ def test_decimated_through_the_quads(built, name, scene, decimate, path):
         det.set_quad_sigma(s)
         g = det.detect_batch_ex(t, max_dets=256)[0]
         J = qs.embed_decimated(img, qs.filter_image(qs.decimate(img, decimate), s), decimate)
-        errs, odets = pu.compare_stages(det, 0, J, ("tag36h11",), K, decimate)
+        errs, odets = pu.compare_stages(det, 0, J, ("tag36h11",), K, decimate, records=False)   # (decode reads img, not J: records below)
         assert not errs, (s, errs[:5])
         got = {int(d["id"]) for d in g}
         assert ids <= got and {int(d["id"]) for d in odets} <= got, (s, sorted(ids), sorted(got))
@@ -154,7 +154,7 @@ def test_colour_equals_mono8(built, decimate, tile, path):
         errs, odets = pu.compare_stages(det, 0, filt, ("tag36h11",), K, 1, tile_size=tile)
         errs += pu.compare_detections(gm, odets, exact=True)
     else:
-        errs, _ = pu.compare_stages(det, 0, qs.embed_decimated(gray, filt, decimate), ("tag36h11",), K, decimate, tile_size=tile)
+        errs, _ = pu.compare_stages(det, 0, qs.embed_decimated(gray, filt, decimate), ("tag36h11",), K, decimate, tile_size=tile, records=False)
     assert not errs, errs[:4]
     # every decimate: stages and records of the mono8 submission against the oracle with quad_sigma on the converted frame
     errs, odets = pu.compare_stages(det, 0, gray, ("tag36h11",), K, decimate, tile_size=tile, quad_sigma=0.8)
