@@ -498,6 +498,40 @@ int amdAprilTagsSetPoseRefinement(amdAprilTagsHandle handle, uint32_t iterations
  * capacity below the frame's count (then *n still carries the count), a submission in flight. */
 int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsRefinedPose_t* out, uint32_t capacity, uint32_t* n);
 
+/* Pose covariance: a first-order 6 x 6 covariance for every pose amdAprilTagsSetPoseRefinement and amdAprilTagsSetBundlesEx hand out,
+ * computed inside the same launches.  Off by default.
+ * The parameters are those of ROS' geometry_msgs/PoseWithCovariance in the camera optical frame, x = (dt_x, dt_y, dt_z, dtheta_x,
+ * dtheta_y, dtheta_z): the perturbed pose is t' = t + dt, R' = Exp(dtheta) R -- a rotation about axes parallel to the camera's,
+ * through the tag or bundle origin; metres and radians, row-major, exactly symmetric.  The model: every corner coordinate carries
+ * independent error of standard deviation corner_sigma_px, which is the CALLER's figure (nothing here estimates it);
+ * cov = corner_sigma_px^2 (J^T J)^-1 with J the Jacobian of the pixel projection of the corners at the reported pose (DESIGN.md
+ * section 7g has every operation; csrc/pose_covariance.h states it once for device and host, tests/pose_cov_ref.py in Python).
+ * It is evaluated at the record's reported R, t whatever the status, and at R_alt, t_alt where an alternative exists.
+ * valid: bit 0 cov, bit 1 cov_alt; a half whose bit is clear is 36 zeros (no alternative, a normal matrix that is not positive
+ * definite in the arithmetic, a result that is not finite, a bundle with too few tags).
+ * sq_err_sum, sq_err_sum_alt: for a tag, the sum over its four corners of the squared pixel reprojection error under R, t and under
+ * R_alt, t_alt (zero without an alternative) -- what a caller can judge its sigma against; zero in a bundle's record, whose pose
+ * record carries them. */
+typedef struct {
+  double cov[36], cov_alt[36];
+  double sq_err_sum, sq_err_sum_alt;
+  uint32_t valid, reserved;
+} amdAprilTagsPoseCovariance_t;
+/* corner_sigma_px = 0 turns the mode off (the default: nothing is launched or allocated, and no record changes by a bit), a finite
+ * value > 0 turns it on.  The mode acts on whichever of amdAprilTagsSetPoseRefinement and amdAprilTagsSetBundlesEx is on in a
+ * submission -- their launches run as their covariance instances; with neither on, nothing is launched.  Callable whenever no
+ * submission is in flight.  AMDAT_INVALID_ARGUMENT: null handle, a NaN, an infinity or a negative value, a submission in flight;
+ * AMDAT_OUT_OF_MEMORY: the record blocks could not be allocated.  A refused call leaves the previous setting in force.  Turning the
+ * mode on or off retires the handle's captured launch graphs, against the same budget of 24 as amdAprilTagsSetQuadSigma; changing
+ * only the value does not (its square lives in device memory). */
+int amdAprilTagsSetPoseCovariance(amdAprilTagsHandle handle, double corner_sigma_px);
+/* The covariance records beside amdAprilTagsGetRefinedPoses' records: same shape, same refusals, and refused where the last
+ * submission did not run both modes. */
+int amdAprilTagsGetRefinedPoseCovariances(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsPoseCovariance_t* out, uint32_t capacity, uint32_t* n);
+/* The covariance records beside amdAprilTagsGetBundlePosesEx' records: same shape, same refusals, and refused where the last
+ * submission did not run both modes. */
+int amdAprilTagsGetBundlePoseCovariancesEx(amdAprilTagsHandle handle, amdAprilTagsPoseCovariance_t* out, uint32_t nframes);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

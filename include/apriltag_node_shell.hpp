@@ -129,6 +129,8 @@ struct RigidBundlePose {
   std::array<double, 9> R{}, R_alt{};   // row-major
   std::array<double, 3> t{}, t_alt{};
   double err = 0, sq_err_sum = 0, err_alt = 0, sq_err_sum_alt = 0;
+  // NodeOptions::pose_covariance_sigma_px: the chosen pose's covariance as PoseWithCovariance's (zeros: off, or not valid)
+  std::array<double, 36> covariance{};
 };
 
 // Parameters declared in the constructor of the reference node (src/apriltag_node.cpp:564-568).
@@ -179,6 +181,12 @@ struct NodeOptions {
   // created: this many iterations per chain, 50 being AprilRobotics' estimate_tag_pose.  With it on, the pose of every detection and
   // its "family:id" transform are the chosen refined pose in place of the homography pose.  0 (the default): off.
   uint32_t pose_refinement = 0;
+  // Extension: pose covariance (amdAprilTagsSetPoseCovariance), set once when the handle is created: the standard deviation, in
+  // pixels, of the independent error the caller ascribes to every corner coordinate.  With it on and pose_refinement > 0, both nodes
+  // fill detection.pose.pose.covariance with the chosen pose's 36 doubles -- row-major in ROS' order (x, y, z, rotation about x, y,
+  // z; camera optical frame), copied without conversion -- and every RigidBundlePose carries its `covariance` the same way.  A record
+  // whose covariance is not valid keeps zeros.  0 (the default): off, the covariance all zero as the reference node leaves it.
+  double pose_covariance_sigma_px = 0;
 };
 
 class AprilTagNode {

@@ -106,6 +106,18 @@ POSE_REFINED, POSE_REFINED_NO_ALT, POSE_DEGENERATE = 0, 1, 2
 MAX_POSE_ITERATIONS = 200
 
 
+class PoseCovariance(C.Structure):
+    """amdAprilTagsPoseCovariance_t."""
+    _fields_ = [("cov", C.c_double * 36), ("cov_alt", C.c_double * 36), ("sq_err_sum", C.c_double), ("sq_err_sum_alt", C.c_double),
+                ("valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# the same record as a numpy dtype: what detector.refined_pose_covariances / bundle_pose_covariances_ex hand out
+POSE_COV_DTYPE = np.dtype([("cov", "<f8", (6, 6)), ("cov_alt", "<f8", (6, 6)), ("sq_err_sum", "<f8"), ("sq_err_sum_alt", "<f8"),
+                           ("valid", "<u4"), ("reserved", "<u4")])
+assert POSE_COV_DTYPE.itemsize == C.sizeof(PoseCovariance)
+
+
 class Float2(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float)]
 
@@ -153,7 +165,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetRectification", "amdAprilTagsSetResize", "amdAprilTagsDistortionFromName",
            "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex", "amdAprilTagsSetBundles", "amdAprilTagsGetBundlePoses",
            "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses",
-           "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx", "amdAprilTagsDebugReconcile"]
+           "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx", "amdAprilTagsDebugReconcile",
+           "amdAprilTagsSetPoseCovariance", "amdAprilTagsGetRefinedPoseCovariances", "amdAprilTagsGetBundlePoseCovariancesEx"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -243,6 +256,9 @@ def lib():
     L.amdAprilTagsGetBundlePosesEx.argtypes = [H, C.POINTER(BundlePoseEx), C.c_uint32]
     L.amdAprilTagsSetPoseRefinement.argtypes = [H, C.c_uint32]
     L.amdAprilTagsGetRefinedPoses.argtypes = [H, C.c_uint32, C.POINTER(RefinedPose), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.amdAprilTagsSetPoseCovariance.argtypes = [H, C.c_double]
+    L.amdAprilTagsGetRefinedPoseCovariances.argtypes = [H, C.c_uint32, C.POINTER(PoseCovariance), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.amdAprilTagsGetBundlePoseCovariancesEx.argtypes = [H, C.POINTER(PoseCovariance), C.c_uint32]
     L.amdAprilTagsDebugReconcile.argtypes = [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:

@@ -298,6 +298,14 @@ struct amdAprilTagsDetector_st {
   uint32_t last_ostride = 0;                            // ... with this many record slots per frame (finish_once reads it too)
   DevBuf<uint32_t> d_pose_cfg;
   HostBuf<PoseRefineRec> h_rposes;                      // pinned, max_batch x dcap: k_pose_refine writes frame * ostride + record, as k_reconcile does
+  // amdAprilTagsSetPoseCovariance: while pose_cov_sigma > 0 the two launches above run as their covariance instances and write these
+  // blocks, which are sized and owned as h_rposes and h_xposes are.  sigma^2 lives in device memory (d_cov_cfg[0]), so that changing
+  // it changes no launch argument; all three are allocated by the first call that turns the mode on
+  double pose_cov_sigma = 0.0;                          // 0: off
+  bool last_pose_cov = false;                           // the last submission ran the mode
+  DevBuf<double> d_cov_cfg;
+  HostBuf<PoseCovRec> h_rcovs;                          // pinned, max_batch x dcap, beside h_rposes
+  HostBuf<PoseCovRec> h_xcovs;                          // pinned, max_batch x AMDAT_MAX_BUNDLES, beside h_xposes
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1154,6 +1162,47 @@ int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAp
   return AMDAT_SUCCESS;
 }
 
+int amdAprilTagsSetPoseCovariance(amdAprilTagsHandle handle, double corner_sigma_px) {
+  if (!handle || !std::isfinite(corner_sigma_px) || corner_sigma_px < 0.0 || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  const bool on = corner_sigma_px > 0.0;
+  if (on) {
+    DeviceGuard guard(handle->device);
+    if (!guard.ok) return AMDAT_HIP_ERROR;
+    if (!handle->d_cov_cfg && !dev_alloc(handle, handle->d_cov_cfg, 64)) return AMDAT_OUT_OF_MEMORY;
+    if (!handle->h_rcovs && !host_alloc(handle, handle->h_rcovs, (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseCovRec)))
+      return AMDAT_OUT_OF_MEMORY;
+    if (!handle->h_xcovs && !host_alloc(handle, handle->h_xcovs, (size_t)handle->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(PoseCovRec)))
+      return AMDAT_OUT_OF_MEMORY;
+    // (no submission is in flight: nothing reads the value; it is pageable, so the copy is waited for before it goes)
+    const double sigma2 = corner_sigma_px * corner_sigma_px;
+    const hipStream_t s = handle->own_stream;
+    HIP_TRY(hipMemcpyAsync(handle->d_cov_cfg, &sigma2, sizeof(sigma2), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (on != (handle->pose_cov_sigma > 0.0)) drop_graphs(handle);   // captured with the one or the other instance; sigma^2 itself lives in device memory
+  handle->pose_cov_sigma = corner_sigma_px;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsGetRefinedPoseCovariances(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsPoseCovariance_t* out, uint32_t capacity, uint32_t* n) {
+  if (!handle || !out || !n || handle->inflight.active || !handle->last_pose_refined || !handle->last_pose_cov || frame >= handle->last_n)
+    return AMDAT_INVALID_ARGUMENT;
+  uint32_t k = handle->h_counters[frame].nout;
+  if (k > handle->last_ostride) k = handle->last_ostride;
+  *n = k;
+  if (capacity < k) return AMDAT_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < k; i++) out[i] = handle->h_rcovs[(size_t)frame * handle->last_ostride + i].c;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsGetBundlePoseCovariancesEx(amdAprilTagsHandle handle, amdAprilTagsPoseCovariance_t* out, uint32_t nframes) {
+  if (!handle || !out || handle->inflight.active || handle->last_nrigid == 0 || !handle->last_pose_cov || nframes > handle->last_n)
+    return AMDAT_INVALID_ARGUMENT;
+  const size_t n = (size_t)nframes * handle->last_nrigid;
+  for (size_t i = 0; i < n; i++) out[i] = handle->h_xcovs[i].c;
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
   if (!ksz || !std::isfinite(quad_sigma)) return AMDAT_INVALID_ARGUMENT;
   if (fabsf(quad_sigma) > 4.0f) return AMDAT_UNSUPPORTED;
@@ -1501,12 +1550,23 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   if (D->nbundles)   // S10: one wave per (frame, bundle) on the kept records, straight behind k_reconcile (kernels_bundle.h)
     hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
                        D->d_bundle_head, D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
+  // (amdAprilTagsSetPoseCovariance: the covariance instance of whichever of the two launches below runs; off, the launches as they were)
+  const bool cov = D->pose_cov_sigma > 0.0;
   if (D->nrigid)   // S12: two waves per (frame, bundle), one chain each, in the planar kind's place (kernels_rigid.h)
-    hipLaunchKernelGGL(k_bundle_rigid, dim3(n, AMDAT_MAX_BUNDLES), dim3(128), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
-                       D->d_rigid_head, D->d_rigid_members, D->d_rigid_table, D->h_xposes, P);
-  if (D->pose_iterations)   // S11: both minima of the records handed out, eight lanes per record, beside the bundles (kernels_pose.h)
-    hipLaunchKernelGGL(k_pose_refine, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
-                       D->d_pose_cfg, D->h_rposes, ostride, P);
+#define RIGID_LAUNCH(COV)                                                                                                           \
+  hipLaunchKernelGGL(k_bundle_rigid<COV>, dim3(n, AMDAT_MAX_BUNDLES), dim3(128), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, \
+                     D->d_rigid_head, D->d_rigid_members, D->d_rigid_table, D->h_xposes, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_xcovs)
+  {
+    if (cov) RIGID_LAUNCH(true); else RIGID_LAUNCH(false);
+  }
+#undef RIGID_LAUNCH
+#define POSE_LAUNCH(COV)                                                                                                            \
+  hipLaunchKernelGGL(k_pose_refine<COV>, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, \
+                     D->d_order, D->d_pose_cfg, D->h_rposes, ostride, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_rcovs)
+  if (D->pose_iterations) {   // S11: both minima of the records handed out, eight lanes per record, beside the bundles (kernels_pose.h)
+    if (cov) POSE_LAUNCH(true); else POSE_LAUNCH(false);
+  }
+#undef POSE_LAUNCH
   mark();
   return AMDAT_SUCCESS;
 }
@@ -1707,6 +1767,18 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
         for (uint32_t i = 0; i < k; i++)
           if (static_cast<volatile PoseRefineRec*>(D->h_rposes)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
       }
+    // pose covariance on: the covariance records beside both kinds carry the stamp as well
+    if (D->pose_cov_sigma > 0.0) {
+      for (uint32_t r = 0; r < D->launched_n * D->nrigid; r++)
+        if (static_cast<volatile PoseCovRec*>(D->h_xcovs)[r].seq != D->seq) return false;
+      if (D->pose_iterations)
+        for (uint32_t f = 0; f < D->launched_n; f++) {
+          uint32_t k = D->h_counters[f].nout;
+          if (k > D->last_ostride) k = D->last_ostride;
+          for (uint32_t i = 0; i < k; i++)
+            if (static_cast<volatile PoseCovRec*>(D->h_rcovs)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
+        }
+    }
     return true;
   };
   if (!stamped()) {
@@ -1801,6 +1873,7 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
   D->last_pose_refined = D->pose_iterations > 0;
+  D->last_pose_cov = D->pose_cov_sigma > 0.0;
   D->last_ostride = ostride;
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
     D->pending_hash_grow = false;
@@ -2011,6 +2084,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   handle->last_nbundles = 0;        // (never solves bundles)
   handle->last_nrigid = 0;
   handle->last_pose_refined = false;   // (never refines poses)
+  handle->last_pose_cov = false;
   handle->last_rectified = false;   // (never rectifies)
   handle->last_resized = false;     // (never resizes)
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));
@@ -2225,7 +2299,7 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
   if (!guard.ok) return AMDAT_HIP_ERROR;
   const hipStream_t s = D->own_stream;
   HIP_TRY(hipDeviceSynchronize());
-  D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_rectified = false; D->last_resized = false;
+  D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_pose_cov = false; D->last_rectified = false; D->last_resized = false;
   FrameDesc fd;
   memset(&fd, 0, sizeof(fd));
   fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;

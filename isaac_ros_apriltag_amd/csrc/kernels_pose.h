@@ -3,14 +3,25 @@
 // chain 0 on corners 0 .. 3, lanes 4 .. 7 run chain 1 -- and every sum over the four corners is the two-step butterfly over the
 // lanes of a quad on the DPP network (quad_perm), which leaves (x0 + x1) + (x2 + x3) on all four.  FP64 throughout, one IEEE
 // operation per operator (-ffp-contract=off).  No LDS, no barrier, no scratch.
+// k_pose_refine<true> (amdAprilTagsSetPoseCovariance, pose_covariance.h) adds, behind the chains, the Jacobian
+// pass of each quad at its chain's pose -- 22 more sums on the same butterfly -- and the 6 x 6 inversion; k_pose_refine<false> is
+// the kernel without any of it.
 #pragma once
 #include "common.h"
 #include "kernels_decode.h"   // pose_from_homography_dev
+#include "pose_covariance.h"
 #include "pose_refine.h"
 
 // A refined record in the pinned host block: the public record and the stamp of the launch that wrote it, stored last.
 struct PoseRefineRec {
   amdAprilTagsRefinedPose_t pose;
+  uint32_t seq;
+  uint32_t pad;
+};
+
+// A covariance record in a pinned host block of its own, beside the pose record's: the public record and the launch's stamp.
+struct PoseCovRec {
+  amdAprilTagsPoseCovariance_t c;
   uint32_t seq;
   uint32_t pad;
 };
@@ -43,10 +54,13 @@ static inline uint32_t pose_refine_waves(uint32_t ostride) {
 // min(nout, host_stride) -- the records k_reconcile handed out; a wave beyond them returns.  cfg[0]: the iteration count (device
 // memory: changing it changes no launch argument).  Every lane of a wave that runs stays active through the iteration (a group
 // beyond the last record repeats that record and stores nothing), so that the DPP moves always read live lanes.
+// COV: cov_cfg[0] is sigma^2 (device memory, as the count), cov_out the covariance records, laid out as host_out.
+template <bool COV>
 __global__ __launch_bounds__(64) void k_pose_refine(const FrameDesc* __restrict__ frames, const DetRec* __restrict__ dets_all,
                                                     const FrameCounters* __restrict__ counters, const uint16_t* __restrict__ order_all,
                                                     const uint32_t* __restrict__ cfg, PoseRefineRec* __restrict__ host_out,
-                                                    uint32_t host_stride, DetParams P) {
+                                                    uint32_t host_stride, DetParams P, const double* __restrict__ cov_cfg,
+                                                    PoseCovRec* __restrict__ cov_out) {
   const int frame = (int)blockIdx.x + P.frame0;
   uint32_t nout = counters[frame].nout;
   if (nout > P.dcap) nout = P.dcap;
@@ -91,6 +105,45 @@ __global__ __launch_bounds__(64) void k_pose_refine(const FrameDesc* __restrict_
   for (int e = 0; e < 3; e++) t1[e] = __shfl(t[e], src);
   const double E1 = __shfl(E, src);
   const bool ok1 = __shfl((int)ok, src) != 0;
+  if constexpr (COV) {
+    // each quad at the pose the record reports for its chain: chain 0's, or the homography pose where chain 0 was degenerate; chain
+    // 1's.  All lanes stay active through the sums and run the inversion; lanes 0 and 4 of a record store.
+    const int lane0 = lane & ~7;
+    double Re[9], te[3];
+#pragma unroll
+    for (int e = 0; e < 9; e++) { const double r1 = POSE_COV_CHAIN1_AT(R[e], lane0); Re[e] = second ? r1 : ok ? R[e] : Rh[e]; }
+#pragma unroll
+    for (int e = 0; e < 3; e++) { const double t1c = POSE_COV_CHAIN1_AT(t[e], lane0); te[e] = second ? t1c : ok ? t[e] : th[e]; }
+    const double zero[1] = {0.0};
+    double N[21], sq, cov[36];
+    pc_normal<1>(C.px, C.py, zero, pix, Re, te, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, sum, N, &sq);
+    const bool inv = pc_invert(N, cov_cfg[0], cov);
+    // the outcome rule of pr_outcome on both storing lanes: chain 0's ok and E reach lane 4 by one shuffle each
+    const bool ok0 = __shfl((int)ok, lane0) != 0;
+    const double E0 = __shfl(E, lane0);
+    const bool alt = ok0 && ok1;
+    const bool chose1 = alt && E1 < E0;
+    const bool to_alt = second != chose1;          // this lane's pose is the record's alternative ...
+    const bool have = !to_alt || alt;              // ... which exists only where both chains ran
+    const bool good = have && inv;
+    PoseCovRec* co = &cov_out[(size_t)frame * host_stride + i];
+    if (live && (lane & 3) == 0) {
+      double* dst = to_alt ? co->c.cov_alt : co->c.cov;
+#pragma unroll
+      for (int e = 0; e < 36; e++) dst[e] = good ? cov[e] : 0.0;
+      *(to_alt ? &co->c.sq_err_sum_alt : &co->c.sq_err_sum) = have ? sq : 0.0;
+    }
+    // the valid word is the first lane's: its own bit and lane 4's.  The stores above are earlier instructions of this wave, so the
+    // fence below, which waits for the wave's outstanding stores, stands behind both lanes' doubles
+    const bool good4 = __shfl((int)good, src) != 0;
+    const bool to_alt4 = __shfl((int)to_alt, src) != 0;
+    if (live && (lane & 7) == 0) {
+      co->c.valid = (good ? (to_alt ? 2u : 1u) : 0u) | (good4 ? (to_alt4 ? 2u : 1u) : 0u);
+      co->c.reserved = 0u;
+      __threadfence_system();
+      __hip_atomic_store(&co->seq, fd.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
   if (live && (lane & 7) == 0) {
     PoseRefineRec* o = &host_out[(size_t)frame * host_stride + i];
     pr_outcome(ok, R, t, E, ok1, R1, t1, E1, Rh, th, Eh, &o->pose);

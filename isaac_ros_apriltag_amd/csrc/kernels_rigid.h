@@ -7,10 +7,16 @@
 // the rows across bit 4 and ds_bpermute for the halves across bit 5 -- the two DS instructions use the LDS crossbar, not its memory.
 // No LDS access and no barrier inside the iteration; chain 1's result crosses to wave 0 through LDS once, behind one barrier.  FP64
 // throughout, one IEEE operation per operator (-ffp-contract=off).
+// k_bundle_rigid<true> (amdAprilTagsSetPoseCovariance, pose_covariance.h) adds, behind each wave's chain, the
+// Jacobian pass at that wave's pose -- 22 more sums on the same butterfly -- and the 6 x 6 inversion; the waves then learn each
+// other's outcome through LDS behind the same barrier, lane 0 of each stores its 36 doubles, and a second barrier puts the stamp
+// behind both.  k_bundle_rigid<false> is the kernel without any of it.
 #pragma once
 #include "common.h"
 #include "kernels_bundle.h"   // bundle_classify
 #include "kernels_decode.h"   // pose_from_homography_dev
+#include "kernels_pose.h"     // PoseCovRec
+#include "pose_covariance.h"
 #include "rigid_layout.h"
 #include "rigid_pose.h"
 
@@ -46,10 +52,13 @@ struct RgSumWave {
 // change of the layout changes no launch parameter (a captured graph stays valid).  The iteration counts, the gates and the whole
 // layout live in device memory.  Every lane of both waves stays active from the classification to the barrier, so that the
 // cross-lane moves always read live lanes.
+// COV: cov_cfg[0] is sigma^2 (device memory), cov_out the covariance records, laid out as host_out.
+template <bool COV>
 __global__ __launch_bounds__(128) void k_bundle_rigid(const FrameDesc* __restrict__ frames, const DetRec* __restrict__ dets_all,
                                                       const FrameCounters* __restrict__ counters, const uint16_t* __restrict__ order_all,
                                                       const RigidHeadDev* __restrict__ head, const RigidMemberDev* __restrict__ members,
-                                                      const uint16_t* __restrict__ table, RigidPoseRec* __restrict__ host_out, DetParams P) {
+                                                      const uint16_t* __restrict__ table, RigidPoseRec* __restrict__ host_out, DetParams P,
+                                                      const double* __restrict__ cov_cfg, PoseCovRec* __restrict__ cov_out) {
   const uint32_t b = blockIdx.y;
   const uint32_t nb = head->nbundles;
   if (b >= nb) return;
@@ -67,6 +76,8 @@ __global__ __launch_bounds__(128) void k_bundle_rigid(const FrameDesc* __restric
   __shared__ double s_sq[2][RG_SLOTS];   // the pixel reprojection sums per slot under chain 0's and chain 1's pose
   __shared__ double s_chain1[13];        // R, t, E of chain 1
   __shared__ int s_ok1;
+  __shared__ double s_E0;                // COV: what wave 1 needs of chain 0, and wave 0 of wave 1's inversion
+  __shared__ int s_ok0, s_valid1;
 
   // ---- classification: each wave classifies every kept record for itself, in chunks of 64 (k_bundle_pose's statement), and compacts
   // the used ones into the tag slots in record order: lane s takes the (s - slots filled so far)-th used record of the chunk ----
@@ -100,6 +111,13 @@ __global__ __launch_bounds__(128) void k_bundle_rigid(const FrameDesc* __restric
       o->pose.status = AMDAT_BUNDLE_TOO_FEW_TAGS;
       o->pose.ntags = ntags;
       o->pose.nskipped = nskipped;
+      if constexpr (COV) {   // a zeroed covariance record
+        PoseCovRec* co = &cov_out[(size_t)frame * nb + b];
+        uint32_t* cw = reinterpret_cast<uint32_t*>(&co->c);
+        for (uint32_t k = 0; k < sizeof(co->c) / 4; k++) cw[k] = 0u;
+        __threadfence_system();
+        __hip_atomic_store(&co->seq, fd.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
       __threadfence_system();
       __hip_atomic_store(&o->seq, fd.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -167,7 +185,52 @@ __global__ __launch_bounds__(128) void k_bundle_rigid(const FrameDesc* __restric
     s_chain1[12] = E;
     s_ok1 = ok ? 1 : 0;
   }
+  double cov[36];
+  bool inv = false;
+  if constexpr (COV) {
+    // this wave's pose as the record reports it: its chain's, or -- wave 0 with a degenerate chain -- the seed start, which the
+    // record reports where both chains were degenerate.  All lanes stay active through the sums and run the inversion.
+    double Re[9], te[3], qx[4], qy[4], qz[4], N[21], sq;
+#pragma unroll
+    for (int e = 0; e < 9; e++) Re[e] = (second || ok) ? R[e] : Rs0[e];
+#pragma unroll
+    for (int e = 0; e < 3; e++) te[e] = (second || ok) ? t[e] : ts0[e];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      qx[k] = RIGID_COV_POINT(C.px[k], C.cx[k]); qy[k] = RIGID_COV_POINT(C.py[k], C.cy[k]); qz[k] = RIGID_COV_POINT(C.pz[k], C.cz[k]);
+    }
+    pc_normal<4>(qx, qy, qz, pix, Re, te, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, sum, N, &sq);
+    inv = pc_invert(N, cov_cfg[0], cov);
+    if (!second && lane == 0) { s_ok0 = ok ? 1 : 0; s_E0 = E; }
+  }
   __syncthreads();
+  if constexpr (COV) {
+    // the outcome rule of rg_outcome on lane 0 of both waves; each stores its own 36 doubles into the half its pose went to
+    PoseCovRec* co = &cov_out[(size_t)frame * nb + b];
+    const bool ok0 = s_ok0 != 0, ok1 = s_ok1 != 0;
+    const bool alt = ok0 && ok1;
+    const bool chose1 = ok1 && (!ok0 || s_chain1[12] < s_E0);
+    const bool to_alt = second != chose1;           // this wave's pose is the record's alternative (wave 0's seed start never is) ...
+    const bool have = !to_alt || alt;               // ... which exists only where both chains ran
+    const bool good = have && inv;
+    if (lane == 0) {
+      double* dst = to_alt ? co->c.cov_alt : co->c.cov;
+#pragma unroll
+      for (int e = 0; e < 36; e++) dst[e] = good ? cov[e] : 0.0;
+      if (second) {
+        s_valid1 = good ? (to_alt ? 2 : 1) : 0;
+        __threadfence_system();   // wave 1's doubles are out before the barrier that the stamp stands behind
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      co->c.sq_err_sum = 0.0; co->c.sq_err_sum_alt = 0.0;
+      co->c.valid = (good ? (to_alt ? 2u : 1u) : 0u) | (uint32_t)s_valid1;
+      co->c.reserved = 0u;
+      __threadfence_system();
+      __hip_atomic_store(&co->seq, fd.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
 
   // ---- the outcome and the record, straight to the pinned host block; the launch's stamp goes last, behind a system-wide fence ----
   if (threadIdx.x == 0) {

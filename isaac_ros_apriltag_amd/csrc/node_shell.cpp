@@ -53,6 +53,9 @@ struct DetectorApi {
   decltype(&amdAprilTagsGetBundlePosesEx) get_bundle_poses_ex = nullptr;
   decltype(&amdAprilTagsSetPoseRefinement) set_pose_refinement = nullptr;
   decltype(&amdAprilTagsGetRefinedPoses) get_refined_poses = nullptr;
+  decltype(&amdAprilTagsSetPoseCovariance) set_pose_covariance = nullptr;
+  decltype(&amdAprilTagsGetRefinedPoseCovariances) get_refined_pose_covariances = nullptr;
+  decltype(&amdAprilTagsGetBundlePoseCovariancesEx) get_bundle_pose_covariances_ex = nullptr;
 };
 
 DetectorApi& api() {
@@ -98,6 +101,9 @@ DetectorApi& api() {
   BIND(get_bundle_poses_ex, "amdAprilTagsGetBundlePosesEx")
   BIND(set_pose_refinement, "amdAprilTagsSetPoseRefinement")
   BIND(get_refined_poses, "amdAprilTagsGetRefinedPoses")
+  BIND(set_pose_covariance, "amdAprilTagsSetPoseCovariance")
+  BIND(get_refined_pose_covariances, "amdAprilTagsGetRefinedPoseCovariances")
+  BIND(get_bundle_pose_covariances_ex, "amdAprilTagsGetBundlePoseCovariancesEx")
 #undef BIND
   return a;
 }
@@ -247,11 +253,31 @@ void apply_pose_refinement(amdAprilTagsHandle detector, const NodeOptions& opt) 
   if (error != 0) throw std::runtime_error("'pose_refinement' " + std::to_string(opt.pose_refinement) + " refused (error code " + std::to_string(error) + ")");
 }
 
+// NodeOptions::pose_covariance_sigma_px on a freshly created handle
+void apply_pose_covariance(amdAprilTagsHandle detector, const NodeOptions& opt) {
+  if (opt.pose_covariance_sigma_px == 0.0) return;
+  const int error = api().set_pose_covariance(detector, opt.pose_covariance_sigma_px);
+  if (error != 0)
+    throw std::runtime_error("'pose_covariance_sigma_px' " + std::to_string(opt.pose_covariance_sigma_px) + " refused (error code " + std::to_string(error) + ")");
+}
+
 // NodeOptions::pose_refinement: the pose of every tag of frame `frame` of the submission that just returned becomes the chosen refined
 // one (amdAprilTagsGetRefinedPoses: record i belongs to tag i) -- translation and column-major orientation in float, as the library
 // forms them from the homography pose.  (The node runs the default corner convention: R as solved.)
-bool refine_tags(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t frame, amdAprilTagsID_t* tags, uint32_t num_detections) {
+// NodeOptions::pose_covariance_sigma_px with it: covs[i] is the chosen pose's covariance, the 36 doubles as the library hands them
+// out (row-major in ROS' order), or zeros where the record's is not valid; off, covs stays empty.
+bool refine_tags(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t frame, amdAprilTagsID_t* tags, uint32_t num_detections,
+                 std::vector<std::array<double, 36>>* covs) {
+  covs->clear();
   if (opt.pose_refinement == 0) return true;
+  if (opt.pose_covariance_sigma_px != 0.0) {
+    std::vector<amdAprilTagsPoseCovariance_t> crecs(num_detections ? num_detections : 1u);
+    uint32_t cn = 0;
+    if (api().get_refined_pose_covariances(detector, frame, crecs.data(), num_detections, &cn) != 0 || cn != num_detections) return false;
+    covs->resize(num_detections);
+    for (uint32_t i = 0; i < cn; i++)
+      for (int k = 0; k < 36; k++) (*covs)[i][k] = (crecs[i].valid & 1u) ? crecs[i].cov[k] : 0.0;
+  }
   std::vector<amdAprilTagsRefinedPose_t> recs(num_detections ? num_detections : 1u);
   uint32_t n = 0;
   if (api().get_refined_poses(detector, frame, recs.data(), num_detections, &n) != 0 || n != num_detections) return false;
@@ -309,6 +335,12 @@ bool collect_rigid_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, 
   if (nb == 0) return true;
   std::vector<amdAprilTagsBundlePoseEx_t> recs(static_cast<size_t>(nframes) * nb);
   if (api().get_bundle_poses_ex(detector, recs.data(), nframes) != 0) return false;
+  // NodeOptions::pose_covariance_sigma_px: the chosen pose's covariance beside every record, zeros where it is not valid
+  std::vector<amdAprilTagsPoseCovariance_t> crecs;
+  if (opt.pose_covariance_sigma_px != 0.0) {
+    crecs.resize(recs.size());
+    if (api().get_bundle_pose_covariances_ex(detector, crecs.data(), nframes) != 0) return false;
+  }
   for (uint32_t f = 0; f < nframes; f++) {
     for (size_t b = 0; b < nb; b++) {
       const amdAprilTagsBundlePoseEx_t& r = recs[f * nb + b];
@@ -318,6 +350,8 @@ bool collect_rigid_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, 
       p.err = r.err; p.sq_err_sum = r.sq_err_sum; p.err_alt = r.err_alt; p.sq_err_sum_alt = r.sq_err_sum_alt;
       for (int i = 0; i < 9; i++) { p.R[i] = r.R[i]; p.R_alt[i] = r.R_alt[i]; }
       for (int i = 0; i < 3; i++) { p.t[i] = r.t[i]; p.t_alt[i] = r.t_alt[i]; }
+      if (!crecs.empty() && (crecs[f * nb + b].valid & 1u))
+        for (int i = 0; i < 36; i++) p.covariance[i] = crecs[f * nb + b].cov[i];
       (*poses)[f].push_back(p);
       if (r.status != AMDAT_BUNDLE_SOLVED) continue;
       TransformStamped tf;
@@ -398,7 +432,8 @@ Quaternion quaternion_from_colmajor(const float* o) {
 
 // AprilTagDetectionArray + TF transforms of one frame from the detector's records (src/apriltag_node.cpp:499-549)
 void assemble_messages(const amdAprilTagsID_t* tags, uint32_t num_detections, const Header& info_header, const std::string& family,
-                       AprilTagDetectionArray* msg_out, std::vector<TransformStamped>* tfs_out) {
+                       AprilTagDetectionArray* msg_out, std::vector<TransformStamped>* tfs_out,
+                       const std::vector<std::array<double, 36>>* covs = nullptr) {
   AprilTagDetectionArray& msg = *msg_out;
   std::vector<TransformStamped>& tfs = *tfs_out;
   msg.header = info_header;  // camera_info header, not the image header (src/apriltag_node.cpp:501)
@@ -427,6 +462,7 @@ void assemble_messages(const amdAprilTagsID_t* tags, uint32_t num_detections, co
     det.pose.pose.pose.position.y = tf.transform.translation.y;
     det.pose.pose.pose.position.z = tf.transform.translation.z;
     det.pose.pose.pose.orientation = tf.transform.rotation;
+    if (covs && i < covs->size()) det.pose.pose.covariance = (*covs)[i];   // (the doubles as they are: no conversion)
     msg.detections.push_back(det);
   }
 }
@@ -559,6 +595,7 @@ struct AprilTagNode::Impl {
     apply_bundles(detector, opt);
     apply_rigid_bundles(detector, opt);
     apply_pose_refinement(detector, opt);
+    apply_pose_covariance(detector, opt);
     width = info.width;
     height = info.height;
     if (!stream && api().stream_create(&stream) != 0) throw std::runtime_error("stream creation failed");
@@ -625,13 +662,14 @@ struct AprilTagNode::Impl {
       std::fprintf(stderr, "[apriltag_node] Failed to run AprilTags detector (error code %d)\n", error);
       return;
     }
-    if (!refine_tags(detector, opt, 0, tags.data(), num_detections)) {
-      std::fprintf(stderr, "[apriltag_node] refined poses not available: frame dropped\n");
+    std::vector<std::array<double, 36>> covs;
+    if (!refine_tags(detector, opt, 0, tags.data(), num_detections, &covs)) {
+      std::fprintf(stderr, "[apriltag_node] refined poses or their covariances not available: frame dropped\n");
       return;
     }
     AprilTagDetectionArray msg;
     std::vector<TransformStamped> tfs;
-    assemble_messages(tags.data(), num_detections, info.header, opt.tag_family, &msg, &tfs);
+    assemble_messages(tags.data(), num_detections, info.header, opt.tag_family, &msg, &tfs, &covs);
     {
       std::vector<std::vector<BundlePose>> poses;
       const Header* hdr = &info.header;
@@ -742,6 +780,7 @@ struct AprilTagMultiCameraNode::Impl {
     apply_bundles(detector, opt);
     apply_rigid_bundles(detector, opt);
     apply_pose_refinement(detector, opt);
+    apply_pose_covariance(detector, opt);
     width = cfg.width;
     height = cfg.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
@@ -915,11 +954,13 @@ uint32_t AprilTagMultiCameraNode::Flush() {
   std::vector<const Header*> headers(n);
   std::vector<std::vector<TransformStamped>*> tf_ptrs(n);
   for (uint32_t i = 0; i < n; i++) {
-    if (!refine_tags(I.detector, I.opt, i, tags.data() + static_cast<size_t>(i) * max_tags, counts[i])) {
-      std::fprintf(stderr, "[apriltag_node] refined poses not available: round dropped\n");
+    std::vector<std::array<double, 36>> covs;
+    if (!refine_tags(I.detector, I.opt, i, tags.data() + static_cast<size_t>(i) * max_tags, counts[i], &covs)) {
+      std::fprintf(stderr, "[apriltag_node] refined poses or their covariances not available: round dropped\n");
       return 0;
     }
-    assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt.tag_family, &msgs[i], &tfs[i]);
+    assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt.tag_family, &msgs[i], &tfs[i],
+                      &covs);
     headers[i] = &I.slots[who[i]].info_header;
     tf_ptrs[i] = &tfs[i];
   }
@@ -1221,6 +1262,44 @@ NodeShellHarness* node_shell_create_refined(int max_tags, double size, int tile_
     return nullptr;
   }
 }
+// AprilTagNode with NodeOptions::pose_covariance_sigma_px beside pose_refinement and / or rigid_bundles (nbundles 0: none)
+NodeShellHarness* node_shell_create_covariance(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                               int decimate, uint32_t pose_refinement, int nbundles, const NodeShellRigidBundle* bundles,
+                                               double pose_covariance_sigma_px, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    set_rigid_bundle_options(&o, nbundles, bundles);
+    o.pose_covariance_sigma_px = pose_covariance_sigma_px;
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+// detection.pose.pose.covariance of the last published message, 36 doubles per detection; the number of detections
+static int copy_covariances(const AprilTagDetectionArray& m, double* out36, int max_out) {
+  const int n = static_cast<int>(m.detections.size());
+  for (int i = 0; i < n && i < max_out; i++)
+    for (int k = 0; k < 36; k++) out36[36 * i + k] = m.detections[i].pose.pose.covariance[k];
+  return n;
+}
+static int copy_rigid_covariances(const std::vector<amd::isaac_ros::apriltag::RigidBundlePose>& poses, double* out36, int max_out) {
+  const int n = static_cast<int>(poses.size());
+  for (int i = 0; i < n && i < max_out; i++)
+    for (int k = 0; k < 36; k++) out36[36 * i + k] = poses[i].covariance[k];
+  return n;
+}
+int node_shell_last_covariances(NodeShellHarness* h, double* out36, int max_out) { return copy_covariances(h->last, out36, max_out); }
+int node_shell_last_rigid_covariances(NodeShellHarness* h, double* out36, int max_out) {
+  return copy_rigid_covariances(h->node->last_rigid_bundle_poses(), out36, max_out);
+}
 // the transforms of the last published frame (tags first, then one per solved bundle), and its bundle records
 int node_shell_last_transforms(NodeShellHarness* h, NodeShellTransform* out, int max_out) { return copy_transforms(h->last_tf, out, max_out); }
 int node_shell_last_bundle_poses(NodeShellHarness* h, NodeShellBundlePose* out, int max_out) {
@@ -1404,6 +1483,35 @@ MultiShellHarness* node_shell_multi_create_refined(int num_streams, int max_tags
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+MultiShellHarness* node_shell_multi_create_covariance(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                      const char* backends, int decimate, int auto_flush, uint32_t pose_refinement,
+                                                      int nbundles, const NodeShellRigidBundle* bundles, double pose_covariance_sigma_px,
+                                                      char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    set_rigid_bundle_options(&o, nbundles, bundles);
+    o.pose_covariance_sigma_px = pose_covariance_sigma_px;
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+int node_shell_multi_last_covariances(MultiShellHarness* h, int stream, double* out36, int max_out) {
+  return copy_covariances(h->last[stream], out36, max_out);
+}
+int node_shell_multi_last_rigid_covariances(MultiShellHarness* h, int stream, double* out36, int max_out) {
+  return copy_rigid_covariances(h->node->last_rigid_bundle_poses(static_cast<uint32_t>(stream)), out36, max_out);
 }
 int node_shell_multi_last_transforms(MultiShellHarness* h, int stream, NodeShellTransform* out, int max_out) {
   return copy_transforms(h->last_tf[stream], out, max_out);

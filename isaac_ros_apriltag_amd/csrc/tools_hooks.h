@@ -55,7 +55,11 @@
 //                           23 = quads_overlap_dev (k_reconcile) without its two containment tests: a duplicate strictly inside another
 //                               record of its id survives
 //                           24 = det_before_dev (k_reconcile) compares decision margins ascending
-//                           (4 .. 24 change values only: no address, index bound, launch size or loop count)
+//                           25 = the pose covariance (pose_covariance.h) leaves the skew term b out of J_u: wrong only under a camera
+//                               with skew
+//                           26 = the second quad of k_pose_refine<true> evaluates the covariance at chain 0's pose: cov_alt equals cov
+//                           27 = the covariance of a rigid bundle takes P - mean P for the object point P
+//                           (4 .. 27 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -66,7 +70,8 @@
 //                           tests/test_bundles_gpu.py::test_the_bundle_tests_fail_on_the_wrong_builds for 15 and 16,
 //                           tests/test_pose_refine_gpu.py::test_the_pose_refinement_tests_fail_on_the_wrong_builds for 17 and 18,
 //                           tests/test_rigid_bundles_gpu.py::test_the_rigid_bundle_tests_fail_on_the_wrong_builds for 19 and 20,
-//                           tests/test_decode_stage_gpu.py::test_the_decode_stage_tests_fail_on_the_wrong_builds for 21 .. 24)
+//                           tests/test_decode_stage_gpu.py::test_the_decode_stage_tests_fail_on_the_wrong_builds for 21 .. 24,
+//                           tests/test_pose_covariance_gpu.py::test_the_pose_covariance_tests_fail_on_the_wrong_builds for 25 .. 27)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -168,6 +173,24 @@
 #define RIGID_NPTS(n) ((void)(n), 4.0)
 #else
 #define RIGID_NPTS(n) (n)
+#endif
+
+// ---- pose_covariance.h: the skew term of J_u; the pose the second quad of k_pose_refine<true> evaluates at (own: its chain's entry,
+// ---- lane0: the lane of the record's first quad); the object point of a rigid bundle's covariance (p: the point, c: p - mean p) ----------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 25
+#define POSE_COV_JU_SKEW(b) ((void)(b), 0.0)
+#else
+#define POSE_COV_JU_SKEW(b) (b)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 26
+#define POSE_COV_CHAIN1_AT(own, lane0) __shfl((own), (lane0))
+#else
+#define POSE_COV_CHAIN1_AT(own, lane0) ((void)(lane0), (own))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 27
+#define RIGID_COV_POINT(p, c) ((void)(p), (c))
+#else
+#define RIGID_COV_POINT(p, c) ((void)(c), (p))
 #endif
 
 // ---- k_decode_wave: whether step k of `steps` of the normal search enters the sums (in: both reads lie inside the image), and whether

@@ -51,7 +51,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, pose_refinement=0, bundles_ex=None, **caps):
+                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -83,6 +83,7 @@ class AprilTagDetector:
         self.nbundles = 0
         self.nbundles_ex = 0
         self.pose_refinement = 0
+        self.pose_covariance = 0.0
         try:
             if quad_sigma:
                 self.set_quad_sigma(quad_sigma)
@@ -98,6 +99,8 @@ class AprilTagDetector:
                 self.set_bundles_ex(bundles_ex)
             if pose_refinement:
                 self.set_pose_refinement(pose_refinement)
+            if pose_covariance:
+                self.set_pose_covariance(pose_covariance)
         except Exception:
             self.close()
             raise
@@ -201,6 +204,38 @@ class AprilTagDetector:
                          "err": float(r.err), "R_alt": np.array(list(r.R_alt)).reshape(3, 3), "t_alt": np.array(list(r.t_alt)),
                          "err_alt": float(r.err_alt), "err_homography": float(r.err_homography)} for r in arr[:cnt.value]])
         return out
+
+    def set_pose_covariance(self, sigma_px):
+        """amdAprilTagsSetPoseCovariance: every pose that set_pose_refinement and set_bundles_ex hand out comes with a first-order
+        6 x 6 covariance in ROS' PoseWithCovariance order (x, y, z, rotation about x, y, z; camera optical frame), for independent corner
+        noise of standard deviation sigma_px, which is the caller's figure; 0 turns it off.  refined_pose_covariances(n) and
+        bundle_pose_covariances_ex(n) hand out the records."""
+        capi._check("amdAprilTagsSetPoseCovariance", self._L.amdAprilTagsSetPoseCovariance(self._h, float(sigma_px)))
+        self.pose_covariance = float(sigma_px)
+
+    def refined_pose_covariances(self, n):
+        """amdAprilTagsGetRefinedPoseCovariances: the covariance records beside refined_poses(n), a numpy array of capi.POSE_COV_DTYPE
+        per frame ("cov", "cov_alt" (6x6), "sq_err_sum", "sq_err_sum_alt", "valid": bit 0 cov, bit 1 cov_alt)."""
+        out = []
+        for f in range(n):
+            cnt = C.c_uint32(0)
+            probe = (capi.PoseCovariance * 1)()
+            rc = self._L.amdAprilTagsGetRefinedPoseCovariances(self._h, f, probe, 0, C.byref(cnt))   # the count (refused for its capacity when > 0)
+            if rc and cnt.value == 0:
+                capi._check("amdAprilTagsGetRefinedPoseCovariances", rc)
+            arr = np.zeros(max(cnt.value, 1), dtype=capi.POSE_COV_DTYPE)
+            capi._check("amdAprilTagsGetRefinedPoseCovariances", self._L.amdAprilTagsGetRefinedPoseCovariances(
+                self._h, f, arr.ctypes.data_as(C.POINTER(capi.PoseCovariance)), cnt.value, C.byref(cnt)))
+            out.append(arr[:cnt.value])
+        return out
+
+    def bundle_pose_covariances_ex(self, n):
+        """amdAprilTagsGetBundlePoseCovariancesEx: the covariance records beside bundle_poses_ex(n), a numpy array of
+        capi.POSE_COV_DTYPE of shape (n, bundles)."""
+        arr = np.zeros(max(n * self.nbundles_ex, 1), dtype=capi.POSE_COV_DTYPE)
+        capi._check("amdAprilTagsGetBundlePoseCovariancesEx", self._L.amdAprilTagsGetBundlePoseCovariancesEx(
+            self._h, arr.ctypes.data_as(C.POINTER(capi.PoseCovariance)), n))
+        return arr[:n * self.nbundles_ex].reshape(n, self.nbundles_ex)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

@@ -147,8 +147,28 @@ def lib():
         L.node_shell_last_rigid_bundle_poses.argtypes = [C.c_void_p, C.POINTER(ShellRigidBundlePose), C.c_int]
         L.node_shell_multi_last_rigid_bundle_poses.restype = C.c_int
         L.node_shell_multi_last_rigid_bundle_poses.argtypes = [C.c_void_p, C.c_int, C.POINTER(ShellRigidBundlePose), C.c_int]
+        L.node_shell_create_covariance.restype = C.c_void_p
+        L.node_shell_create_covariance.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int,
+                                                   C.POINTER(ShellRigidBundle), C.c_double, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_covariance.restype = C.c_void_p
+        L.node_shell_multi_create_covariance.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                         C.c_uint32, C.c_int, C.POINTER(ShellRigidBundle), C.c_double, C.c_char_p, C.c_size_t]
+        for fn in (L.node_shell_last_covariances, L.node_shell_last_rigid_covariances):
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
+        for fn in (L.node_shell_multi_last_covariances, L.node_shell_multi_last_rigid_covariances):
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int]
         _lib = L
     return _lib
+
+
+def _covariances(call, max_out):
+    """The 6 x 6 covariances a flat-view call hands out (36 doubles each), as a list of numpy arrays."""
+    import numpy as np
+    out = (C.c_double * (36 * max_out))()
+    n = min(call(out, max_out), max_out)
+    return [np.array(out[36 * i:36 * (i + 1)]).reshape(6, 6) for i in range(n)]
 
 
 def _shell_bundles(bundles):
@@ -268,7 +288,7 @@ class AprilTagMultiCameraNode:
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
                  auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None, pose_refinement=0,
-                 rigid_bundles=None):
+                 rigid_bundles=None, pose_covariance=0.0):
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
         undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
@@ -279,11 +299,23 @@ class AprilTagMultiCameraNode:
         pose_refinement (NodeOptions::pose_refinement, alone among the extensions): iterations of the orthogonal-iteration pose -- the
         detections' poses and the tags' transforms are the chosen refined pose.  rigid_bundles (NodeOptions::rigid_bundles, alone among
         the extensions): [{"name", "iterations", "members": [(id, (x, y, z), (qw, qx, qy, qz), size)], ...}] -- one "bundle:<name>"
-        transform per solved rigid bundle, from the chosen pose."""
+        transform per solved rigid bundle, from the chosen pose.  pose_covariance (NodeOptions::pose_covariance_sigma_px, with
+        pose_refinement and / or rigid_bundles): the corner noise in pixels -- covariances(stream) and rigid_bundle_covariances(stream)
+        hand out what the node published."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags, self.num_streams = max_tags, num_streams
+        if pose_covariance:
+            if bundles or quad_sigma or max_width or max_height or rectify or resize or not (pose_refinement or rigid_bundles):
+                raise ValueError("pose_covariance is served with pose_refinement and / or rigid_bundles by this view, and with nothing else")
+            arr = _shell_rigid_bundles(rigid_bundles or [])
+            self._h = self._L.node_shell_multi_create_covariance(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(),
+                                                                 decimate, 1 if auto_flush else 0, int(pose_refinement), len(arr), arr,
+                                                                 float(pose_covariance), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if rigid_bundles:
             if bundles or pose_refinement or quad_sigma or max_width or max_height or rectify or resize:
                 raise ValueError("rigid_bundles is served alone by this view: not with bundles, pose_refinement, quad_sigma, max_width / "
@@ -353,6 +385,13 @@ class AprilTagMultiCameraNode:
         out = (ShellRigidBundlePose * max_out)()
         return _unpack_rigid_bundle_poses(out, min(self._L.node_shell_multi_last_rigid_bundle_poses(self._h, stream, out, max_out), max_out))
 
+    def covariances(self, stream):
+        """detection.pose.pose.covariance of the last message published for `stream`: one 6 x 6 array per detection."""
+        return _covariances(lambda out, n: self._L.node_shell_multi_last_covariances(self._h, stream, out, n), self.max_tags)
+
+    def rigid_bundle_covariances(self, stream, max_out=8):
+        return _covariances(lambda out, n: self._L.node_shell_multi_last_rigid_covariances(self._h, stream, out, n), max_out)
+
     def flush(self):
         return self._L.node_shell_multi_flush(self._h)
 
@@ -373,7 +412,7 @@ class AprilTagNode:
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
                  strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None, pose_refinement=0,
-                 rigid_bundles=None):
+                 rigid_bundles=None, pose_covariance=0.0):
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
         (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
@@ -384,11 +423,22 @@ class AprilTagNode:
         pose_refinement (NodeOptions::pose_refinement, alone among the extensions): iterations of the orthogonal-iteration pose -- the
         detections' poses and the tags' transforms are the chosen refined pose.  rigid_bundles (NodeOptions::rigid_bundles, alone among
         the extensions): [{"name", "iterations", "members": [(id, (x, y, z), (qw, qx, qy, qz), size)], ...}] -- one "bundle:<name>"
-        transform per solved rigid bundle, from the chosen pose."""
+        transform per solved rigid bundle, from the chosen pose.  pose_covariance (NodeOptions::pose_covariance_sigma_px, with
+        pose_refinement and / or rigid_bundles): the corner noise in pixels -- covariances() and rigid_bundle_covariances() hand out
+        what the node published."""
         rw, rh = (int(resize[0]), int(resize[1])) if resize else (0, 0)
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags = max_tags
+        if pose_covariance:
+            if bundles or quad_sigma or rectify or resize or strict_cuapriltags_encodings or not (pose_refinement or rigid_bundles):
+                raise ValueError("pose_covariance is served with pose_refinement and / or rigid_bundles by this view, and with nothing else")
+            arr = _shell_rigid_bundles(rigid_bundles or [])
+            self._h = self._L.node_shell_create_covariance(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                           int(pose_refinement), len(arr), arr, float(pose_covariance), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if rigid_bundles:
             if bundles or pose_refinement or quad_sigma or rectify or resize or strict_cuapriltags_encodings:
                 raise ValueError("rigid_bundles is served alone by this view: not with bundles, pose_refinement, quad_sigma, rectify, resize "
@@ -445,6 +495,13 @@ class AprilTagNode:
     def rigid_bundle_poses(self, max_out=8):
         out = (ShellRigidBundlePose * max_out)()
         return _unpack_rigid_bundle_poses(out, min(self._L.node_shell_last_rigid_bundle_poses(self._h, out, max_out), max_out))
+
+    def covariances(self):
+        """detection.pose.pose.covariance of the last published message: one 6 x 6 array per detection."""
+        return _covariances(lambda out, n: self._L.node_shell_last_covariances(self._h, out, n), self.max_tags)
+
+    def rigid_bundle_covariances(self, max_out=8):
+        return _covariances(lambda out, n: self._L.node_shell_last_rigid_covariances(self._h, out, n), max_out)
 
     def on_frame(self, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0),
                  info_stamp=None, D=None, distortion_model=None, P12=None, R=None):

@@ -99,6 +99,10 @@ public:
     // the orthogonal-iteration tag pose with both minima (AprilRobotics' estimate_tag_pose) inside the detector's submission: this many
     // iterations per chain (50 upstream); the published poses and transforms are then the chosen refined pose.  0: off
     opt.pose_refinement = static_cast<uint32_t>(declare_parameter<int>("pose_refinement_iterations", 0));
+    // pose covariance: the standard deviation, in pixels, of the independent error the caller ascribes to every corner coordinate.  With
+    // pose_refinement_iterations > 0 the published pose.pose.covariance is then the first-order covariance of the chosen pose (x, y, z,
+    // rotation about x, y, z in the camera optical frame), zeros where it could not be formed.  0: off, covariance all zero
+    opt.pose_covariance_sigma_px = declare_parameter<double>("pose_covariance_sigma_px", 0.0);
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);
@@ -124,6 +128,7 @@ public:
           m.pose.pose.pose.orientation.y = d.pose.pose.pose.orientation.y;
           m.pose.pose.pose.orientation.z = d.pose.pose.pose.orientation.z;
           m.pose.pose.pose.orientation.w = d.pose.pose.pose.orientation.w;
+          for (size_t i = 0; i < 36; i++) {m.pose.pose.covariance[i] = d.pose.pose.covariance[i];}
           msg.detections.push_back(m);
         }
         detections_pub_->publish(msg);
