@@ -406,7 +406,10 @@ typedef struct { uint32_t bundle, status, ntags, nskipped; double R[9]; double t
  * handle's list, an id outside the family's codes, a (family_index, id) named twice (within or across bundles), a non-finite or
  * non-positive size, a non-finite coordinate, min_tags = 0, a name without terminator, a submission in flight; AMDAT_OUT_OF_MEMORY: the
  * device buffers could not be allocated.  A refused call leaves the previous setting in force.  Turning the mode on or off retires the
- * handle's captured launch graphs, against the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the layout does not. */
+ * handle's captured launch graphs, against the same budget of 24 as amdAprilTagsSetQuadSigma; changing only the layout does not.
+ * A bundle's max_hamming above 2147483646 (INT32_MAX - 1) is taken as that value, here and in amdAprilTagsSetBundlesEx: no decoded
+ * record has a hamming above 3, and INT32_MAX itself is the mark of an invalid undistorted record (amdAprilTagsSetCornerUndistortion),
+ * which no gate may pass. */
 int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundle_t* bundles);
 /* The bundle records of the last completed submission: nframes x nbundles, frame-major (out[f * nbundles + b]).
  * AMDAT_INVALID_ARGUMENT: null handle or out, bundles off, nframes beyond the last submission's, a submission in flight. */
@@ -531,6 +534,47 @@ int amdAprilTagsGetRefinedPoseCovariances(amdAprilTagsHandle handle, uint32_t fr
 /* The covariance records beside amdAprilTagsGetBundlePosesEx' records: same shape, same refusals, and refused where the last
  * submission did not run both modes. */
 int amdAprilTagsGetBundlePoseCovariancesEx(amdAprilTagsHandle handle, amdAprilTagsPoseCovariance_t* out, uint32_t nframes);
+
+/* Raw-frame mode: detect on the distorted frame as it comes from the camera and undistort the detected corners, not the pixels --
+ * what a calibration or SLAM pipeline does with cv::undistortPoints.  Off by default; while it is off no record changes by a bit.
+ * With the mode on, every following submission runs one small launch behind the last detector stage: every record the frame keeps
+ * gets an undistorted twin under cams[i % ncams] for frame i.  Its corners are p_u[k] = undistort(p[k]) -- the raw pixel through
+ * K^-1, the inverse of the kind's distortion by AMDAT_UNDISTORT_ITERATIONS Newton steps (no early exit), the rotation R and Knew; the
+ * inverse, operation for operation, of the projection amdAprilTagsSetRectificationEx states.  Its H is the exact four-point homography
+ * from the tag's corners c_k onto p_u[k], its c is H(0, 0), and its R, t are the homography pose under the frame's intrinsics and skew
+ * and the handle's tag_size.  DESIGN.md section 7h has every operation (csrc/undistort.h states the point map once for device and
+ * host; tests/undistort_ref.py in numpy).  FP64 throughout.
+ * The records live in the coordinates a rectified image would have: pass Knew's fx, fy, cx, cy as the pose intrinsics, exactly as with
+ * amdAprilTagsSetRectificationEx; with R set the pose is in the rectified camera's frame.  The model describes the DETECTED image: with
+ * amdAprilTagsSetResize or a window of amdAprilTagsSetPerFrameSizes the caller scales or shifts K, as they do with the intrinsics.
+ * amdAprilTagsID_t and amdAprilTagsDetectionEx_t keep the raw frame's values whether the mode is on or off; the bundle launches
+ * (amdAprilTagsSetBundles, amdAprilTagsSetBundlesEx) and the refinement launch (amdAprilTagsSetPoseRefinement, with
+ * amdAprilTagsSetPoseCovariance) read the undistorted twins in the raw records' place, so their poses are those of the ideal camera.
+ * A record is AMDAT_UNDISTORT_INVALID where a corner does not come back to its pixel within 2^-20 px when pushed forward again (a
+ * polynomial that folds over, a fisheye radius beyond the model's range), where a corner's ray points away from the rectified camera
+ * (W <= 0), where a value is not finite, or where H is singular.  All geometric fields of such a record are zero; no bundle uses it
+ * (it counts in nskipped, as a record that fails a gate), its refined pose is AMDAT_POSE_DEGENERATE with all other fields zero and
+ * its covariance record is all zero with valid = 0.
+ * Not covered: the detector itself is not distortion-aware (a strongly curved tag edge still meets a straight-line fit), the thin-prism
+ * and tilted-sensor terms, and a skew in K or Knew (K[1], Knew[1] are not read). */
+#define AMDAT_UNDISTORT_OK 0u
+#define AMDAT_UNDISTORT_INVALID 1u
+#define AMDAT_UNDISTORT_ITERATIONS 20
+typedef struct {
+  uint32_t status, reserved;
+  double H[9], c[2], p[4][2], R[9], t[3];
+} amdAprilTagsUndistortedDetection_t;
+/* ncams = 0 turns the mode off.  The models are host state of the handle and travel to the device with each submission's descriptors:
+ * no device synchronisation, a front end may call it before every flush.  The first call that turns the mode on allocates the twin
+ * record list and the pinned record block.  Applies to every submitting call, on both launch sets.  Validation and refusals are those
+ * of amdAprilTagsSetRectificationEx, and in addition: AMDAT_INVALID_ARGUMENT while rectification is on (a frame is either resampled or
+ * read raw); amdAprilTagsSetRectification[Ex] with ncams > 0 is refused while this mode is on.  A refused call
+ * leaves the previous setting in force.  Turning the mode on or off retires the handle's captured launch graphs, against the same
+ * budget of 24 as amdAprilTagsSetQuadSigma; changing only the models does not. */
+int amdAprilTagsSetCornerUndistortion(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams);
+/* The undistorted records of frame `frame` of the last completed submission: out[i] belongs to the i-th detection handed out for that
+ * frame; their number through *n.  The shape and the refusals of amdAprilTagsGetRefinedPoses. */
+int amdAprilTagsGetUndistortedDetections(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsUndistortedDetection_t* out, uint32_t capacity, uint32_t* n);
 
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);

@@ -92,6 +92,15 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
  * (amdAprilTagsDebugCopy and the getters refuse until the next submission); the handle itself stays usable. */
 int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
                                amdAprilTagsDetectionEx_t* records_out, uint32_t capacity, uint32_t* nout);
+/* k_undistort_records alone on records the caller chooses (amdAprilTagsSetCornerUndistortion's stage; the mode itself may be off): n <=
+ * max_detections records go into batch slot 0's list as its kept records, in the order given, under the camera `cam` (validated as by
+ * the setter); the kernel runs on the handle's own stream with the handle's intrinsics, skew and tag size, and the call waits.  Both
+ * outputs come back, n each: `out` the public records, `twins_out` the twins as the pose launches read them from device memory
+ * (hamming INT32_MAX where invalid); either may be null.  The last submission's buffers cannot be inspected afterwards, as with
+ * amdAprilTagsDebugReconcile. */
+int amdAprilTagsDebugUndistort(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
+                               const amdAprilTagsCameraModelEx_t* cam, amdAprilTagsUndistortedDetection_t* out,
+                               amdAprilTagsDetectionEx_t* twins_out);
 /* Device-arithmetic self check: op 0 = sqrt(f64), 1 = a/b (f64), 2 = sqrtf(f32 bits in low word),
  * 3 = a/b (f32), 4 = a/b (f64) through the shared-reciprocal sequence the line fit uses, 5 = square root of the
  * integer a < 2^18 through the line-fit weights' f32-seeded sequence, 6 = atan_s(a), the arctangent of the equidistant camera model

@@ -161,6 +161,15 @@ struct NodeOptions {
   // distortion models, and the rectification rotation r of a stereo head.  Turns rectification on by itself; with it off `rectify`
   // takes plumb_bob alone and ignores r, as it always has.  The pose is reported in the rectified camera's frame.
   bool rectify_full = false;
+  // Extension: raw-frame mode (amdAprilTagsSetCornerUndistortion), in place of `rectify` / `rectify_full` (both kinds set is an error):
+  // the frames are detected as the camera delivers them and the corners of the detections are undistorted, not the pixels.  The model is
+  // RectificationModelEx of the stream's CameraInfo, taken and set as `rectify_full` takes and sets it (with resize_width x resize_height
+  // its K and Knew are scaled to the resized image, which is the one detected), and the pose is computed with Knew.  The detections'
+  // corners and centre stay the raw frame's; their poses, the "family:id" transforms, the bundle transforms, the refined poses and the
+  // covariances are those of the undistorted corners.  A detection whose corners cannot be undistorted (AMDAT_UNDISTORT_INVALID) is
+  // published with a zero translation and the identity orientation -- with pose_refinement on as well: the refined record of such a
+  // detection (AMDAT_POSE_DEGENERATE, all zero) is not taken.
+  bool undistort_corners = false;
   // Extension: every frame is resized to resize_width x resize_height INSIDE the detector's submission, behind the rectification where
   // `rectify` is set (amdAprilTagsSetResize; the reference puts a ResizeNode in front and recommends it for 4K input, README.md:16-29).
   // Both set: AprilTagNode creates its handle at that size, AprilTagMultiCameraNode at that size too (or at max_width x max_height with

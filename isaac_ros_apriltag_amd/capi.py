@@ -118,6 +118,20 @@ POSE_COV_DTYPE = np.dtype([("cov", "<f8", (6, 6)), ("cov_alt", "<f8", (6, 6)), (
 assert POSE_COV_DTYPE.itemsize == C.sizeof(PoseCovariance)
 
 
+class UndistortedDetection(C.Structure):
+    """amdAprilTagsUndistortedDetection_t."""
+    _fields_ = [("status", C.c_uint32), ("reserved", C.c_uint32), ("H", C.c_double * 9), ("c", C.c_double * 2), ("p", (C.c_double * 2) * 4),
+                ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+# the same record as a numpy dtype (detector.debug_undistort)
+UNDISTORTED_DTYPE = np.dtype([("status", "<u4"), ("reserved", "<u4"), ("H", "<f8", (9,)), ("c", "<f8", (2,)), ("p", "<f8", (4, 2)),
+                              ("R", "<f8", (9,)), ("t", "<f8", (3,))])
+assert UNDISTORTED_DTYPE.itemsize == C.sizeof(UndistortedDetection)
+UNDISTORT_OK, UNDISTORT_INVALID = 0, 1
+UNDISTORT_ITERATIONS = 20
+
+
 class Float2(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float)]
 
@@ -166,7 +180,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetRectificationEx", "amdAprilTagsRectifyMono8Ex", "amdAprilTagsSetBundles", "amdAprilTagsGetBundlePoses",
            "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses",
            "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx", "amdAprilTagsDebugReconcile",
-           "amdAprilTagsSetPoseCovariance", "amdAprilTagsGetRefinedPoseCovariances", "amdAprilTagsGetBundlePoseCovariancesEx"]
+           "amdAprilTagsSetPoseCovariance", "amdAprilTagsGetRefinedPoseCovariances", "amdAprilTagsGetBundlePoseCovariancesEx",
+           "amdAprilTagsSetCornerUndistortion", "amdAprilTagsGetUndistortedDetections", "amdAprilTagsDebugUndistort"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -260,6 +275,9 @@ def lib():
     L.amdAprilTagsGetRefinedPoseCovariances.argtypes = [H, C.c_uint32, C.POINTER(PoseCovariance), C.c_uint32, C.POINTER(C.c_uint32)]
     L.amdAprilTagsGetBundlePoseCovariancesEx.argtypes = [H, C.POINTER(PoseCovariance), C.c_uint32]
     L.amdAprilTagsDebugReconcile.argtypes = [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.amdAprilTagsSetCornerUndistortion.argtypes = [H, C.c_uint32, C.POINTER(CameraModelEx)]
+    L.amdAprilTagsGetUndistortedDetections.argtypes = [H, C.c_uint32, C.POINTER(UndistortedDetection), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.amdAprilTagsDebugUndistort.argtypes = [H, C.c_uint32, C.c_void_p, C.POINTER(CameraModelEx), C.c_void_p, C.c_void_p]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)

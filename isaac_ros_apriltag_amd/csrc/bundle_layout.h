@@ -99,7 +99,7 @@ inline int bundle_layout_build(uint32_t nfam, const uint32_t* fam_ncodes, uint32
     BundleDev& d = out->head.b[b];
     d.mx = mx; d.my = my; d.sc = sc;
     d.min_decision_margin = B.min_decision_margin;
-    d.max_hamming = B.max_hamming > 0x7FFFFFFFu ? 0x7FFFFFFF : (int32_t)B.max_hamming;
+    d.max_hamming = B.max_hamming > 0x7FFFFFFEu ? 0x7FFFFFFE : (int32_t)B.max_hamming;   // (below INT32_MAX, the hamming of an invalid undistorted record: DESIGN.md section 7h)
     d.min_tags = B.min_tags;
     d.nmembers = B.nmembers;
   }

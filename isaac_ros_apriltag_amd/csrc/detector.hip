@@ -32,6 +32,7 @@
 #include "kernels_quad.h"
 #include "kernels_quad_small.h"
 #include "kernels_threshold.h"
+#include "kernels_undistort.h"
 #include "launch_plan.h"
 
 static_assert(sizeof(DetRec) == sizeof(amdAprilTagsDetectionEx_t), "DetRec must match the public record");
@@ -306,6 +307,16 @@ struct amdAprilTagsDetector_st {
   DevBuf<double> d_cov_cfg;
   HostBuf<PoseCovRec> h_rcovs;                          // pinned, max_batch x dcap, beside h_rposes
   HostBuf<PoseCovRec> h_xcovs;                          // pinned, max_batch x AMDAT_MAX_BUNDLES, beside h_xposes
+  // amdAprilTagsSetCornerUndistortion: k_undistort_records runs behind k_reconcile while undist_models is not empty, and the bundle,
+  // rigid and refinement launches then read d_dets_u in d_dets' place.  Frame i of a submission takes undist_models[i % size]; the
+  // slot's camera travels through the pinned block h_ucams, which k_prologue uploads with the frame descriptors.  All four buffers are
+  // allocated by the first call that turns the mode on
+  std::vector<amdAprilTagsCameraModelEx_t> undist_models;   // empty: off
+  bool last_undistorted = false;                        // the last submission ran the mode (amdAprilTagsGetUndistortedDetections)
+  HostBuf<UndistortCam> h_ucams;                        // pinned, one per batch slot
+  DevBuf<UndistortCam> d_ucams;
+  DevBuf<DetRec> d_dets_u;                              // max_batch x dcap, laid out and indexed as d_dets
+  HostBuf<UndistortRec> h_udets;                        // pinned, max_batch x dcap: frame * ostride + record, as k_reconcile writes h_out
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1015,6 +1026,7 @@ int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, cons
 
 int amdAprilTagsSetRectificationEx(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams) {
   if (!handle || handle->inflight.active || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  if (ncams && !handle->undist_models.empty()) return AMDAT_INVALID_ARGUMENT;   // (raw-frame mode is on: a frame is resampled or read raw, not both)
   bool general = false;
   for (uint32_t c = 0; c < ncams; c++) {
     if (!camera_model_ok(cams[c])) return AMDAT_INVALID_ARGUMENT;
@@ -1132,6 +1144,59 @@ int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePo
   return AMDAT_SUCCESS;
 }
 
+// The kernel's parameters of a camera model (undistort.h): K, D, R and Knew as they are given.
+static UndistortCam undistort_cam(const amdAprilTagsCameraModelEx_t& m) {
+  UndistortCam c = {};
+  c.kind = m.kind;
+  c.fx = m.K[0]; c.fy = m.K[4]; c.cx = m.K[2]; c.cy = m.K[5];
+  for (int j = 0; j < 8; j++) c.d[j] = m.D[j];
+  for (int j = 0; j < 9; j++) c.R[j] = m.R[j];
+  c.nfx = m.Knew[0]; c.nfy = m.Knew[4]; c.ncx = m.Knew[2]; c.ncy = m.Knew[5];
+  return c;
+}
+
+// What the first call that turns the corner undistortion on (or amdAprilTagsDebugUndistort) allocates.
+static int ensure_undistort_buffers(amdAprilTagsDetector_st* D) {
+  const size_t B = D->cfg.max_batch;
+  static_assert(sizeof(UndistortCam) % 4 == 0, "k_prologue copies words");
+  if (!D->h_ucams && !host_alloc(D, D->h_ucams, B * sizeof(UndistortCam))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->d_ucams && !dev_alloc(D, D->d_ucams, B * sizeof(UndistortCam))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->d_dets_u && !dev_alloc(D, D->d_dets_u, B * (size_t)D->P.dcap * sizeof(DetRec))) return AMDAT_OUT_OF_MEMORY;
+  if (!D->h_udets && !host_alloc(D, D->h_udets, B * (size_t)D->P.dcap * sizeof(UndistortRec))) return AMDAT_OUT_OF_MEMORY;
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetCornerUndistortion(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams) {
+  if (!handle || handle->inflight.active || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  if (ncams && !handle->rect_models.empty()) return AMDAT_INVALID_ARGUMENT;   // (rectification is on: a frame is resampled or read raw, not both)
+  for (uint32_t c = 0; c < ncams; c++)
+    if (!camera_model_ok(cams[c])) return AMDAT_INVALID_ARGUMENT;
+  const bool on = ncams > 0;
+  if (on != !handle->undist_models.empty()) {
+    DeviceGuard guard(handle->device);
+    if (!guard.ok) return AMDAT_HIP_ERROR;
+    if (on) { const int rc = ensure_undistort_buffers(handle); if (rc) return rc; }
+    drop_graphs(handle);   // captured with or without the launch, and with the pose launches on the one or the other record list; the models travel through the descriptors
+  }
+  handle->undist_models.assign(cams, cams + ncams);
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsGetUndistortedDetections(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsUndistortedDetection_t* out, uint32_t capacity, uint32_t* n) {
+  if (!handle || !out || !n || handle->inflight.active || !handle->last_undistorted || frame >= handle->last_n) return AMDAT_INVALID_ARGUMENT;
+  uint32_t k = handle->h_counters[frame].nout;
+  if (k > handle->last_ostride) k = handle->last_ostride;
+  *n = k;
+  if (capacity < k) return AMDAT_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < k; i++) out[i] = handle->h_udets[(size_t)frame * handle->last_ostride + i].det;
+  return AMDAT_SUCCESS;
+}
+
+// Record i of `frame` of the last submission was refined from an invalid undistorted twin.
+static bool undistorted_invalid(const amdAprilTagsDetector_st* D, uint32_t frame, uint32_t i) {
+  return D->last_undistorted && D->h_udets[(size_t)frame * D->last_ostride + i].det.status != AMDAT_UNDISTORT_OK;
+}
+
 int amdAprilTagsSetPoseRefinement(amdAprilTagsHandle handle, uint32_t iterations) {
   if (!handle || iterations > AMDAT_MAX_POSE_ITERATIONS || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   static_assert(AMDAT_MAX_POSE_ITERATIONS == PR_MAX_ITERATIONS, "the header's bound is the kernel's");
@@ -1158,7 +1223,10 @@ int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAp
   if (k > handle->last_ostride) k = handle->last_ostride;
   *n = k;
   if (capacity < k) return AMDAT_INVALID_ARGUMENT;
-  for (uint32_t i = 0; i < k; i++) out[i] = handle->h_rposes[(size_t)frame * handle->last_ostride + i].pose;
+  for (uint32_t i = 0; i < k; i++) {
+    out[i] = handle->h_rposes[(size_t)frame * handle->last_ostride + i].pose;
+    if (undistorted_invalid(handle, frame, i)) { out[i] = {}; out[i].status = AMDAT_POSE_DEGENERATE; }   // (section 7h: nothing of an invalid twin is handed out)
+  }
   return AMDAT_SUCCESS;
 }
 
@@ -1191,7 +1259,10 @@ int amdAprilTagsGetRefinedPoseCovariances(amdAprilTagsHandle handle, uint32_t fr
   if (k > handle->last_ostride) k = handle->last_ostride;
   *n = k;
   if (capacity < k) return AMDAT_INVALID_ARGUMENT;
-  for (uint32_t i = 0; i < k; i++) out[i] = handle->h_rcovs[(size_t)frame * handle->last_ostride + i].c;
+  for (uint32_t i = 0; i < k; i++) {
+    out[i] = handle->h_rcovs[(size_t)frame * handle->last_ostride + i].c;
+    if (undistorted_invalid(handle, frame, i)) out[i] = {};   // (section 7h: all zero, valid = 0)
+  }
   return AMDAT_SUCCESS;
 }
 
@@ -1435,10 +1506,12 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
 // and frame counters to zero (one block per frame)
 __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ host_frames, uint32_t* __restrict__ frames,
                                                  uint32_t* __restrict__ workctl, uint32_t* __restrict__ counters, int fd_words, int fc_words,
-                                                 const uint32_t* __restrict__ host_front, uint32_t* __restrict__ front, int front_words) {
+                                                 const uint32_t* __restrict__ host_front, uint32_t* __restrict__ front, int front_words,
+                                                 const uint32_t* __restrict__ host_ucams, uint32_t* __restrict__ ucams, int ucam_words) {
   const int frame = (int)blockIdx.x, t = (int)threadIdx.x;
   for (int i = t; i < fd_words; i += 64) frames[frame * fd_words + i] = host_frames[frame * fd_words + i];
   for (int i = t; i < front_words; i += 64) front[frame * front_words + i] = host_front[frame * front_words + i];   // (no front stage: no words)
+  for (int i = t; i < ucam_words; i += 64) ucams[frame * ucam_words + i] = host_ucams[frame * ucam_words + i];   // (no corner undistortion: no words)
   for (int i = t; i < fc_words; i += 64) counters[frame * fc_words + i] = 0u;
   if (frame == 0 && t < 32) workctl[t] = 0u;
 }
@@ -1547,21 +1620,28 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   mark();
   hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
                      D->h_counters, P);
+  // S9b: raw-frame mode -- the undistorted twin of every kept record (kernels_undistort.h); the three launches below then read the
+  // twins, which order and count as the raw records do
+  const bool undist = !D->undist_models.empty();
+  if (undist)
+    hipLaunchKernelGGL(k_undistort_records, dim3(n, UD_WAVES_PER_FRAME), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+                       D->d_ucams, D->d_dets_u, D->h_udets, ostride, P);
+  const DetRec* const pose_dets = undist ? UD_POSE_RECORDS(D->d_dets, D->d_dets_u) : D->d_dets;   // (tools_hooks.h: d_dets_u in the product build)
   if (D->nbundles)   // S10: one wave per (frame, bundle) on the kept records, straight behind k_reconcile (kernels_bundle.h)
-    hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+    hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order,
                        D->d_bundle_head, D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
   // (amdAprilTagsSetPoseCovariance: the covariance instance of whichever of the two launches below runs; off, the launches as they were)
   const bool cov = D->pose_cov_sigma > 0.0;
   if (D->nrigid)   // S12: two waves per (frame, bundle), one chain each, in the planar kind's place (kernels_rigid.h)
 #define RIGID_LAUNCH(COV)                                                                                                           \
-  hipLaunchKernelGGL(k_bundle_rigid<COV>, dim3(n, AMDAT_MAX_BUNDLES), dim3(128), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, \
+  hipLaunchKernelGGL(k_bundle_rigid<COV>, dim3(n, AMDAT_MAX_BUNDLES), dim3(128), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, \
                      D->d_rigid_head, D->d_rigid_members, D->d_rigid_table, D->h_xposes, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_xcovs)
   {
     if (cov) RIGID_LAUNCH(true); else RIGID_LAUNCH(false);
   }
 #undef RIGID_LAUNCH
 #define POSE_LAUNCH(COV)                                                                                                            \
-  hipLaunchKernelGGL(k_pose_refine<COV>, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, \
+  hipLaunchKernelGGL(k_pose_refine<COV>, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, \
                      D->d_order, D->d_pose_cfg, D->h_rposes, ostride, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_rcovs)
   if (D->pose_iterations) {   // S11: both minima of the records handed out, eight lanes per record, beside the bundles (kernels_pose.h)
     if (cov) POSE_LAUNCH(true); else POSE_LAUNCH(false);
@@ -1584,7 +1664,9 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
                      static_cast<uint32_t*>(D->d_frames.p), D->d_workctl, reinterpret_cast<uint32_t*>(D->d_counters),
                      (int)(sizeof(FrameDesc) / 4), (int)(sizeof(FrameCounters) / 4),
                      static_cast<const uint32_t*>(D->h_front.p), static_cast<uint32_t*>(D->d_front.p),
-                     resize || rect ? (int)(sizeof(FrontDesc) / 4) : 0);
+                     resize || rect ? (int)(sizeof(FrontDesc) / 4) : 0,
+                     static_cast<const uint32_t*>(D->h_ucams.p), static_cast<uint32_t*>(D->d_ucams.p),
+                     D->undist_models.empty() ? 0 : (int)(sizeof(UndistortCam) / 4));
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
@@ -1767,6 +1849,14 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
         for (uint32_t i = 0; i < k; i++)
           if (static_cast<volatile PoseRefineRec*>(D->h_rposes)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
       }
+    // corner undistortion on: k_undistort_records stamps every record it hands out
+    if (!D->undist_models.empty())
+      for (uint32_t f = 0; f < D->launched_n; f++) {
+        uint32_t k = D->h_counters[f].nout;
+        if (k > D->last_ostride) k = D->last_ostride;
+        for (uint32_t i = 0; i < k; i++)
+          if (static_cast<volatile UndistortRec*>(D->h_udets)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
+      }
     // pose covariance on: the covariance records beside both kinds carry the stamp as well
     if (D->pose_cov_sigma > 0.0) {
       for (uint32_t r = 0; r < D->launched_n * D->nrigid; r++)
@@ -1875,6 +1965,11 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   D->last_pose_refined = D->pose_iterations > 0;
   D->last_pose_cov = D->pose_cov_sigma > 0.0;
   D->last_ostride = ostride;
+  D->last_undistorted = !D->undist_models.empty();
+  if (D->last_undistorted) {   // each slot's camera, beside the frame descriptors (the model describes the detected image)
+    const uint32_t ncams = (uint32_t)D->undist_models.size();
+    for (uint32_t i = 0; i < n; i++) D->h_ucams[i] = undistort_cam(D->undist_models[UD_MODEL_OF_SLOT(i, ncams)]);   // (tools_hooks.h: i % ncams)
+  }
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
     D->pending_hash_grow = false;
     const GrowPlan g = plan_pending_hash(caps_of(D), D->grow);
@@ -2085,6 +2180,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   handle->last_nrigid = 0;
   handle->last_pose_refined = false;   // (never refines poses)
   handle->last_pose_cov = false;
+  handle->last_undistorted = false;   // (never undistorts corners)
   handle->last_rectified = false;   // (never rectifies)
   handle->last_resized = false;     // (never resizes)
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));
@@ -2300,6 +2396,7 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
   const hipStream_t s = D->own_stream;
   HIP_TRY(hipDeviceSynchronize());
   D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_pose_cov = false; D->last_rectified = false; D->last_resized = false;
+  D->last_undistorted = false;
   FrameDesc fd;
   memset(&fd, 0, sizeof(fd));
   fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;
@@ -2326,6 +2423,57 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
   *nout = nk;
   const uint32_t k = nk < capacity ? nk : capacity;
   if (k) memcpy(records_out, D->h_out, (size_t)k * sizeof(DetRec));
+  return AMDAT_SUCCESS;
+}
+
+// k_undistort_records alone, on records the caller chooses: they become batch slot 0's kept records in the order given (the order list
+// is the identity), under `cam`; the slot's descriptor carries the handle's intrinsics and a fresh sequence number.
+int amdAprilTagsDebugUndistort(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
+                               const amdAprilTagsCameraModelEx_t* cam, amdAprilTagsUndistortedDetection_t* out,
+                               amdAprilTagsDetectionEx_t* twins_out) {
+  if (!handle || !cam || handle->inflight.active || (n && !records_in) || !camera_model_ok(*cam)) return AMDAT_INVALID_ARGUMENT;
+  if (n > handle->P.dcap) return AMDAT_INVALID_ARGUMENT;
+  if (handle->unusable) return AMDAT_OUT_OF_MEMORY;
+  amdAprilTagsDetector_st* D = handle;
+  DeviceGuard guard(D->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  { const int rc = ensure_undistort_buffers(D); if (rc) return rc; }
+  const hipStream_t s = D->own_stream;
+  HIP_TRY(hipDeviceSynchronize());
+  D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_pose_cov = false; D->last_rectified = false; D->last_resized = false;
+  D->last_undistorted = false;
+  FrameDesc fd;
+  memset(&fd, 0, sizeof(fd));
+  fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;
+  fd.cx = (double)D->cfg.intrinsics.cx; fd.cy = (double)D->cfg.intrinsics.cy;
+  fd.skew = (double)(D->frame_skew.empty() ? D->cfg.skew : D->frame_skew[0]);
+  fd.seq = ++D->seq;
+  FrameCounters fc;
+  memset(&fc, 0, sizeof(fc));
+  fc.ndets = n; fc.nout = n;
+  const UndistortCam uc = undistort_cam(*cam);
+  std::vector<uint16_t> ident(n);
+  for (uint32_t i = 0; i < n; i++) ident[i] = (uint16_t)i;
+  HIP_TRY(hipMemcpyAsync(D->d_frames, &fd, sizeof(fd), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(D->d_counters, &fc, sizeof(fc), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(D->d_ucams, &uc, sizeof(uc), hipMemcpyHostToDevice, s));
+  if (n) {
+    HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(D->d_order, ident.data(), (size_t)n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+  }
+  DetParams P = D->P;
+  P.frame0 = 0;
+  hipLaunchKernelGGL(k_undistort_records, dim3(1, UD_WAVES_PER_FRAME), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+                     D->d_ucams, D->d_dets_u, D->h_udets, P.dcap, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));   // (the pageable sources above are read before this returns)
+  for (uint32_t i = 0; i < n; i++)
+    if (static_cast<volatile UndistortRec*>(D->h_udets)[i].seq != fd.seq) {
+      HIP_TRY(hipDeviceSynchronize());
+      if (static_cast<volatile UndistortRec*>(D->h_udets)[i].seq != fd.seq) return AMDAT_HIP_ERROR;
+    }
+  if (out) for (uint32_t i = 0; i < n; i++) out[i] = D->h_udets[i].det;
+  if (twins_out && n) HIP_TRY(hipMemcpy(twins_out, D->d_dets_u, (size_t)n * sizeof(DetRec), hipMemcpyDeviceToHost));
   return AMDAT_SUCCESS;
 }
 

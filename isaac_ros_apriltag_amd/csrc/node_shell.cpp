@@ -56,6 +56,8 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetPoseCovariance) set_pose_covariance = nullptr;
   decltype(&amdAprilTagsGetRefinedPoseCovariances) get_refined_pose_covariances = nullptr;
   decltype(&amdAprilTagsGetBundlePoseCovariancesEx) get_bundle_pose_covariances_ex = nullptr;
+  decltype(&amdAprilTagsSetCornerUndistortion) set_corner_undistortion = nullptr;
+  decltype(&amdAprilTagsGetUndistortedDetections) get_undistorted_detections = nullptr;
 };
 
 DetectorApi& api() {
@@ -104,6 +106,8 @@ DetectorApi& api() {
   BIND(set_pose_covariance, "amdAprilTagsSetPoseCovariance")
   BIND(get_refined_pose_covariances, "amdAprilTagsGetRefinedPoseCovariances")
   BIND(get_bundle_pose_covariances_ex, "amdAprilTagsGetBundlePoseCovariancesEx")
+  BIND(set_corner_undistortion, "amdAprilTagsSetCornerUndistortion")
+  BIND(get_undistorted_detections, "amdAprilTagsGetUndistortedDetections")
 #undef BIND
   return a;
 }
@@ -136,11 +140,12 @@ amdAprilTagsCameraModelEx_t to_abi(const CameraModelEx& m) {
 }
 
 bool rectifying(const NodeOptions& opt) { return opt.rectify || opt.rectify_full; }
+bool undistorting(const NodeOptions& opt) { return opt.undistort_corners; }
 
 // The model of a stream's CameraInfo under the options: RectificationModelEx with rectify_full, otherwise RectificationModel (plumb_bob
 // alone, no rotation) in the same form.  Throws what they throw.
 CameraModelEx stream_model(const NodeOptions& opt, const CameraInfo& info) {
-  if (opt.rectify_full) return RectificationModelEx(info);
+  if (opt.rectify_full || opt.undistort_corners) return RectificationModelEx(info);
   const CameraModel m = RectificationModel(info);
   CameraModelEx e;
   e.k = m.k; e.knew = m.knew;
@@ -168,11 +173,37 @@ int apply_models(amdAprilTagsHandle detector, const NodeOptions& opt, const Came
 
 bool resizing(const NodeOptions& opt) { return opt.resize_width != 0 && opt.resize_height != 0; }
 
+// NodeOptions::undistort_corners: the stream's model as the library must see it -- the camera of the DETECTED image, so with
+// NodeOptions::resize_width x resize_height K and Knew scaled as pose_camera scales the pose's camera.
+CameraModelEx detected_model(const NodeOptions& opt, const CameraInfo& info) {
+  CameraModelEx m = stream_model(opt, info);
+  if (resizing(opt) && info.width != 0 && info.height != 0) {
+    for (int c = 0; c < 3; c++) {
+      m.k[c] = m.k[c] * static_cast<double>(opt.resize_width) / static_cast<double>(info.width);
+      m.k[3 + c] = m.k[3 + c] * static_cast<double>(opt.resize_height) / static_cast<double>(info.height);
+      m.knew[c] = m.knew[c] * static_cast<double>(opt.resize_width) / static_cast<double>(info.width);
+      m.knew[3 + c] = m.knew[3 + c] * static_cast<double>(opt.resize_height) / static_cast<double>(info.height);
+    }
+  }
+  return m;
+}
+
+// n such models to the handle
+int apply_corner_models(amdAprilTagsHandle detector, const CameraModelEx* models, uint32_t n) {
+  std::vector<amdAprilTagsCameraModelEx_t> abi(n);
+  for (uint32_t i = 0; i < n; i++) abi[i] = to_abi(models[i]);
+  return api().set_corner_undistortion(detector, n, abi.data());
+}
+
+void check_camera_options(const NodeOptions& opt) {
+  if (undistorting(opt) && rectifying(opt)) throw std::runtime_error("'undistort_corners' and 'rectify' exclude each other: a frame is resampled or read raw");
+}
+
 // The camera matrix the pose is computed with: Knew of the stream's model with NodeOptions::rectify, K otherwise -- and with
 // NodeOptions::resize_width x resize_height that camera scaled to the resized image (image_proc's convention: the first row times
 // resize_width / width, the second times resize_height / height).
 std::array<double, 9> pose_camera(const NodeOptions& opt, const CameraInfo& info) {
-  std::array<double, 9> k = rectifying(opt) ? stream_model(opt, info).knew : info.k;
+  std::array<double, 9> k = rectifying(opt) || undistorting(opt) ? stream_model(opt, info).knew : info.k;
   if (resizing(opt) && info.width != 0 && info.height != 0) {
     for (int c = 0; c < 3; c++) {
       k[c] = k[c] * static_cast<double>(opt.resize_width) / static_cast<double>(info.width);
@@ -266,8 +297,10 @@ void apply_pose_covariance(amdAprilTagsHandle detector, const NodeOptions& opt) 
 // forms them from the homography pose.  (The node runs the default corner convention: R as solved.)
 // NodeOptions::pose_covariance_sigma_px with it: covs[i] is the chosen pose's covariance, the 36 doubles as the library hands them
 // out (row-major in ROS' order), or zeros where the record's is not valid; off, covs stays empty.
+// invalid: the marks of undistort_tags (NodeOptions::undistort_corners).  A tag marked there keeps the pose that call gave it: its refined
+// record is AMDAT_POSE_DEGENERATE with zero fields, which is no pose (and its covariance record is not valid: zeros).
 bool refine_tags(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t frame, amdAprilTagsID_t* tags, uint32_t num_detections,
-                 std::vector<std::array<double, 36>>* covs) {
+                 std::vector<std::array<double, 36>>* covs, const std::vector<uint8_t>& invalid) {
   covs->clear();
   if (opt.pose_refinement == 0) return true;
   if (opt.pose_covariance_sigma_px != 0.0) {
@@ -282,9 +315,31 @@ bool refine_tags(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t f
   uint32_t n = 0;
   if (api().get_refined_poses(detector, frame, recs.data(), num_detections, &n) != 0 || n != num_detections) return false;
   for (uint32_t i = 0; i < n; i++) {
+    if (i < invalid.size() && invalid[i]) continue;
     for (int r = 0; r < 3; r++)
       for (int c = 0; c < 3; c++) tags[i].orientation[c * 3 + r] = static_cast<float>(recs[i].R[r * 3 + c]);
     for (int k = 0; k < 3; k++) tags[i].translation[k] = static_cast<float>(recs[i].t[k]);
+  }
+  return true;
+}
+
+// NodeOptions::undistort_corners: the pose of every tag of frame `frame` of the submission that just returned becomes its undistorted
+// twin's (amdAprilTagsGetUndistortedDetections: record i belongs to tag i), formed in float as the library forms a tag's from the
+// record's; an invalid twin gives a zero translation and the identity, and is marked in `invalid` (one entry per tag; empty with the
+// mode off).  Corners and centre stay the raw frame's.
+bool undistort_tags(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t frame, amdAprilTagsID_t* tags, uint32_t num_detections,
+                    std::vector<uint8_t>* invalid) {
+  invalid->clear();
+  if (!undistorting(opt)) return true;
+  std::vector<amdAprilTagsUndistortedDetection_t> recs(num_detections ? num_detections : 1u);
+  uint32_t n = 0;
+  if (api().get_undistorted_detections(detector, frame, recs.data(), num_detections, &n) != 0 || n != num_detections) return false;
+  for (uint32_t i = 0; i < n; i++) {
+    const bool ok = recs[i].status == AMDAT_UNDISTORT_OK;
+    invalid->push_back(ok ? 0 : 1);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) tags[i].orientation[c * 3 + r] = ok ? static_cast<float>(recs[i].R[r * 3 + c]) : (r == c ? 1.0f : 0.0f);
+    for (int k = 0; k < 3; k++) tags[i].translation[k] = ok ? static_cast<float>(recs[i].t[k]) : 0.0f;
   }
   return true;
 }
@@ -562,6 +617,7 @@ struct AprilTagNode::Impl {
 
   void Initialize(const Image& image, const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
+    check_camera_options(opt);
     if (detector) { api().destroy(detector); detector = nullptr; }   // left over from a failed attempt
     // intrinsics from K, double -> float as the reference does (src/apriltag_node.cpp:442-447)
     amdAprilTagsConfig_t cfg;
@@ -590,6 +646,11 @@ struct AprilTagNode::Impl {
       const CameraModelEx model = stream_model(opt, info);
       const int rerr = apply_models(detector, opt, &model, 1);
       if (rerr != 0) throw std::runtime_error("'rectify': camera model refused (error code " + std::to_string(rerr) + ")");
+    }
+    if (undistorting(opt)) {
+      const CameraModelEx model = detected_model(opt, info);
+      const int rerr = apply_corner_models(detector, &model, 1);
+      if (rerr != 0) throw std::runtime_error("'undistort_corners': camera model refused (error code " + std::to_string(rerr) + ")");
     }
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
@@ -662,8 +723,13 @@ struct AprilTagNode::Impl {
       std::fprintf(stderr, "[apriltag_node] Failed to run AprilTags detector (error code %d)\n", error);
       return;
     }
+    std::vector<uint8_t> invalid;
+    if (!undistort_tags(detector, opt, 0, tags.data(), num_detections, &invalid)) {
+      std::fprintf(stderr, "[apriltag_node] undistorted detections not available: frame dropped\n");
+      return;
+    }
     std::vector<std::array<double, 36>> covs;
-    if (!refine_tags(detector, opt, 0, tags.data(), num_detections, &covs)) {
+    if (!refine_tags(detector, opt, 0, tags.data(), num_detections, &covs, invalid)) {
       std::fprintf(stderr, "[apriltag_node] refined poses or their covariances not available: frame dropped\n");
       return;
     }
@@ -751,6 +817,7 @@ struct AprilTagMultiCameraNode::Impl {
 
   void Initialize(const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
+    check_camera_options(opt);
     // left over from an attempt that threw after the handle existed (e.g. the slot allocation failed)
     if (detector) { api().destroy(detector); detector = nullptr; }
     if (d_mono) { api().dev_free(d_mono); d_mono = nullptr; }
@@ -887,6 +954,7 @@ bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& 
     return false;  // ExactTime synchroniser would not fire
   CameraModelEx model;
   if (rectifying(impl_->opt)) model = stream_model(impl_->opt, camera_info);   // (throws before anything is staged)
+  if (undistorting(impl_->opt)) model = detected_model(impl_->opt, camera_info);
   if (!impl_->initialized) impl_->Initialize(camera_info);
   Impl::Slot& sl = impl_->slots[stream];
   // the slot's device image is about to be overwritten: a frame staged earlier and not yet submitted is gone either way,
@@ -942,6 +1010,16 @@ uint32_t AprilTagMultiCameraNode::Flush() {
       return 0;
     }
   }
+  if (undistorting(I.opt)) {   // raw-frame mode: the same, for the corner undistortion
+    std::vector<CameraModelEx> models(n);
+    for (uint32_t i = 0; i < n; i++) models[i] = I.slots[who[i]].model;
+    const int rerr = apply_corner_models(I.detector, models.data(), n);
+    if (rerr != 0) {
+      std::fprintf(stderr, "[apriltag_node] per-stream camera models refused (error code %d): round dropped\n", rerr);
+      for (uint32_t s : who) I.slots[s].pending = false;
+      return 0;
+    }
+  }
   const int error = api().detect_batch(I.detector, n, imgs.data(), intr.data(), tags.data(), counts.data(), max_tags, nullptr);
   for (uint32_t s : who) I.slots[s].pending = false;
   if (error != 0) {
@@ -954,8 +1032,13 @@ uint32_t AprilTagMultiCameraNode::Flush() {
   std::vector<const Header*> headers(n);
   std::vector<std::vector<TransformStamped>*> tf_ptrs(n);
   for (uint32_t i = 0; i < n; i++) {
+    std::vector<uint8_t> invalid;
+    if (!undistort_tags(I.detector, I.opt, i, tags.data() + static_cast<size_t>(i) * max_tags, counts[i], &invalid)) {
+      std::fprintf(stderr, "[apriltag_node] undistorted detections not available: round dropped\n");
+      return 0;
+    }
     std::vector<std::array<double, 36>> covs;
-    if (!refine_tags(I.detector, I.opt, i, tags.data() + static_cast<size_t>(i) * max_tags, counts[i], &covs)) {
+    if (!refine_tags(I.detector, I.opt, i, tags.data() + static_cast<size_t>(i) * max_tags, counts[i], &covs, invalid)) {
       std::fprintf(stderr, "[apriltag_node] refined poses or their covariances not available: round dropped\n");
       return 0;
     }
@@ -1023,10 +1106,11 @@ static void fill_camera_info_extras(CameraInfo* info, const double* d, int nd, c
   if (r9) for (int i = 0; i < 9; i++) info->r[i] = r9[i];
 }
 
-// the flat value of `rectify`: 0 off, 1 NodeOptions::rectify, 2 NodeOptions::rectify_full
+// the flat value of `rectify`: 0 off, 1 NodeOptions::rectify, 2 NodeOptions::rectify_full, 3 NodeOptions::undistort_corners
 static void set_rectify_option(NodeOptions* o, int rectify) {
   o->rectify = rectify == 1;
   o->rectify_full = rectify == 2;
+  o->undistort_corners = rectify == 3;
 }
 
 // RectificationModelEx of a CameraInfo with these fields: out36 = kind, K[9], D[8], R[9], Knew[9].  0, or -2 with the exception's text.
@@ -1262,6 +1346,26 @@ NodeShellHarness* node_shell_create_refined(int max_tags, double size, int tile_
     return nullptr;
   }
 }
+// AprilTagNode with NodeOptions::undistort_corners beside pose_refinement (and pose_covariance_sigma_px; 0: off)
+NodeShellHarness* node_shell_create_undistort_refined(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                                      int decimate, uint32_t pose_refinement, double sigma_px, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    o.pose_covariance_sigma_px = sigma_px;
+    o.undistort_corners = true;
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
 // AprilTagNode with NodeOptions::pose_covariance_sigma_px beside pose_refinement and / or rigid_bundles (nbundles 0: none)
 NodeShellHarness* node_shell_create_covariance(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
                                                int decimate, uint32_t pose_refinement, int nbundles, const NodeShellRigidBundle* bundles,
@@ -1463,6 +1567,28 @@ MultiShellHarness* node_shell_multi_create_rigid_bundles(int num_streams, int ma
 }
 int node_shell_multi_last_rigid_bundle_poses(MultiShellHarness* h, int stream, NodeShellRigidBundlePose* out, int max_out) {
   return copy_rigid_bundle_poses(h->node->last_rigid_bundle_poses(static_cast<uint32_t>(stream)), out, max_out);
+}
+// AprilTagMultiCameraNode with NodeOptions::undistort_corners beside pose_refinement
+MultiShellHarness* node_shell_multi_create_undistort_refined(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                             const char* backends, int decimate, int auto_flush, uint32_t pose_refinement,
+                                                             char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    o.undistort_corners = true;
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
 }
 MultiShellHarness* node_shell_multi_create_refined(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
                                                    const char* backends, int decimate, int auto_flush, uint32_t pose_refinement,

@@ -114,7 +114,7 @@ inline int rigid_layout_build(uint32_t nfam, const uint32_t* fam_ncodes, uint32_
     }
     RigidBundleDev& d = out->head.b[b];
     d.min_decision_margin = B.min_decision_margin;
-    d.max_hamming = B.max_hamming > 0x7FFFFFFFu ? 0x7FFFFFFF : (int32_t)B.max_hamming;
+    d.max_hamming = B.max_hamming > 0x7FFFFFFEu ? 0x7FFFFFFE : (int32_t)B.max_hamming;   // (below INT32_MAX, the hamming of an invalid undistorted record: DESIGN.md section 7h)
     d.min_tags = B.min_tags;
     d.nmembers = B.nmembers;
     d.iterations = B.iterations;

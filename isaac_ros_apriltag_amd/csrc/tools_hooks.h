@@ -59,7 +59,11 @@
 //                               with skew
 //                           26 = the second quad of k_pose_refine<true> evaluates the covariance at chain 0's pose: cov_alt equals cov
 //                           27 = the covariance of a rigid bundle takes P - mean P for the object point P
-//                           (4 .. 27 change values only: no address, index bound, launch size or loop count)
+//                           28 = the corner undistortion (undistort.h) takes the identity for the rectification rotation R
+//                           29 = with amdAprilTagsSetCornerUndistortion on, the bundle and refinement launches still read the raw
+//                               records (d_dets, not d_dets_u: two live buffers of one size)
+//                           30 = amdAprilTagsSetCornerUndistortion: every frame of a submission takes cams[0] instead of cams[i % ncams]
+//                           (4 .. 30 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -71,7 +75,8 @@
 //                           tests/test_pose_refine_gpu.py::test_the_pose_refinement_tests_fail_on_the_wrong_builds for 17 and 18,
 //                           tests/test_rigid_bundles_gpu.py::test_the_rigid_bundle_tests_fail_on_the_wrong_builds for 19 and 20,
 //                           tests/test_decode_stage_gpu.py::test_the_decode_stage_tests_fail_on_the_wrong_builds for 21 .. 24,
-//                           tests/test_pose_covariance_gpu.py::test_the_pose_covariance_tests_fail_on_the_wrong_builds for 25 .. 27)
+//                           tests/test_pose_covariance_gpu.py::test_the_pose_covariance_tests_fail_on_the_wrong_builds for 25 .. 27,
+//                           tests/test_corner_undistortion_gpu.py::test_the_undistortion_tests_fail_on_the_wrong_builds for 28 .. 30)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -125,6 +130,24 @@
 #define CAM_RATIONAL_DEN(den) ((void)(den), 1.0)
 #else
 #define CAM_RATIONAL_DEN(den) (den)
+#endif
+
+// ---- corner undistortion: entry j of the rectification rotation (undistort.h), the records the pose launches read with the mode on
+// ---- (raw: d_dets, und: d_dets_u), and the camera model of batch slot i -----------------------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 28
+#define UD_R(R, j) ((void)(R), ((j) % 4 == 0 ? 1.0 : 0.0))
+#else
+#define UD_R(R, j) ((R)[j])
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 29
+#define UD_POSE_RECORDS(raw, und) ((void)(und), (raw))
+#else
+#define UD_POSE_RECORDS(raw, und) ((void)(raw), (und))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 30
+#define UD_MODEL_OF_SLOT(i, ncams) ((void)(i), (void)(ncams), 0u)
+#else
+#define UD_MODEL_OF_SLOT(i, ncams) ((i) % (ncams))
 #endif
 
 // ---- resize: the source position in 1/2048 pixel of destination index i, and the target size of batch slot i -------------------------

@@ -51,7 +51,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, **caps):
+                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -93,6 +93,8 @@ class AprilTagDetector:
                 self.set_rectification(rectification)
             if resize:
                 self.set_resize(resize)
+            if corner_undistortion:
+                self.set_corner_undistortion(corner_undistortion)
             if bundles:
                 self.set_bundles(bundles)
             if bundles_ex:
@@ -236,6 +238,35 @@ class AprilTagDetector:
         capi._check("amdAprilTagsGetBundlePoseCovariancesEx", self._L.amdAprilTagsGetBundlePoseCovariancesEx(
             self._h, arr.ctypes.data_as(C.POINTER(capi.PoseCovariance)), n))
         return arr[:n * self.nbundles_ex].reshape(n, self.nbundles_ex)
+
+    def set_corner_undistortion(self, models):
+        """amdAprilTagsSetCornerUndistortion (raw-frame mode): models is a list of (K, D, Knew) or (K, D, Knew, model_name, R), as
+        set_rectification takes them.  Frame i of every following submission is detected as it stands, and every record it keeps gets an
+        undistorted twin under models[i % len(models)]: corners through the inverse of the camera model, the exact homography onto them,
+        centre and pose from that.  The detection records keep the raw frame's values; undistorted_detections(n) hands out the twins, and
+        bundle_poses, bundle_poses_ex, refined_poses and the covariances are computed from them.  Pass Knew's fx, fy, cx, cy as the pose
+        intrinsics.  None or [] turns it off; refused while rectification is on."""
+        arr = capi.camera_models_ex(list(models or []))
+        capi._check("amdAprilTagsSetCornerUndistortion", self._L.amdAprilTagsSetCornerUndistortion(self._h, len(arr), arr))
+
+    def undistorted_detections(self, n):
+        """amdAprilTagsGetUndistortedDetections: the undistorted twins of the first n frames of the last completed submission, a list per
+        frame, aligned by index with the frame's detections, of {"status" (capi.UNDISTORT_OK / UNDISTORT_INVALID), "H" (3x3), "center",
+        "p" (4x2), "R" (3x3), "t"}; an invalid record's fields are all zero."""
+        out = []
+        for f in range(n):
+            cnt = C.c_uint32(0)
+            probe = (capi.UndistortedDetection * 1)()
+            rc = self._L.amdAprilTagsGetUndistortedDetections(self._h, f, probe, 0, C.byref(cnt))   # the count (refused for its capacity when > 0)
+            if rc and cnt.value == 0:
+                capi._check("amdAprilTagsGetUndistortedDetections", rc)
+            arr = (capi.UndistortedDetection * max(cnt.value, 1))()
+            capi._check("amdAprilTagsGetUndistortedDetections",
+                        self._L.amdAprilTagsGetUndistortedDetections(self._h, f, arr, cnt.value, C.byref(cnt)))
+            out.append([{"status": int(r.status), "H": np.array(list(r.H)).reshape(3, 3), "center": np.array(list(r.c)),
+                         "p": np.array([[r.p[i][0], r.p[i][1]] for i in range(4)]), "R": np.array(list(r.R)).reshape(3, 3),
+                         "t": np.array(list(r.t))} for r in arr[:cnt.value]])
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -430,3 +461,15 @@ class AprilTagDetector:
         capi._check("amdAprilTagsDebugReconcile",
                     self._L.amdAprilTagsDebugReconcile(self._h, len(rec), rec.ctypes.data, out.ctypes.data, len(out), C.byref(nout)))
         return out[:min(nout.value, len(out))].copy()
+
+    def debug_undistort(self, records, model):
+        """amdAprilTagsDebugUndistort: k_undistort_records alone on `records` (capi.DET_DTYPE; at most max_detections of them, taken as
+        one frame's kept records in the order given) under model = (K, D, Knew) or (K, D, Knew, model_name, R).  Returns (public records:
+        capi.UNDISTORTED_DTYPE, device twins: capi.DET_DTYPE).  The last submission's stage buffers cannot be read afterwards."""
+        rec = np.array(records, dtype=capi.DET_DTYPE, order="C", copy=True).reshape(-1)
+        cam = capi.camera_models_ex([model])
+        out = np.zeros(max(len(rec), 1), dtype=capi.UNDISTORTED_DTYPE)
+        twins = np.zeros(max(len(rec), 1), dtype=capi.DET_DTYPE)
+        capi._check("amdAprilTagsDebugUndistort",
+                    self._L.amdAprilTagsDebugUndistort(self._h, len(rec), rec.ctypes.data, cam, out.ctypes.data, twins.ctypes.data))
+        return out[:len(rec)].copy(), twins[:len(rec)].copy()

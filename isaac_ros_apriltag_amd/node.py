@@ -129,6 +129,12 @@ def lib():
         L.node_shell_multi_create_refined.restype = C.c_void_p
         L.node_shell_multi_create_refined.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32,
                                                       C.c_char_p, C.c_size_t]
+        L.node_shell_create_undistort_refined.restype = C.c_void_p
+        L.node_shell_create_undistort_refined.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_double,
+                                                          C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_undistort_refined.restype = C.c_void_p
+        L.node_shell_multi_create_undistort_refined.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                                                C.c_uint32, C.c_char_p, C.c_size_t]
         L.node_shell_last_transforms.restype = C.c_int
         L.node_shell_last_transforms.argtypes = [C.c_void_p, C.POINTER(ShellTransform), C.c_int]
         L.node_shell_last_bundle_poses.restype = C.c_int
@@ -262,11 +268,13 @@ def _rotation(R):
 
 
 def _rectify_flag(rectify):
-    """NodeOptions::rectify / rectify_full as the flat view takes them: False 0, True 1, "full" 2."""
+    """NodeOptions::rectify / rectify_full / undistort_corners as the flat view takes them: False 0, True 1, "full" 2, "corners" 3."""
     if rectify == "full":
         return 2
+    if rectify == "corners":
+        return 3
     if isinstance(rectify, str):
-        raise ValueError("rectify is False, True or \"full\"")
+        raise ValueError("rectify is False, True, \"full\" or \"corners\"")
     return 1 if rectify else 0
 
 
@@ -292,7 +300,9 @@ class AprilTagMultiCameraNode:
         """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
         undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
-        (NodeOptions::rectify_full): with any of the three distortion models and the rotation R of its CameraInfo.  resize
+        (NodeOptions::rectify_full): with any of the three distortion models and the rotation R of its CameraInfo; "corners"
+        (NodeOptions::undistort_corners): the frames are detected raw and the detections' corners undistorted under that model -- poses
+        and transforms are those of the undistorted corners, corners and centre stay the raw frame's.  resize
         (NodeOptions::resize_width, resize_height): (w, h) -- frames of any size are resized to it inside the submission, behind the
         rectification, and the pose is computed with the scaled camera.  bundles (NodeOptions::bundles, alone among the extensions):
         [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'.
@@ -323,6 +333,15 @@ class AprilTagMultiCameraNode:
             arr = _shell_rigid_bundles(rigid_bundles)
             self._h = self._L.node_shell_multi_create_rigid_bundles(num_streams, max_tags, size, tile_size, tag_family.encode(),
                                                                     backends.encode(), decimate, 1 if auto_flush else 0, len(arr), arr, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
+        if pose_refinement and rectify == "corners" and not (bundles or quad_sigma or max_width or max_height or resize or rigid_bundles
+                                                             or pose_covariance):
+            # (NodeOptions::undistort_corners beside pose_refinement: the one pair of extensions this view serves together)
+            self._h = self._L.node_shell_multi_create_undistort_refined(num_streams, max_tags, size, tile_size, tag_family.encode(),
+                                                                        backends.encode(), decimate, 1 if auto_flush else 0,
+                                                                        int(pose_refinement), err, 1024)
             if not self._h:
                 raise RuntimeError(err.value.decode())
             return
@@ -416,7 +435,8 @@ class AprilTagNode:
         """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
         (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
-        three distortion models and the rotation R of that CameraInfo.  resize (NodeOptions::resize_width, resize_height):
+        three distortion models and the rotation R of that CameraInfo; "corners" (NodeOptions::undistort_corners): the frames are
+        detected raw and the detections' corners undistorted under that model.  resize (NodeOptions::resize_width, resize_height):
         (w, h) -- the handle has that size, frames of any size are resized to it inside the submission, behind the rectification, and
         the pose is computed with the camera scaled by w / width and h / height.  bundles (NodeOptions::bundles, alone among the
         extensions): [{"name", "members": [(id, x, y, size)], ...}] -- one "bundle:<name>" transform per solved bundle behind the tags'.
@@ -430,6 +450,13 @@ class AprilTagNode:
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags = max_tags
+        if pose_refinement and rectify == "corners" and not (bundles or quad_sigma or resize or rigid_bundles or strict_cuapriltags_encodings):
+            # (NodeOptions::undistort_corners beside pose_refinement and, where given, pose_covariance: served together by this view)
+            self._h = self._L.node_shell_create_undistort_refined(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                                  int(pose_refinement), float(pose_covariance), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if pose_covariance:
             if bundles or quad_sigma or rectify or resize or strict_cuapriltags_encodings or not (pose_refinement or rigid_bundles):
                 raise ValueError("pose_covariance is served with pose_refinement and / or rigid_bundles by this view, and with nothing else")

@@ -54,6 +54,9 @@ public:
     // the same for every camera camera_info describes: plumb_bob, rational_polynomial or equidistant, behind its rectification
     // rotation R (either half of a stereo pair)
     opt.rectify_full = declare_parameter<bool>("rectify_full", false);
+    // raw-frame mode, in place of both: the distorted image is detected as it stands and the detections' corners are undistorted under
+    // that model; poses, transforms and covariances are those of the undistorted corners, in the rectified camera's frame
+    opt.undistort_corners = declare_parameter<bool>("undistort_corners", false);
     // both set: every frame, whatever its size, is resized to resize_width x resize_height inside the detector's submission (behind the
     // rectification), in place of a ResizeNode in front of this one; the pose uses the camera scaled to that size.  0: off
     opt.resize_width = static_cast<uint32_t>(declare_parameter<int>("resize_width", 0));
