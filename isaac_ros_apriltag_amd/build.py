@@ -1,19 +1,26 @@
 """Builds the native pieces of the package in-tree (the .so files travel to the GPU box with the repo).
 
   libapriltag_amd.so    HIP kernels + C ABI (hipcc, gfx950 only)         <- csrc/detector.hip
+  libapriltag_amd.resources.txt   registers, spills, scratch, LDS and occupancy per kernel, as that compile reported them
   libapriltag_synth.so  deterministic frame renderer (host C)            <- csrc/synth_render.c
   libapriltag_node.so   ROS-free C++ mirror of the reference node shell  <- csrc/node_shell.cpp (if present)
   examples/multi_stream_host   C++ multi-GPU front end (RCCL broadcast)  <- examples/multi_stream_host.cpp
 """
 import os
+import re
 import shutil
 import subprocess
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_AMD = os.path.join(_HERE, "libapriltag_amd.so")
 LIB_SYNTH = os.path.join(_HERE, "libapriltag_synth.so")
 LIB_NODE = os.path.join(_HERE, "libapriltag_node.so")
+# what the compiler reported per kernel of libapriltag_amd.so (registers, spills, private segment, LDS, occupancy): written by
+# build_amd() from the remarks of the product compile itself, read by tests/test_kernel_scratch_cpu.py and tools/kernel_resources.py
+RESOURCES_AMD = os.path.join(_HERE, "libapriltag_amd.resources.txt")
+_REMARK = "-Rpass-analysis=kernel-resource-usage"   # a remark: does not change code generation
 
 
 def _hipcc():
@@ -40,13 +47,63 @@ def _sources(*exts):
     return out
 
 
+def _demangle(names):
+    for f in (os.path.join(os.path.dirname(_hipcc()), "..", "llvm", "bin", "llvm-cxxfilt"), shutil.which("llvm-cxxfilt"), shutil.which("c++filt")):
+        if f and os.path.exists(f):
+            out = subprocess.run([f] + list(names), capture_output=True, text=True).stdout.splitlines()
+            if len(out) == len(names):
+                return out
+    return list(names)
+
+
+def resource_remarks(stderr_text):
+    """The kernel-resource-usage remarks of a hipcc run as text: per kernel one "Function Name: <demangled name without arguments>"
+    line, then its "    <field>: <number>" lines as the compiler printed them (units dropped); and what else the compiler said."""
+    kernels, rest, skip = [], [], 0
+    for line in stderr_text.splitlines():
+        if _REMARK in line:
+            m = re.search(r"remark:\s+([A-Za-z ]+\w)(?: \[[^\]]*\])?: (\S+) \[" + _REMARK, line)
+            if m and m.group(1) == "Function Name":
+                kernels.append((m.group(2), []))
+                skip = 2   # the source line and the caret under it
+            elif m and kernels:
+                kernels[-1][1].append("    %s: %s" % (m.group(1), m.group(2)))
+        elif skip and not line.startswith("In file included"):
+            skip -= 1
+        elif not (line.startswith("In file included") or re.match(r"\d+ (warning|remark)s? generated", line.strip())):
+            rest.append(line)
+    names = _demangle([k for k, _ in kernels])
+    text = "".join("Function Name: %s\n%s\n" % (n.split("(")[0].replace("void ", "", 1), "\n".join(f)) for n, (_, f) in zip(names, kernels))
+    return text, "\n".join(rest)
+
+
+def parse_resources(text):
+    """{kernel name: {field: int}} of a file written by build_amd() (RESOURCES_AMD)."""
+    rows, cur = {}, None
+    for line in text.splitlines():
+        if line.startswith("Function Name: "):
+            cur = rows.setdefault(line[len("Function Name: "):].strip(), {})
+        elif cur is not None and ": " in line:
+            k, v = line.strip().rsplit(": ", 1)
+            if v.isdigit():
+                cur[k] = int(v)
+    return rows
+
+
 def build_amd(force=False):
     srcs = _sources(".hip", ".h")
-    if force or _newer(LIB_AMD, srcs):
+    if force or _newer(LIB_AMD, srcs) or not os.path.exists(RESOURCES_AMD):
         cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-               "-fno-fast-math", "-Wall", "-Wno-unused-value", "-Wno-unused-function", "-Wno-pass-failed",
+               "-fno-fast-math", "-Wall", "-Wno-unused-value", "-Wno-unused-function", "-Wno-pass-failed", _REMARK,
                os.path.join(_CSRC, "detector.hip"), "-o", LIB_AMD]
-        subprocess.check_call(cmd)
+        r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+        text, rest = resource_remarks(r.stderr)
+        if rest.strip():
+            sys.stderr.write(rest + "\n")
+        if r.returncode:
+            raise subprocess.CalledProcessError(r.returncode, cmd)
+        with open(RESOURCES_AMD, "w") as f:
+            f.write(text)
     return LIB_AMD
 
 

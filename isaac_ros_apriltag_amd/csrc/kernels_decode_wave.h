@@ -16,7 +16,7 @@
 #define DW_KB 9     // steps of the normal search whose image gathers are in flight together (17 steps at full resolution)
 #endif
 
-// 6 waves per SIMD (80 registers, a few spilled): the per-quad work is chains of dependent double-precision operations in
+// 6 waves per SIMD (80 registers, six spilled): the per-quad work is chains of dependent double-precision operations in
 // the CPU definition's order, so the stage's rate is set by how many quads are in flight (1.16 -> 0.80 ms per 256 noisy
 // frames together with the larger grid; 5 and 7 waves measured slower)
 #ifndef DW_WPE
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
   __shared__ double s_values[144], s_sharp[64];
 
   const int frame = (int)blockIdx.y + P.frame0;
-  const int lane = threadIdx.x;
+  int lane = threadIdx.x;
   uint32_t nq = counters[frame].nquads;
   if (nq > P.qcap) nq = P.qcap;
   const FrameDesc fd = frames[frame];
@@ -45,9 +45,18 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
   const int w = fd.W0, h = fd.H0, pitch = (int)fd.pitch;   // the frame's own input size
 
   for (uint32_t qi = blockIdx.x; qi < nq; qi += gridDim.x) {
+    // The lane index is made opaque once per quad (as k_fit_quads does with its thread index, kernels_quad.h): what a lane
+    // derives from it alone is re-derived where it is used instead of living across the whole quad loop.  With the quad's
+    // corners read per lane from memory (below; indexing the register copy of the record by the lane put the whole record
+    // into the private segment) the kernel went from 36 spilled registers and 192 bytes of scratch, reloaded inside the
+    // search and decode loops, to 6 and 28 bytes, reloaded once per quad or per chunk of samples: decode stage 0.47 -> 0.41 ms
+    // per 256 noisy frames.
+    asm volatile("" : "+v"(lane));
+    __builtin_assume(lane >= 0 && lane < 64);
     __syncthreads();
-    const QuadRec q = quads_all[(size_t)frame * P.qcap + qi];
-    if (lane < 4) { s_p[lane][0] = s_p0[lane][0] = q.p[lane][0]; s_p[lane][1] = s_p0[lane][1] = q.p[lane][1]; }
+    const QuadRec* const qg = quads_all + (size_t)frame * P.qcap + qi;
+    const QuadRec q = *qg;
+    if (lane < 4) { s_p[lane][0] = s_p0[lane][0] = qg->p[lane][0]; s_p[lane][1] = s_p0[lane][1] = qg->p[lane][1]; }
     __syncthreads();
 
     // ---- S6 edge refinement -------------------------------------------------------------------

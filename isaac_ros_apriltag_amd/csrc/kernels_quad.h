@@ -929,7 +929,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
   __shared__ uint32_t s_okf[FQ_XG], s_okw[FQ_XG];   // early exit: admissible forward / wrap-around arcs per cut group
   __shared__ int s_feasible;
 
-  const int tid = threadIdx.x;
+  int tid = threadIdx.x;
   const uint32_t nwork = min(*work_n, work_cap);
   // scratch slot of this workgroup: cumulative moments of the cluster in flight (and, for clusters that do
   // not fit the LDS key array, their sort keys and two error arrays)
@@ -952,6 +952,14 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
   // microsecond) put the last cluster's start some 40 us behind the first's.  The cursor hands out the items from gridDim.x on.
   uint32_t next_item = blockIdx.x, chunk_left = 1;   // uniform
   for (;;) {
+    // The thread index is made opaque once per cluster.  Everything a thread derives from it alone -- LDS addresses of its key
+    // slots, table rows and staging rows, its index pair of the 45, the masks of "tid < 45", "lane == 63" and their like -- is
+    // invariant in this loop; hoisted to kernel entry, some thirty such values were live across all phases, 9 .. 17 of them
+    // in scratch (and two more registers held SGPR masks), reloaded once per cluster.  Re-derived where a phase uses them they
+    // cost a few integer instructions per cluster and the kernel needs no private segment: a launch that needs one started
+    // 0.13 ms late whenever the segment on its queue had to grow.  No arithmetic depends on this.
+    asm volatile("" : "+v"(tid));
+    __builtin_assume(tid >= 0 && tid < NT);
     __syncthreads();   // the previous cluster's LDS use (and s_item) is finished in every wave
     if (chunk_left == 0) {
       if (tid == 0) s_item = gridDim.x + atomicAdd(work_cursor, (uint32_t)pop);

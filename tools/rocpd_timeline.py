@@ -25,3 +25,13 @@ print("step with the longest scatter-end -> decode-start span: %.3f ms" % ((best
 for r in best["fits"]:
     print("%-24s start %8.3f ms  end %8.3f ms  dur %8.3f ms  grid=(%s,%s) lds=%s" %
           (r[0].split("(")[0][5:], (r[1] - t0) / 1e6, (r[2] - t0) / 1e6, (r[2] - r[1]) / 1e6, r[3], r[4], r[5]))
+# Every step: the idle time in front of the second, third and fourth fit launch (each starts where its predecessor on the
+# submission stream ended) and the span of the fit.  The longest step is as a rule the FIRST of the process, which pays what
+# only a first submission pays (a queue's private segment is set up when a launch first needs one).
+print("every step (gaps in us in front of launches 2, 3, 4 of the fit; first fit start -> last fit end in ms):")
+for gi, g in enumerate(groups):
+    f = g["fits"]
+    if len(f) < 4:
+        continue
+    gaps = ["%s %6.1f" % (f[k][0].split("(")[0][5:], (f[k][1] - f[k - 1][2]) / 1e3) for k in (1, 2, 3)]
+    print("step %d:  %s   span %7.3f" % (gi, "   ".join(gaps), (max(r[2] for r in f) - f[0][1]) / 1e6))
