@@ -164,7 +164,7 @@ def build_stress(force=False):
     return LIB_STRESS
 
 
-MUTANTS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30)   # csrc/tools_hooks.h, AMDAT_MUTATE
+MUTANTS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36)   # csrc/tools_hooks.h, AMDAT_MUTATE
 
 
 def lib_mutant(n):
@@ -187,13 +187,16 @@ def build_mutants(force=False):
     24 k_reconcile's order with margins ascending, 25 the pose covariance without the skew term in J_u, 26 the second quad of
     k_pose_refine<true> at chain 0's pose, 27 a rigid bundle's covariance with centred object points, 28 the corner undistortion without its rectification rotation, 29 the
     pose launches on the raw records with the corner undistortion on, 30 every frame of an undistorted submission with the first
-    camera's model),
+    camera's model, 31 the one-pass threshold's low-contrast rule with <=, 32 k_threshold_leftover with >= against the threshold,
+    33 cc_row_requests' up-link skip without the left-source guard, 34 k_cc_resolve with > against min_component_size, 35 k_points'
+    general form with every left neighbour a source, 36 k_cluster_select with > against min_cluster_points),
     shipped like the stress build so that the GPU suite itself shows, under the driver's eyes, that its stage tests FAIL on each of them
     (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds, tests/test_per_frame_sizes_gpu.py for 6,
     tests/test_fit_classes_gpu.py for 7 and 8, tests/test_rectify_submission_gpu.py for 9 and 10,
     tests/test_resize_submission_gpu.py for 11 and 12, tests/test_camera_models_gpu.py for 13 and 14, tests/test_bundles_gpu.py for 15 and 16,
     tests/test_pose_refine_gpu.py for 17 and 18, tests/test_rigid_bundles_gpu.py for 19 and 20, tests/test_decode_stage_gpu.py for
-    21 .. 24, tests/test_pose_covariance_gpu.py for 25 .. 27, tests/test_corner_undistortion_gpu.py for 28 .. 30).  Never loaded by the product path."""
+    21 .. 24, tests/test_pose_covariance_gpu.py for 25 .. 27, tests/test_corner_undistortion_gpu.py for 28 .. 30,
+    tests/test_integer_stages_gpu.py for 31 .. 36).  Never loaded by the product path."""
     import threading
     err = []
 

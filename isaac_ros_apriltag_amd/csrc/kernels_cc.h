@@ -399,7 +399,7 @@ __device__ __forceinline__ void cc_row_requests(int W, int gx, uint32_t tl, uint
   if (gx < 1 || gx > W - 2 || tc == AT_NO_LABEL) return;
   const uint32_t me = tc & AT_LABEL_MASK;
   const bool left_src = gx - 1 >= 1;
-  if (pe_same(bc, tc) && !(left_src && pe_same(tl, tc) && pe_same(bl, tc))) { ra[0] = me; rb[0] = bc & AT_LABEL_MASK; }
+  if (pe_same(bc, tc) && !(CC_ROW_UP_LEFT_SRC(left_src) && pe_same(tl, tc) && pe_same(bl, tc))) { ra[0] = me; rb[0] = bc & AT_LABEL_MASK; }
   if (pe_white(tc)) {
     if (pe_white(bl) && !pe_white(bc) && !(left_src && pe_white(tl))) { ra[1] = me; rb[1] = bl & AT_LABEL_MASK; }
     const bool right_src = gx + 1 <= W - 2;
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(256) void k_cc_resolve(uint32_t* __restrict__ label
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nroots; i += gridDim.x * 256) {
     const uint32_t p = roots[i];
     const uint32_t r = label[p];   // (k_cc_sizes left the representative there, without the bit)
-    if ((int)csize[r] >= P.min_component_size) {
+    if (CC_RESOLVE_LARGE((int)csize[r], P.min_component_size)) {   // (tools_hooks.h: count >= min_component_size)
       label[p] = r | AT_LABEL_BIG;
       label[r] = r | AT_LABEL_BIG;
     }

@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void k_points(const uint8_t* __restrict__ thr_
       }
     } else {
     const bool gx_ok = gx >= 1 && gx <= W - 2;
-    const bool left_is_source = gx - 1 >= 1;
+    const bool left_is_source = PT_LEFT_IS_SOURCE(gx - 1 >= 1);   // (tools_hooks.h: as it stands)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int ly = (tid >> 6) + 4 * k;
@@ -481,7 +481,7 @@ __global__ __launch_bounds__(256) void k_cluster_select(unsigned long long* __re
     for (int j = 0; j < 4; j++) {
       key[j] = c[j] ? hkeys_all[hi + j] : AT_EMPTY_KEY;
       if (c[j]) hkeys_all[hi + j] = AT_EMPTY_KEY;   // this kernel is the table's last reader: it leaves it empty for the next submission
-      keep[j] = frame_ok && key[j] != AT_EMPTY_KEY && (int)c[j] >= P.min_cluster_points && (int)c[j] <= max_cluster_points;
+      keep[j] = frame_ok && key[j] != AT_EMPTY_KEY && SEL_ENOUGH_POINTS((int)c[j], P.min_cluster_points) && (int)c[j] <= max_cluster_points;
       if (keep[j]) { tsum += c[j]; tcnt++; }
     }
     const uint32_t inc = wave_incl_scan(tsum), cinc = wave_incl_scan(tcnt);

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void k_threshold(const FrameDesc* __restrict__
       valid[j] = tX < ftw;
       const uint32_t mn = min(min(cmin[j], cmin[j + 1]), cmin[j + 2]);
       const uint32_t mx = max(max(cmax[j], cmax[j + 1]), cmax[j + 2]);
-      if ((int)(mx - mn) < P.min_white_black_diff) {
+      if (TH_LOW_CONTRAST((int)(mx - mn), P.min_white_black_diff)) {   // (tools_hooks.h: range < min_diff)
 #pragma unroll
         for (int r = 0; r < 4; r++) o[r][j] = 0x7F7F7F7Fu;
       } else {
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256) void k_threshold_leftover(const FrameDesc* __r
         }
   uint32_t thresh = mn + (mx - mn) / 2;
   uint32_t v = th_px<DEC, FMT>(simg, spitch, sW0, sH0, x, y);
-  thr_all[(size_t)frame * P.H * P.WS + (size_t)y * P.WS + x] = v > thresh ? 255 : 0;
+  thr_all[(size_t)frame * P.H * P.WS + (size_t)y * P.WS + x] = TH_STRIP_WHITE(v, thresh) ? 255 : 0;   // (tools_hooks.h: v > thresh)
   if (DEC > 1) gray_all[(size_t)frame * P.H * P.WS + (size_t)y * P.WS + x] = (uint8_t)v;
   // (FMT: the one-pass kernel's units cover these pixels too and have written their gray values)
 }

@@ -63,7 +63,18 @@
 //                           29 = with amdAprilTagsSetCornerUndistortion on, the bundle and refinement launches still read the raw
 //                               records (d_dets, not d_dets_u: two live buffers of one size)
 //                           30 = amdAprilTagsSetCornerUndistortion: every frame of a submission takes cams[0] instead of cams[i % ncams]
-//                           (4 .. 30 change values only: no address, index bound, launch size or loop count)
+//                           31 = the low-contrast rule of the one-pass k_threshold (tile size 4) as mx - mn <= min_white_black_diff:
+//                               wrong only in a tile whose dilated range is exactly min_white_black_diff (5)
+//                           32 = k_threshold_leftover compares v >= thresh: wrong only where a pixel right of / below the last full
+//                               tile equals its nearest tile's threshold
+//                           33 = cc_row_requests (k_cc_border) skips the up link without asking whether the left neighbour is a link
+//                               source: wrong only at x = 1 on a tile-top row, where column 0 carries no link
+//                           34 = k_cc_resolve sets the size bit for a count > min_component_size: wrong only for a component that
+//                               reaches exactly min_component_size (25) pixels across tiles
+//                           35 = the general form of k_points takes every left neighbour for an emission source: wrong only at x = 1
+//                           36 = k_cluster_select keeps a pair for a count > min_cluster_points: wrong only for a cluster of exactly
+//                               min_cluster_points (24) points
+//                           (4 .. 36 change values only: no address, index bound, launch size or loop count)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -76,7 +87,8 @@
 //                           tests/test_rigid_bundles_gpu.py::test_the_rigid_bundle_tests_fail_on_the_wrong_builds for 19 and 20,
 //                           tests/test_decode_stage_gpu.py::test_the_decode_stage_tests_fail_on_the_wrong_builds for 21 .. 24,
 //                           tests/test_pose_covariance_gpu.py::test_the_pose_covariance_tests_fail_on_the_wrong_builds for 25 .. 27,
-//                           tests/test_corner_undistortion_gpu.py::test_the_undistortion_tests_fail_on_the_wrong_builds for 28 .. 30)
+//                           tests/test_corner_undistortion_gpu.py::test_the_undistortion_tests_fail_on_the_wrong_builds for 28 .. 30,
+//                           tests/test_integer_stages_gpu.py::test_integer_stage_tests_fail_on_the_wrong_builds for 31 .. 36)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -99,6 +111,40 @@
 #define CC_LAST_ROW_OFFSET(NW) ((NW) == 4 ? 2 : 1)
 #else
 #define CC_LAST_ROW_OFFSET(NW) 1
+#endif
+
+// ---- the integer stages: the low-contrast rule of the one-pass k_threshold; "white" in k_threshold_leftover; whether the up link's
+// ---- skip rule of cc_row_requests may rely on the left neighbour; "large enough" in k_cc_resolve; whether the left neighbour of a
+// ---- pixel of k_points' general form is an emission source; "enough points" in k_cluster_select ------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 31
+#define TH_LOW_CONTRAST(range, min_diff) ((range) <= (min_diff))
+#else
+#define TH_LOW_CONTRAST(range, min_diff) ((range) < (min_diff))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 32
+#define TH_STRIP_WHITE(v, thresh) ((v) >= (thresh))
+#else
+#define TH_STRIP_WHITE(v, thresh) ((v) > (thresh))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 33
+#define CC_ROW_UP_LEFT_SRC(left_src) ((void)(left_src), true)
+#else
+#define CC_ROW_UP_LEFT_SRC(left_src) (left_src)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 34
+#define CC_RESOLVE_LARGE(size, min_size) ((size) > (min_size))
+#else
+#define CC_RESOLVE_LARGE(size, min_size) ((size) >= (min_size))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 35
+#define PT_LEFT_IS_SOURCE(is_source) ((void)(is_source), true)
+#else
+#define PT_LEFT_IS_SOURCE(is_source) (is_source)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 36
+#define SEL_ENOUGH_POINTS(count, min_points) ((count) > (min_points))
+#else
+#define SEL_ENOUGH_POINTS(count, min_points) ((count) >= (min_points))
 #endif
 
 // ---- k_quad_sigma: the half width of the copy rule on the far (right / bottom) edge of a pass --------------------------------------
