@@ -53,7 +53,7 @@ __device__ __forceinline__ int fit_border_reversed(const FitCentre& c, double sx
 }
 __device__ __forceinline__ bool fit_border_unwanted(int reversed, const DetParams& P) {
   if (!P.reversed_border && reversed) return true;
-  if (!P.normal_border && !reversed) return true;
+  if (FIT_NORMAL_UNWANTED(P, reversed)) return true;   // (tools_hooks.h: !P.normal_border && !reversed)
   return false;
 }
 

@@ -791,7 +791,7 @@ __device__ __forceinline__ void fq_corner_search(const double* s_tab, const uint
     const bool pass = q3 < m && ((fok >> p01) & 1ull) && ((fok >> p12) & 1ull) && ((fok >> p23) & 1ull) && ((wok >> p03) & 1ull);
     if (pass) {
       const double dotn = s_tab[FQT_FNX + p01] * s_tab[FQT_FNX + p12] + s_tab[FQT_FNY + p01] * s_tab[FQT_FNY + p12];
-      if (!(fabs(dotn) > P.cos_critical_rad)) {
+      if (!(FQ_DOT_SIZE(dotn) > P.cos_critical_rad)) {   // (tools_hooks.h: fabs(dotn))
         const double e = s_tab[FQT_FERR + p01] + s_tab[FQT_FERR + p12] + s_tab[FQT_FERR + p23] + s_tab[FQT_WERR + p03];
         if (e < best_err) { best_err = e; best_t = t; }
       }
@@ -1416,6 +1416,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
     // Selection and ordering of at most max_nmaxima corners: wave 0 alone, no workgroup barriers inside.
     // When there are more candidates, the current largest is removed (max_nmaxima + 1) times; the last
     // removed value is the threshold (only the values matter, so ties may be broken arbitrarily).
+    // (FIT_CUT_RANK(site, n): tools_hooks.h, n in the product build.)
     if (tid < 64) {
       const int lane = tid;
       if (nmaxima > P.max_nmaxima && nmaxima <= 64) {
@@ -1429,10 +1430,10 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
           const unsigned long long ok = readlane_u64(myk, l);
           rank += (ok > myk || (ok == myk && l < lane)) ? 1 : 0;
         }
-        const unsigned long long tmask = __ballot(have && rank == P.max_nmaxima);
+        const unsigned long long tmask = __ballot(have && rank == FIT_CUT_RANK(1, P.max_nmaxima));
         const int tl = (int)__ffsll((long long)tmask) - 1;
         const unsigned long long tk = shfl_u64(myk, tl);
-        const bool kept = have && rank < P.max_nmaxima && myk > tk;
+        const bool kept = have && rank < FIT_CUT_RANK(1, P.max_nmaxima) && myk > tk;
         const unsigned long long kmask = __ballot(kept);
         if (kept) s_maxidx[__popcll(kmask & ((1ull << lane) - 1ull))] = myi;
         if (lane == 0) s_nkept = (int)__popcll(kmask);
@@ -1448,7 +1449,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
         }
         unsigned long long rem_key = 0;   // lane r (< 12) keeps the key and candidate index of round r
         int rem_k = 0;
-        for (int round = 0; round <= P.max_nmaxima; round++) {
+        for (int round = 0; round <= FIT_CUT_RANK(2, P.max_nmaxima); round++) {
           unsigned long long bk = 0; int br = 0;
 #pragma unroll
           for (int r = 0; r < FQ_SEL_REGS; r++)
@@ -1465,14 +1466,14 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
           if (lane == round) { rem_key = mk; rem_k = src + 64 * wr; }
         }
         // threshold = key of the last round; keep the earlier winners that are strictly larger
-        const unsigned long long tk = shfl_u64(rem_key, P.max_nmaxima);
-        const bool kept = lane < P.max_nmaxima && rem_key > tk;
+        const unsigned long long tk = shfl_u64(rem_key, FIT_CUT_RANK(2, P.max_nmaxima));
+        const bool kept = lane < FIT_CUT_RANK(2, P.max_nmaxima) && rem_key > tk;
         const unsigned long long kmask = __ballot(kept);
         if (kept) s_maxidx[__popcll(kmask & ((1ull << lane) - 1ull))] = cand_idx[rem_k];
         if (lane == 0) s_nkept = (int)__popcll(kmask);
         __threadfence_block();
       } else if (nmaxima > P.max_nmaxima) {
-        for (int round = 0; round <= P.max_nmaxima; round++) {
+        for (int round = 0; round <= FIT_CUT_RANK(3, P.max_nmaxima); round++) {
           unsigned long long bk = 0; int bi = -1;
           for (int k = lane; k < nmaxima; k += 64) {
             if (cand_idx[k] >= 0) {
@@ -1491,9 +1492,9 @@ __global__ __launch_bounds__(NT, (NT == 64 ? FQ_WPE_64 : NT == 128 ? FQ_WPE_128 
           __threadfence_block();
         }
         if (lane == 0) {
-          const double thresh = s_remval[P.max_nmaxima];
+          const double thresh = s_remval[FIT_CUT_RANK(3, P.max_nmaxima)];
           int mm = 0;
-          for (int r = 0; r < P.max_nmaxima; r++)
+          for (int r = 0; r < FIT_CUT_RANK(3, P.max_nmaxima); r++)
             if (s_remval[r] > thresh) s_maxidx[mm++] = s_remidx[r];
           s_nkept = mm;
         }
@@ -1769,7 +1770,7 @@ __global__ __launch_bounds__(256) void k_quad_finish(const FitCand* __restrict__
       const double q1 = dx1 * dx1 + dy1 * dy1;
       len[k] = __dsqrt_rn(q1);
       const double cos_dtheta = (dx1 * dx2 + dy1 * dy2) / __dsqrt_rn(q1 * (dx2 * dx2 + dy2 * dy2));
-      if ((cos_dtheta > P.cos_critical_rad || cos_dtheta < -P.cos_critical_rad) || dx1 * dy2 < dy1 * dx2) ok = false;
+      if ((cos_dtheta > P.cos_critical_rad || QF_COS_BELOW(cos_dtheta, P.cos_critical_rad)) || QF_WINDING_WRONG(dx1 * dy2, dy1 * dx2)) ok = false;   // (tools_hooks.h: cos_dtheta < -cos_critical_rad, dx1 * dy2 < dy1 * dx2)
     }
     double area = 0;
     {
@@ -1783,7 +1784,7 @@ __global__ __launch_bounds__(256) void k_quad_finish(const FitCand* __restrict__
         area += __dsqrt_rn(hp * (hp - sa) * (hp - sb) * (hp - ed));
       }
     }
-    if (area < 0.95 * P.min_tag_width * P.min_tag_width) ok = false;
+    if (area < QF_AREA_LIMIT(P.min_tag_width)) ok = false;   // (tools_hooks.h: 0.95 * min_tag_width * min_tag_width)
     if (!ok) continue;
     QuadRec q;
 #pragma unroll

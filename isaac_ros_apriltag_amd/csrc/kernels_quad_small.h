@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
     int m;
     if (nmaxima > P.max_nmaxima) {
       // KR candidates per lane as order-preserving keys (0 = none); rank of a key = keys above it (value descending,
-      // position ascending among equals); the key of rank max_nmaxima is the threshold
+      // position ascending among equals); the key of rank max_nmaxima is the threshold (FIT_CUT_RANK: tools_hooks.h, max_nmaxima)
       constexpr int KR = K <= 2 ? 1 : 2;
       unsigned long long myk[KR];
 #pragma unroll
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
       unsigned long long tk = 0;
 #pragma unroll
       for (int r = 0; r < KR; r++) {
-        const unsigned long long tmask = __ballot(myk[r] != 0ull && rank[r] == P.max_nmaxima);
+        const unsigned long long tmask = __ballot(myk[r] != 0ull && rank[r] == FIT_CUT_RANK(0, P.max_nmaxima));
         if (tmask) {
           const int tl = (int)__ffsll((long long)tmask) - 1;
           tk = readlane_u64(myk[r], tl);
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(64, FS_WPE) void k_fit_small(const FrameDesc* __res
       m = 0;
 #pragma unroll
       for (int r = 0; r < KR; r++) {
-        const bool keepc = myk[r] != 0ull && rank[r] < P.max_nmaxima && myk[r] > tk;
+        const bool keepc = myk[r] != 0ull && rank[r] < FIT_CUT_RANK(0, P.max_nmaxima) && myk[r] > tk;
         const unsigned long long kmask = __ballot(keepc);
         if (keepc) s_maxidx[m + (int)__popcll(kmask & ((1ull << lane) - 1ull))] = cand_idx[lane + 64 * r];
         m += (int)__popcll(kmask);

@@ -74,7 +74,19 @@
 //                           35 = the general form of k_points takes every left neighbour for an emission source: wrong only at x = 1
 //                           36 = k_cluster_select keeps a pair for a count > min_cluster_points: wrong only for a cluster of exactly
 //                               min_cluster_points (24) points
-//                           (4 .. 36 change values only: no address, index bound, launch size or loop count)
+//                           37 = k_quad_finish's area limit as 1.0 * w * w: wrong only for a quad whose Heron area lies in
+//                               [0.95 w^2, w^2), w = min_tag_width
+//                           38 = k_quad_finish without cos_dtheta < -cos_critical_rad: a quad with a corner sharper than 10 degrees is kept
+//                           39 = k_quad_finish without the winding term: a quad whose corners turn the wrong way (a dart) is kept
+//                           40 = fit_border_unwanted without its normal_border statement: a handle whose families all have a reversed
+//                               border keeps the quads of normal borders
+//                           41 .. 44 = the cut to max_nmaxima corners takes its threshold from rank max_nmaxima - 1 and so keeps nine:
+//                               41 in k_fit_small, 42 in k_fit_quads with up to 64 maxima, 43 with up to 64 * FQ_SEL_REGS, 44 above;
+//                               wrong only where a corner of the chosen set is the tenth largest maximum
+//                           45 = fq_corner_search without its dot test: a corner choice whose first two sides are nearly parallel is
+//                               admitted
+//                           (4 .. 45 change values only: no address, index bound or launch size; 43 and 44 run their removal loop
+//                           one round less)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -88,7 +100,8 @@
 //                           tests/test_decode_stage_gpu.py::test_the_decode_stage_tests_fail_on_the_wrong_builds for 21 .. 24,
 //                           tests/test_pose_covariance_gpu.py::test_the_pose_covariance_tests_fail_on_the_wrong_builds for 25 .. 27,
 //                           tests/test_corner_undistortion_gpu.py::test_the_undistortion_tests_fail_on_the_wrong_builds for 28 .. 30,
-//                           tests/test_integer_stages_gpu.py::test_integer_stage_tests_fail_on_the_wrong_builds for 31 .. 36)
+//                           tests/test_integer_stages_gpu.py::test_integer_stage_tests_fail_on_the_wrong_builds for 31 .. 36,
+//                           tests/test_fit_rules_gpu.py::test_the_fit_rule_tests_fail_on_the_wrong_builds for 37 .. 45)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -145,6 +158,41 @@
 #define SEL_ENOUGH_POINTS(count, min_points) ((count) > (min_points))
 #else
 #define SEL_ENOUGH_POINTS(count, min_points) ((count) >= (min_points))
+#endif
+
+// ---- the quad fit's rules: k_quad_finish's area limit (w: min_tag_width), its lower angle test and its winding term (a: dx1 * dy2,
+// ---- b: dy1 * dx2); the normal_border statement of fit_border_unwanted; and the rank whose value is the threshold of the cut to
+// ---- max_nmaxima corners (n), per site: 0 k_fit_small, 1 k_fit_quads up to 64 maxima, 2 up to 64 * FQ_SEL_REGS, 3 above ----------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 37
+#define QF_AREA_LIMIT(w) (1.0 * (w) * (w))
+#else
+#define QF_AREA_LIMIT(w) (0.95 * (w) * (w))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 38
+#define QF_COS_BELOW(c, crit) ((void)(c), (void)(crit), false)
+#else
+#define QF_COS_BELOW(c, crit) ((c) < -(crit))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 39
+#define QF_WINDING_WRONG(a, b) ((void)(a), (void)(b), false)
+#else
+#define QF_WINDING_WRONG(a, b) ((a) < (b))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 40
+#define FIT_NORMAL_UNWANTED(P, reversed) ((void)(reversed), false)
+#else
+#define FIT_NORMAL_UNWANTED(P, reversed) (!(P).normal_border && !(reversed))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE >= 41 && AMDAT_MUTATE <= 44
+#define FIT_CUT_RANK(site, n) ((site) == AMDAT_MUTATE - 41 ? (n) - 1 : (n))
+#else
+#define FIT_CUT_RANK(site, n) (n)
+#endif
+// what fq_corner_search's dot test compares with cos_critical_rad (d: the dot product of the first two sides' normals)
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 45
+#define FQ_DOT_SIZE(d) ((void)(d), 0.0)
+#else
+#define FQ_DOT_SIZE(d) fabs(d)
 #endif
 
 // ---- k_quad_sigma: the half width of the copy rule on the far (right / bottom) edge of a pass --------------------------------------

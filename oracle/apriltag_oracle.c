@@ -422,7 +422,39 @@ static void ato_diag_push(int reason, int points) {
     memcpy(r->ratio, g_diag_ratio, sizeof(g_diag_ratio));
   }
 }
-#define ATO_STAT(r, n) do { ato_stats[(r)]++; ato_stats[16 + (r)] += (n); ato_diag_push((r), (n)); } while (0)
+/* Per-cluster log of the quad fit (tests/fit_rule_frames.py; not thread-safe): when ato_fit_cap > 0, every cluster that enters
+ * fit_quad with min_cluster_points or more appends one record when it leaves, whatever the reason.  The log reads the fit's values
+ * and repeats the corner search without the dot test beside it; it changes no result.  A field the cluster did not reach is -1 (NaN
+ * for a double).  nmaxima: maxima before the cut to max_nmaxima; nkept: after it; nties: maxima equal to the cut's threshold value
+ * (the threshold's own included; 0 where nothing was cut); weakest_rank: for a chosen corner set, the rank by value (1 = largest,
+ * over all maxima before the cut) of its weakest corner; dot_removed: corner choices with four admissible sides that the dot test
+ * alone removed; dot_changes: the choice differs (or none is left) with the dot test off; err_per_point: best_error / sz;
+ * min_abs_det: the smallest |det| of the intersections formed; area: the Heron area; min_cos / max_cos / max_abs_cos: over the four
+ * corners' cos_dtheta; winding_fails: corners at which dx1 * dy2 < dy1 * dx2; winding_only: some corner fails the winding term
+ * and none an angle test; cut_changes: with more than max_nmaxima and at most ato_fit_uncut_max maxima (48 unless the caller raises
+ * it: the uncut search of a cluster with hundreds of maxima takes seconds), the choice differs (or appears, or is lost) when the search
+ * runs over all of them; dot_sign_changes: the choice differs when the dot test reads dot > cos_critical_rad, without fabs. */
+typedef struct {
+  uint64_t key;
+  int32_t points_in, points, ksz, reason, nmaxima, nkept, nties, weakest_rank, dot_removed, dot_changes, winding_fails, winding_only, cut_changes, dot_sign_changes;
+  double err_per_point, min_abs_det, area, min_cos, max_cos, max_abs_cos;
+} ato_fit_rec_t;
+ato_fit_rec_t* ato_fit_log;
+int ato_fit_cap, ato_fit_n, ato_fit_uncut_max = 48;
+static __thread ato_fit_rec_t g_fit;
+static __thread int g_fit_on;
+static void ato_fit_begin(uint64_t key, int points_in) {
+  g_fit_on = ato_fit_cap > 0;
+  if (!g_fit_on) return;
+  memset(&g_fit, 0xFF, sizeof(g_fit));   /* every int -1 */
+  g_fit.key = key; g_fit.points_in = points_in;
+  g_fit.err_per_point = g_fit.min_abs_det = g_fit.area = g_fit.min_cos = g_fit.max_cos = g_fit.max_abs_cos = (double)NAN;
+}
+static void ato_fit_push(int reason) {
+  if (g_fit_on && ato_fit_n < ato_fit_cap) { g_fit.reason = reason; ato_fit_log[ato_fit_n++] = g_fit; }
+  g_fit_on = 0;
+}
+#define ATO_STAT(r, n) do { ato_stats[(r)]++; ato_stats[16 + (r)] += (n); ato_diag_push((r), (n)); ato_fit_push((r)); } while (0)
 static __thread int g_qsm_reason;
 
 
@@ -471,9 +503,54 @@ static int dbl_desc(const void* a, const void* b) {
   return (x < y) - (x > y);
 }
 
+/* the fit log's own corner search over maxima[0..n): the best choice with the dot test off (err_all, set_all) and on (err_dot,
+ * set_dot) and with the test as dot > cos_critical_rad (err_sgn, set_sgn), and how many choices have four admissible sides without
+ * (nadm_all) and with it (nadm_dot) */
+static void fit_log_search(const ato_params_t* prm, const lfp_t* lfps, int sz, const int* maxima, int n, int* nadm_all, int* nadm_dot,
+                           double* err_all, int set_all[4], double* err_dot, int set_dot[4], double* err_sgn, int set_sgn[4]) {
+  *nadm_all = *nadm_dot = 0;
+  *err_all = *err_dot = *err_sgn = (double)HUGE_VALF;
+  for (int i = 0; i < 4; i++) set_all[i] = set_dot[i] = set_sgn[i] = 0;
+  if (n < 4) return;
+  /* every side once: E[a * n + b] = the error of the side from maximum a to maximum b (a < b: forward, a > b: around the end), NaN where
+   * its mse is above the limit; NX, NY: its normal (forward sides only) */
+  double* E = (double*)malloc(sizeof(double) * 3 * (size_t)n * n);
+  double* NX = E + (size_t)n * n; double* NY = NX + (size_t)n * n;
+  for (int a = 0; a < n; a++)
+    for (int b = 0; b < n; b++) {
+      double q[4], e, m;
+      if (a == b) { E[(size_t)a * n + b] = (double)NAN; continue; }
+      fit_line(lfps, sz, maxima[a], maxima[b], q, &e, &m);
+      E[(size_t)a * n + b] = m > prm->max_line_fit_mse ? (double)NAN : e;
+      NX[(size_t)a * n + b] = q[2]; NY[(size_t)a * n + b] = q[3];
+    }
+  for (int m0 = 0; m0 < n - 3; m0++)
+    for (int m1 = m0 + 1; m1 < n - 2; m1++) {
+      const double e01 = E[(size_t)m0 * n + m1];
+      if (e01 != e01) continue;
+      for (int m2 = m1 + 1; m2 < n - 1; m2++) {
+        const double e12 = E[(size_t)m1 * n + m2];
+        if (e12 != e12) continue;
+        const double dot = NX[(size_t)m0 * n + m1] * NX[(size_t)m1 * n + m2] + NY[(size_t)m0 * n + m1] * NY[(size_t)m1 * n + m2];
+        const int dot_ok = !(fabs(dot) > prm->cos_critical_rad), sgn_ok = !(dot > prm->cos_critical_rad);
+        for (int m3 = m2 + 1; m3 < n; m3++) {
+          const double e23 = E[(size_t)m2 * n + m3], e30 = E[(size_t)m3 * n + m0];
+          if (e23 != e23 || e30 != e30) continue;
+          const double e = e01 + e12 + e23 + e30;
+          *nadm_all += 1; *nadm_dot += dot_ok;
+          if (e < *err_all) { *err_all = e; set_all[0] = maxima[m0]; set_all[1] = maxima[m1]; set_all[2] = maxima[m2]; set_all[3] = maxima[m3]; }
+          if (sgn_ok && e < *err_sgn) { *err_sgn = e; set_sgn[0] = maxima[m0]; set_sgn[1] = maxima[m1]; set_sgn[2] = maxima[m2]; set_sgn[3] = maxima[m3]; }
+          if (dot_ok && e < *err_dot) { *err_dot = e; set_dot[0] = maxima[m0]; set_dot[1] = maxima[m1]; set_dot[2] = maxima[m2]; set_dot[3] = maxima[m3]; }
+        }
+      }
+    }
+  free(E);
+}
+
 static int quad_segment_maxima(const ato_params_t* prm, const lfp_t* lfps, int sz, int indices[4]) {
   int ksz = sz / 12 < 20 ? sz / 12 : 20;
   g_qsm_reason = 3;
+  if (g_fit_on) g_fit.ksz = ksz;
   if (ksz < 2) return 0;
   double* errs = (double*)malloc(sizeof(double) * sz);
   double* sm = (double*)malloc(sizeof(double) * sz);
@@ -493,6 +570,13 @@ static int quad_segment_maxima(const ato_params_t* prm, const lfp_t* lfps, int s
       maxima[nmaxima] = i; maxima_errs[nmaxima] = errs[i]; nmaxima++;
     }
   int ok = 0;
+  int* all_maxima = NULL;   /* the fit log's copy of the maxima before the cut (maxima_errs keeps their values) */
+  const int nmaxima_all = nmaxima;
+  if (g_fit_on) {
+    g_fit.nmaxima = nmaxima; g_fit.nkept = nmaxima; g_fit.nties = 0;
+    all_maxima = (int*)malloc(sizeof(int) * (nmaxima ? nmaxima : 1));
+    memcpy(all_maxima, maxima, sizeof(int) * nmaxima);
+  }
   if (nmaxima >= 4) {
     if (nmaxima > prm->max_nmaxima) {
       double* cp = (double*)malloc(sizeof(double) * nmaxima);
@@ -506,6 +590,10 @@ static int quad_segment_maxima(const ato_params_t* prm, const lfp_t* lfps, int s
       }
       nmaxima = out;
       free(cp);
+      if (g_fit_on) {
+        g_fit.nkept = out; g_fit.nties = 0;
+        for (int in = 0; in < nmaxima_all; in++) g_fit.nties += maxima_errs[in] == thresh;
+      }
     }
     int best[4] = {0, 0, 0, 0};
     double best_error = (double)HUGE_VALF;
@@ -536,13 +624,41 @@ static int quad_segment_maxima(const ato_params_t* prm, const lfp_t* lfps, int s
         }
       }
     }
+    if (g_fit_on) {
+      /* the same search with the dot test off: how many choices that test alone removed, and whether it decided the winner */
+      int nadm_dot = 0, nadm_all = 0, alt[4], with_dot[4], sgn[4];
+      double alt_error, dot_error, sgn_error;
+      fit_log_search(prm, lfps, sz, maxima, nmaxima, &nadm_all, &nadm_dot, &alt_error, alt, &dot_error, with_dot, &sgn_error, sgn);
+      g_fit.dot_sign_changes = (sgn_error != (double)HUGE_VALF) != (best_error != (double)HUGE_VALF) ||
+                               (best_error != (double)HUGE_VALF && memcmp(sgn, best, sizeof(sgn)) != 0);
+      /* ... and over the maxima before the cut (up to ato_fit_uncut_max of them): whether the cut decided the outcome */
+      if (nmaxima_all > prm->max_nmaxima && nmaxima_all <= ato_fit_uncut_max) {
+        int na, nd, uncut_all[4], uncut[4], uncut_sgn[4];
+        double uncut_all_error, uncut_error, uncut_sgn_error;
+        fit_log_search(prm, lfps, sz, all_maxima, nmaxima_all, &na, &nd, &uncut_all_error, uncut_all, &uncut_error, uncut, &uncut_sgn_error, uncut_sgn);
+        g_fit.cut_changes = (uncut_error != (double)HUGE_VALF) != (best_error != (double)HUGE_VALF) ||
+                            (best_error != (double)HUGE_VALF && memcmp(uncut, best, sizeof(uncut)) != 0);
+      }
+      g_fit.dot_removed = nadm_all - nadm_dot;
+      g_fit.dot_changes = (alt_error != (double)HUGE_VALF) != (best_error != (double)HUGE_VALF) ||
+                          (best_error != (double)HUGE_VALF && memcmp(alt, best, sizeof(alt)) != 0);
+      if (best_error != (double)HUGE_VALF) {
+        double weakest = (double)HUGE_VALF;
+        for (int i = 0; i < 4; i++)
+          for (int k = 0; k < nmaxima_all; k++)
+            if (all_maxima[k] == best[i] && maxima_errs[k] < weakest) weakest = maxima_errs[k];
+        g_fit.weakest_rank = 1;
+        for (int k = 0; k < nmaxima_all; k++) g_fit.weakest_rank += maxima_errs[k] > weakest;
+        g_fit.err_per_point = best_error / sz;
+      }
+    }
     if (best_error != (double)HUGE_VALF) {
       for (int i = 0; i < 4; i++) indices[i] = best[i];
       g_qsm_reason = 5;
       if (best_error / sz < prm->max_line_fit_mse) ok = 1;
     }
   }
-  free(errs); free(maxima); free(maxima_errs);
+  free(errs); free(maxima); free(maxima_errs); free(all_maxima);
   return ok;
 }
 
@@ -624,6 +740,7 @@ static int fit_quad(const ato_params_t* prm, const uint8_t* gray, int w, int h, 
     sgx += gx; sgy += gy;
   }
   const int sz_in = sz;
+  ato_fit_begin(quad->key, sz_in);
   if ((xmax - xmin) * (ymax - ymin) < tag_width) { ATO_STAT(0, sz_in); return 0; }
   double cxd = (xmin + xmax) * 0.5 + 0.05118, cyd = (ymin + ymax) * 0.5 + -0.028581;
   /* CANONICAL: dot = sum(dx*gx + dy*gy) evaluated exactly (upstream: float accumulation in hash order) */
@@ -741,6 +858,7 @@ static int fit_quad(const ato_params_t* prm, const uint8_t* gray, int w, int h, 
       if ((keys[i] >> 4) != (keys[i - 1] >> 4)) keys[outpos++] = keys[i];   /* bits 4..31 = (y,x) */
     sz = outpos;
   }
+  if (g_fit_on) g_fit.points = sz;
   if (sz < 24) { free(keys); ATO_STAT(2, sz_in); return 0; }
 
   /* cumulative weighted moments (compute_lfps).  Per-point terms are formed exactly as upstream does
@@ -849,6 +967,7 @@ static int fit_quad(const ato_params_t* prm, const uint8_t* gray, int w, int h, 
     double B0 = -lines[i][0] + lines[(i + 1) & 3][0];
     double B1 = -lines[i][1] + lines[(i + 1) & 3][1];
     double det = A00 * A11 - A10 * A01;
+    if (g_fit_on && !(fabs(det) >= g_fit.min_abs_det)) g_fit.min_abs_det = fabs(det);
     if (fabs(det) < 0.001) { ATO_STAT(7, sz_in); goto finish; }
     double W00 = A11 / det, W01 = -A01 / det;
     double L0 = W00 * B0 + W01 * B1;
@@ -875,7 +994,24 @@ static int fit_quad(const ato_params_t* prm, const uint8_t* gray, int w, int h, 
     }
     p = (length[0] + length[1] + length[2]) / 2;
     area += sqrt(p * (p - length[0]) * (p - length[1]) * (p - length[2]));
+    if (g_fit_on) g_fit.area = area;
     if (area < 0.95 * tag_width * tag_width) { ATO_STAT(8, sz_in); goto finish; }
+  }
+  if (g_fit_on) {   /* all four corners, whichever the loop below leaves at */
+    int angle_fails = 0;
+    g_fit.winding_fails = 0;
+    for (int i = 0; i < 4; i++) {
+      int i0 = i, i1 = (i + 1) & 3, i2 = (i + 2) & 3;
+      double dx1 = (double)(quad->p[i1][0] - quad->p[i0][0]), dy1 = (double)(quad->p[i1][1] - quad->p[i0][1]);
+      double dx2 = (double)(quad->p[i2][0] - quad->p[i1][0]), dy2 = (double)(quad->p[i2][1] - quad->p[i1][1]);
+      double c = (dx1 * dx2 + dy1 * dy2) / sqrt((dx1 * dx1 + dy1 * dy1) * (dx2 * dx2 + dy2 * dy2));
+      if (!(c >= g_fit.min_cos)) g_fit.min_cos = c;
+      if (!(c <= g_fit.max_cos)) g_fit.max_cos = c;
+      if (!(fabs(c) <= g_fit.max_abs_cos)) g_fit.max_abs_cos = fabs(c);
+      angle_fails += c > prm->cos_critical_rad || c < -prm->cos_critical_rad;
+      g_fit.winding_fails += dx1 * dy2 < dy1 * dx2;
+    }
+    g_fit.winding_only = g_fit.winding_fails > 0 && angle_fails == 0;
   }
   for (int i = 0; i < 4; i++) {
     int i0 = i, i1 = (i + 1) & 3, i2 = (i + 2) & 3;

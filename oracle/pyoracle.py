@@ -240,11 +240,40 @@ def reconcile(records, params=None):
     return np.frombuffer(bytes(buf), dtype=RECORD_DTYPE)[:nk].copy()
 
 
-def detect(img, families=("tag36h11",), params=None, max_det=1024, want_dump=False):
+# one record of the quad fit's per-cluster log (apriltag_oracle.c: ato_fit_rec_t; FIT_REASONS[reason] names the exit as ato_stats counts it)
+FIT_LOG_DTYPE = np.dtype([("key", "<u8"), ("points_in", "<i4"), ("points", "<i4"), ("ksz", "<i4"), ("reason", "<i4"), ("nmaxima", "<i4"),
+                          ("nkept", "<i4"), ("nties", "<i4"), ("weakest_rank", "<i4"), ("dot_removed", "<i4"), ("dot_changes", "<i4"),
+                          ("winding_fails", "<i4"), ("winding_only", "<i4"), ("cut_changes", "<i4"), ("dot_sign_changes", "<i4"),
+                          ("err_per_point", "<f8"), ("min_abs_det", "<f8"),
+                          ("area", "<f8"), ("min_cos", "<f8"), ("max_cos", "<f8"), ("max_abs_cos", "<f8")])
+FIT_REASONS = ("box", "border direction", "fewer than 24 after duplicate removal", "fewer than 4 maxima", "no admissible corner choice",
+               "total error", "final line mse", "degenerate intersection", "area", "angles / winding", "accepted")
+
+
+def detect(img, families=("tag36h11",), params=None, max_det=1024, want_dump=False, want_fit_log=False, fit_log_uncut_max=48):
     """Runs the full CPU restatement on one mono8 frame.
 
-    Returns (detections, dump) where dump is None or a dict of numpy arrays (copies).
+    Returns (detections, dump) where dump is None or a dict of numpy arrays (copies); with want_fit_log
+    (detections, dump, log): one FIT_LOG_DTYPE record per cluster that entered the quad fit, in cluster order.
+    The log is a global of the library: not for concurrent calls.  fit_log_uncut_max: up to how many maxima the log repeats the corner
+    search without the cut (cut_changes); hundreds take seconds.
     """
+    if want_fit_log:
+        cap = 1 << 16
+        buf = np.zeros(cap, dtype=FIT_LOG_DTYPE)
+        C.c_void_p.in_dll(lib(), "ato_fit_log").value = buf.ctypes.data
+        C.c_int.in_dll(lib(), "ato_fit_n").value = 0
+        C.c_int.in_dll(lib(), "ato_fit_cap").value = cap
+        C.c_int.in_dll(lib(), "ato_fit_uncut_max").value = int(fit_log_uncut_max)
+        try:
+            dets, d = detect(img, families, params, max_det, want_dump)
+        finally:
+            C.c_int.in_dll(lib(), "ato_fit_cap").value = 0
+            C.c_int.in_dll(lib(), "ato_fit_uncut_max").value = 48
+            C.c_void_p.in_dll(lib(), "ato_fit_log").value = None
+        n = C.c_int.in_dll(lib(), "ato_fit_n").value
+        assert n < cap, "fit log full"
+        return dets, d, buf[:n].copy()
     img = np.asarray(img, dtype=np.uint8)
     assert img.ndim == 2 and img.strides[1] == 1
     h, w = img.shape
