@@ -34,6 +34,7 @@
 #include "kernels_threshold.h"
 #include "kernels_undistort.h"
 #include "launch_plan.h"
+#include "post_plan.h"
 
 static_assert(sizeof(DetRec) == sizeof(amdAprilTagsDetectionEx_t), "DetRec must match the public record");
 static_assert(sizeof(QuadRec) == 48, "QuadRec layout");
@@ -257,7 +258,16 @@ struct amdAprilTagsDetector_st {
   int path_mode = AMDAT_PATH_AUTO;
   int last_path = AMDAT_PATH_AUTO;   // the set the last submission ran (amdAprilTagsDebugLastSubmissionPath)
   float stage_ms[AMDAT_NUM_STAGES] = {};
-  uint32_t last_n = 0;
+  // The stages behind k_reconcile (post_plan.h).  `post` is what the setters set, and they refuse while a
+  // submission is in flight; `last` is what the last submission ran with, assigned once by begin_batch and emptied by the entry
+  // points that never run the back end: all that the getters, the stamp check and the launches themselves read.
+  PostMode post;
+  struct LastSubmission {
+    uint32_t n = 0, ostride = 0;   // frames, and record slots per frame
+    PostMode post;
+    bool rectified = false;        // it formed the rectified plane (AMDAT_DBG_RECTIFIED)
+    bool resized = false;          // it resized (AMDAT_DBG_RESIZED)
+  } last;
   // quad_sigma (amdAprilTagsSetQuadSigma): the filter runs while qs_ksz > 1; qs.tk are the taps of the k_quad_sigma<qs_kh> instance
   uint32_t qs_ksz = 1;
   int qs_kh = 0;
@@ -274,45 +284,28 @@ struct amdAprilTagsDetector_st {
   HostBuf<FrontDesc> h_front;                           // pinned, one per batch slot: k_prologue uploads them with the frame descriptors
   DevBuf<FrontDesc> d_front;
   std::vector<amdAprilTagsImageInput_t> front_imgs;     // the plane's slots as the mono8 images of the submission (fill_front)
-  bool last_rectified = false;                          // the last submission formed the rectified plane (AMDAT_DBG_RECTIFIED)
-  bool last_resized = false;                            // the last submission resized (AMDAT_DBG_RESIZED)
-  // amdAprilTagsSetBundles: k_bundle_pose runs behind k_reconcile while nbundles > 0.  The device layout (bundle_layout.h) is allocated
-  // once, at its largest size, by the first call that turns the feature on, so that a later layout changes no launch argument
-  uint32_t nbundles = 0;                                // 0: off
-  uint32_t last_nbundles = 0;                           // of the last submission (amdAprilTagsGetBundlePoses)
+  // What the post stages own, each set allocated by the first call that turns its stage on -- the layouts at their largest size,
+  // the iteration count and sigma^2 in device memory -- so that a later value changes no launch argument.
+  // amdAprilTagsSetBundles (bundle_layout.h):
   DevBuf<BundleHeadDev> d_bundle_head;
   DevBuf<BundleMemberDev> d_bundle_members;             // AMDAT_MAX_BUNDLE_MEMBERS
   DevBuf<uint16_t> d_bundle_table;                      // one entry per code of every family of the handle
   HostBuf<BundlePoseRec> h_bposes;                      // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_pose writes frame * nbundles + bundle
-  // amdAprilTagsSetBundlesEx: k_bundle_rigid runs behind k_reconcile while nrigid > 0 (then nbundles is 0: one kind is on at a time).  The
-  // device layout (rigid_layout.h) is allocated once, at its largest size, by the first call that turns the mode on
-  uint32_t nrigid = 0;                                  // 0: off
-  uint32_t last_nrigid = 0;                             // of the last submission (amdAprilTagsGetBundlePosesEx)
+  // amdAprilTagsSetBundlesEx (rigid_layout.h):
   DevBuf<RigidHeadDev> d_rigid_head;
   DevBuf<RigidMemberDev> d_rigid_members;               // RIGID_MAX_MEMBERS
   DevBuf<uint16_t> d_rigid_table;                       // one entry per code of every family of the handle
   HostBuf<RigidPoseRec> h_xposes;                       // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_rigid writes frame * nrigid + bundle
-  // amdAprilTagsSetPoseRefinement: k_pose_refine runs behind k_reconcile while pose_iterations > 0.  The count lives in device memory
-  // (d_pose_cfg[0]), so that changing it changes no launch argument; both buffers are allocated by the first call that turns the mode on
-  uint32_t pose_iterations = 0;                         // 0: off
-  bool last_pose_refined = false;                       // the last submission refined (amdAprilTagsGetRefinedPoses) ...
-  uint32_t last_ostride = 0;                            // ... with this many record slots per frame (finish_once reads it too)
-  DevBuf<uint32_t> d_pose_cfg;
+  // amdAprilTagsSetPoseRefinement:
+  DevBuf<uint32_t> d_pose_cfg;                          // [0]: the iteration count
   HostBuf<PoseRefineRec> h_rposes;                      // pinned, max_batch x dcap: k_pose_refine writes frame * ostride + record, as k_reconcile does
-  // amdAprilTagsSetPoseCovariance: while pose_cov_sigma > 0 the two launches above run as their covariance instances and write these
-  // blocks, which are sized and owned as h_rposes and h_xposes are.  sigma^2 lives in device memory (d_cov_cfg[0]), so that changing
-  // it changes no launch argument; all three are allocated by the first call that turns the mode on
-  double pose_cov_sigma = 0.0;                          // 0: off
-  bool last_pose_cov = false;                           // the last submission ran the mode
-  DevBuf<double> d_cov_cfg;
+  // amdAprilTagsSetPoseCovariance:
+  DevBuf<double> d_cov_cfg;                             // [0]: sigma^2
   HostBuf<PoseCovRec> h_rcovs;                          // pinned, max_batch x dcap, beside h_rposes
   HostBuf<PoseCovRec> h_xcovs;                          // pinned, max_batch x AMDAT_MAX_BUNDLES, beside h_xposes
-  // amdAprilTagsSetCornerUndistortion: k_undistort_records runs behind k_reconcile while undist_models is not empty, and the bundle,
-  // rigid and refinement launches then read d_dets_u in d_dets' place.  Frame i of a submission takes undist_models[i % size]; the
-  // slot's camera travels through the pinned block h_ucams, which k_prologue uploads with the frame descriptors.  All four buffers are
-  // allocated by the first call that turns the mode on
-  std::vector<amdAprilTagsCameraModelEx_t> undist_models;   // empty: off
-  bool last_undistorted = false;                        // the last submission ran the mode (amdAprilTagsGetUndistortedDetections)
+  // amdAprilTagsSetCornerUndistortion: frame i of a submission takes undist_models[i % size]; the slot's camera travels through the
+  // pinned block h_ucams, which k_prologue uploads with the frame descriptors
+  std::vector<amdAprilTagsCameraModelEx_t> undist_models;   // post.nundist of them
   HostBuf<UndistortCam> h_ucams;                        // pinned, one per batch slot
   DevBuf<UndistortCam> d_ucams;
   DevBuf<DetRec> d_dets_u;                              // max_batch x dcap, laid out and indexed as d_dets
@@ -545,6 +538,9 @@ static bool host_alloc(amdAprilTagsDetector_st* D, HostAlloc& b, size_t bytes) {
   D->host_owned.push_back(&b);
   return true;
 }
+// First-use allocation: what a mode needs is allocated by the first call that turns it on, and kept.
+static bool ensure_dev(amdAprilTagsDetector_st* D, DevAlloc& b, size_t bytes) { return b.p || dev_alloc(D, b, bytes); }
+static bool ensure_host(amdAprilTagsDetector_st* D, HostAlloc& b, size_t bytes) { return b.p || host_alloc(D, b, bytes); }
 
 static void free_all(amdAprilTagsDetector_st* D) {
   for (auto& g : D->graphs) if (g.exec) hipGraphExecDestroy(g.exec);
@@ -963,8 +959,7 @@ static uint8_t* conv_slot(const amdAprilTagsDetector_st* D, uint32_t i) { return
 static int ensure_front_buffers(amdAprilTagsDetector_st* D) {
   const size_t B = D->cfg.max_batch;
   { const int rc = ensure_conv_plane(D); if (rc) return rc; }
-  if (!D->d_front && !dev_alloc(D, D->d_front, B * sizeof(FrontDesc))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_front && !host_alloc(D, D->h_front, B * sizeof(FrontDesc))) return AMDAT_OUT_OF_MEMORY;
+  if (!ensure_dev(D, D->d_front, B * sizeof(FrontDesc)) || !ensure_host(D, D->h_front, B * sizeof(FrontDesc))) return AMDAT_OUT_OF_MEMORY;
   D->front_imgs.resize(B);
   return AMDAT_SUCCESS;
 }
@@ -1026,7 +1021,7 @@ int amdAprilTagsSetRectification(amdAprilTagsHandle handle, uint32_t ncams, cons
 
 int amdAprilTagsSetRectificationEx(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams) {
   if (!handle || handle->inflight.active || (ncams && !cams) || ncams > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
-  if (ncams && !handle->undist_models.empty()) return AMDAT_INVALID_ARGUMENT;   // (raw-frame mode is on: a frame is resampled or read raw, not both)
+  if (ncams && handle->post.nundist) return AMDAT_INVALID_ARGUMENT;   // (raw-frame mode is on: a frame is resampled or read raw, not both)
   bool general = false;
   for (uint32_t c = 0; c < ncams; c++) {
     if (!camera_model_ok(cams[c])) return AMDAT_INVALID_ARGUMENT;
@@ -1060,88 +1055,58 @@ int amdAprilTagsSetResize(amdAprilTagsHandle handle, uint32_t nsizes, const amdA
   return AMDAT_SUCCESS;
 }
 
-// What the first call that turns bundles on allocates: the device layout at its largest size and the pinned record block.
-static int ensure_bundle_buffers(amdAprilTagsDetector_st* D, size_t table_entries) {
-  if (!D->d_bundle_head && !dev_alloc(D, D->d_bundle_head, sizeof(BundleHeadDev))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->d_bundle_members && !dev_alloc(D, D->d_bundle_members, AMDAT_MAX_BUNDLE_MEMBERS * sizeof(BundleMemberDev))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->d_bundle_table && !dev_alloc(D, D->d_bundle_table, table_entries * sizeof(uint16_t))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_bposes && !host_alloc(D, D->h_bposes, (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(BundlePoseRec))) return AMDAT_OUT_OF_MEMORY;
+// ---- the stages behind k_reconcile (post_plan.h) -----------------------------------------------------------------------------
+static_assert(POST_UD_WAVES == UD_WAVES_PER_FRAME && POST_PR_RECORDS_PER_WAVE == PR_RECORDS_PER_WAVE, "post_plan.h states the kernels' grids");
+
+// Takes a setter's request into the mode.  The graphs are retired if and only if the request changes a stage's on / off bit: they
+// were captured with or without each launch, and with the one or the other instance and record list.
+static void set_post_mode(amdAprilTagsDetector_st* D, PostSetting what, double value) {
+  const PostMode next = post_apply(D->post, what, value);
+  if (post_graph_key(next) != post_graph_key(D->post)) drop_graphs(D);
+  D->post = next;
+}
+
+// The planar and the rigid bundle setter.  Where it turns its kind on, the first call allocates the device layout at its largest
+// size and the pinned record block; every such call uploads head, members and table and waits.
+extern "C++" {   // (a template, inside the C ABI block)
+template <class Layout, class Bundle, class Head, class Member, class Rec>
+static int set_bundle_layout(amdAprilTagsDetector_st* D, PostSetting kind, uint32_t nbundles, const Bundle* bundles,
+                             int (*build)(uint32_t, const uint32_t*, uint32_t, const Bundle*, Layout*), DevBuf<Head>& d_head,
+                             DevBuf<Member>& d_members, size_t max_members, DevBuf<uint16_t>& d_table, HostBuf<Rec>& h_poses) {
+  uint32_t ncodes[AT_MAX_FAMILIES] = {};
+  for (int i = 0; i < D->P.nfam; i++) ncodes[i] = D->P.fam[i].ncodes;
+  Layout L;
+  { const int rc = build((uint32_t)D->P.nfam, ncodes, nbundles, bundles, &L); if (rc) return rc; }
+  DeviceGuard guard(D->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  if (nbundles > 0) {
+    if (!ensure_dev(D, d_head, sizeof(Head)) || !ensure_dev(D, d_members, max_members * sizeof(Member)) ||
+        !ensure_dev(D, d_table, L.table.size() * sizeof(uint16_t)) ||
+        !ensure_host(D, h_poses, (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(Rec)))
+      return AMDAT_OUT_OF_MEMORY;
+    // (no submission is in flight: nothing reads the layout; `L` is pageable, so the copies are waited for before it goes)
+    const hipStream_t s = D->own_stream;
+    HIP_TRY(hipMemcpyAsync(d_head, &L.head, sizeof(L.head), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_members, L.members.data(), L.members.size() * sizeof(Member), hipMemcpyHostToDevice, s));
+    if (!L.table.empty()) HIP_TRY(hipMemcpyAsync(d_table, L.table.data(), L.table.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  set_post_mode(D, kind, nbundles);
   return AMDAT_SUCCESS;
 }
+}  // extern "C++"
 
 int amdAprilTagsSetBundles(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundle_t* bundles) {
   if (!handle || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
-  uint32_t ncodes[AT_MAX_FAMILIES] = {};
-  for (int i = 0; i < handle->P.nfam; i++) ncodes[i] = handle->P.fam[i].ncodes;
-  BundleLayout L;
-  { const int rc = bundle_layout_build((uint32_t)handle->P.nfam, ncodes, nbundles, bundles, &L); if (rc) return rc; }
-  const bool on = nbundles > 0;
-  DeviceGuard guard(handle->device);
-  if (!guard.ok) return AMDAT_HIP_ERROR;
-  if (on) {
-    { const int rc = ensure_bundle_buffers(handle, L.table.size()); if (rc) return rc; }
-    // (no submission is in flight: nothing reads the layout; `L` is pageable, so the copies are waited for before it goes)
-    const hipStream_t s = handle->own_stream;
-    HIP_TRY(hipMemcpyAsync(handle->d_bundle_head, &L.head, sizeof(L.head), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(handle->d_bundle_members, L.members.data(), L.members.size() * sizeof(BundleMemberDev), hipMemcpyHostToDevice, s));
-    if (!L.table.empty()) HIP_TRY(hipMemcpyAsync(handle->d_bundle_table, L.table.data(), L.table.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  // captured with or without the bundle launch, or with the other kind's (turning this kind on turns the rigid kind off); the layout
-  // itself lives in device memory
-  if (on != (handle->nbundles > 0) || (on && handle->nrigid > 0)) drop_graphs(handle);
-  handle->nbundles = nbundles;
-  if (on) handle->nrigid = 0;
-  return AMDAT_SUCCESS;
-}
-
-int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose_t* out, uint32_t nframes) {
-  if (!handle || !out || handle->inflight.active || handle->last_nbundles == 0 || nframes > handle->last_n) return AMDAT_INVALID_ARGUMENT;
-  const size_t n = (size_t)nframes * handle->last_nbundles;
-  for (size_t i = 0; i < n; i++) out[i] = handle->h_bposes[i].pose;
-  return AMDAT_SUCCESS;
-}
-
-// What the first call that turns rigid bundles on allocates: the device layout at its largest size and the pinned record block.
-static int ensure_rigid_buffers(amdAprilTagsDetector_st* D, size_t table_entries) {
-  if (!D->d_rigid_head && !dev_alloc(D, D->d_rigid_head, sizeof(RigidHeadDev))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->d_rigid_members && !dev_alloc(D, D->d_rigid_members, RIGID_MAX_MEMBERS * sizeof(RigidMemberDev))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->d_rigid_table && !dev_alloc(D, D->d_rigid_table, table_entries * sizeof(uint16_t))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_xposes && !host_alloc(D, D->h_xposes, (size_t)D->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(RigidPoseRec))) return AMDAT_OUT_OF_MEMORY;
-  return AMDAT_SUCCESS;
+  return set_bundle_layout(handle, POST_SET_PLANAR, nbundles, bundles, bundle_layout_build, handle->d_bundle_head, handle->d_bundle_members,
+                           AMDAT_MAX_BUNDLE_MEMBERS, handle->d_bundle_table, handle->h_bposes);
 }
 
 int amdAprilTagsSetBundlesEx(amdAprilTagsHandle handle, uint32_t nbundles, const amdAprilTagsBundleEx_t* bundles) {
   if (!handle || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   static_assert(AMDAT_MAX_RIGID_BUNDLE_MEMBERS == RG_SLOTS, "the header's bound is the kernel's: one lane holds one tag");
-  uint32_t ncodes[AT_MAX_FAMILIES] = {};
-  for (int i = 0; i < handle->P.nfam; i++) ncodes[i] = handle->P.fam[i].ncodes;
-  RigidLayout L;
-  { const int rc = rigid_layout_build((uint32_t)handle->P.nfam, ncodes, nbundles, bundles, &L); if (rc) return rc; }
-  const bool on = nbundles > 0;
-  DeviceGuard guard(handle->device);
-  if (!guard.ok) return AMDAT_HIP_ERROR;
-  if (on) {
-    { const int rc = ensure_rigid_buffers(handle, L.table.size()); if (rc) return rc; }
-    // (no submission is in flight: nothing reads the layout; `L` is pageable, so the copies are waited for before it goes)
-    const hipStream_t s = handle->own_stream;
-    HIP_TRY(hipMemcpyAsync(handle->d_rigid_head, &L.head, sizeof(L.head), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(handle->d_rigid_members, L.members.data(), L.members.size() * sizeof(RigidMemberDev), hipMemcpyHostToDevice, s));
-    if (!L.table.empty()) HIP_TRY(hipMemcpyAsync(handle->d_rigid_table, L.table.data(), L.table.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  // captured with or without the launch, or with the planar kind's (turning this kind on turns the planar kind off)
-  if (on != (handle->nrigid > 0) || (on && handle->nbundles > 0)) drop_graphs(handle);
-  handle->nrigid = nbundles;
-  if (on) handle->nbundles = 0;
-  return AMDAT_SUCCESS;
-}
-
-int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePoseEx_t* out, uint32_t nframes) {
-  if (!handle || !out || handle->inflight.active || handle->last_nrigid == 0 || nframes > handle->last_n) return AMDAT_INVALID_ARGUMENT;
-  const size_t n = (size_t)nframes * handle->last_nrigid;
-  for (size_t i = 0; i < n; i++) out[i] = handle->h_xposes[i].pose;
-  return AMDAT_SUCCESS;
+  return set_bundle_layout(handle, POST_SET_RIGID, nbundles, bundles, rigid_layout_build, handle->d_rigid_head, handle->d_rigid_members,
+                           RIGID_MAX_MEMBERS, handle->d_rigid_table, handle->h_xposes);
 }
 
 // The kernel's parameters of a camera model (undistort.h): K, D, R and Knew as they are given.
@@ -1159,11 +1124,9 @@ static UndistortCam undistort_cam(const amdAprilTagsCameraModelEx_t& m) {
 static int ensure_undistort_buffers(amdAprilTagsDetector_st* D) {
   const size_t B = D->cfg.max_batch;
   static_assert(sizeof(UndistortCam) % 4 == 0, "k_prologue copies words");
-  if (!D->h_ucams && !host_alloc(D, D->h_ucams, B * sizeof(UndistortCam))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->d_ucams && !dev_alloc(D, D->d_ucams, B * sizeof(UndistortCam))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->d_dets_u && !dev_alloc(D, D->d_dets_u, B * (size_t)D->P.dcap * sizeof(DetRec))) return AMDAT_OUT_OF_MEMORY;
-  if (!D->h_udets && !host_alloc(D, D->h_udets, B * (size_t)D->P.dcap * sizeof(UndistortRec))) return AMDAT_OUT_OF_MEMORY;
-  return AMDAT_SUCCESS;
+  return ensure_host(D, D->h_ucams, B * sizeof(UndistortCam)) && ensure_dev(D, D->d_ucams, B * sizeof(UndistortCam)) &&
+         ensure_dev(D, D->d_dets_u, B * (size_t)D->P.dcap * sizeof(DetRec)) &&
+         ensure_host(D, D->h_udets, B * (size_t)D->P.dcap * sizeof(UndistortRec)) ? AMDAT_SUCCESS : AMDAT_OUT_OF_MEMORY;
 }
 
 int amdAprilTagsSetCornerUndistortion(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsCameraModelEx_t* cams) {
@@ -1172,106 +1135,123 @@ int amdAprilTagsSetCornerUndistortion(amdAprilTagsHandle handle, uint32_t ncams,
   for (uint32_t c = 0; c < ncams; c++)
     if (!camera_model_ok(cams[c])) return AMDAT_INVALID_ARGUMENT;
   const bool on = ncams > 0;
-  if (on != !handle->undist_models.empty()) {
+  if (on != (handle->post.nundist > 0)) {
     DeviceGuard guard(handle->device);
     if (!guard.ok) return AMDAT_HIP_ERROR;
     if (on) { const int rc = ensure_undistort_buffers(handle); if (rc) return rc; }
-    drop_graphs(handle);   // captured with or without the launch, and with the pose launches on the one or the other record list; the models travel through the descriptors
   }
+  set_post_mode(handle, POST_SET_UNDISTORT, ncams);   // (the models travel through the descriptors)
   handle->undist_models.assign(cams, cams + ncams);
   return AMDAT_SUCCESS;
 }
 
-int amdAprilTagsGetUndistortedDetections(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsUndistortedDetection_t* out, uint32_t capacity, uint32_t* n) {
-  if (!handle || !out || !n || handle->inflight.active || !handle->last_undistorted || frame >= handle->last_n) return AMDAT_INVALID_ARGUMENT;
-  uint32_t k = handle->h_counters[frame].nout;
-  if (k > handle->last_ostride) k = handle->last_ostride;
-  *n = k;
-  if (capacity < k) return AMDAT_INVALID_ARGUMENT;
-  for (uint32_t i = 0; i < k; i++) out[i] = handle->h_udets[(size_t)frame * handle->last_ostride + i].det;
+// One value of a mode that lives in device memory.  (No submission is in flight: nothing reads it; the source is pageable, so the
+// copy is waited for before it goes.)
+static int upload_value(amdAprilTagsDetector_st* D, void* dst, const void* value, size_t bytes) {
+  HIP_TRY(hipMemcpyAsync(dst, value, bytes, hipMemcpyHostToDevice, D->own_stream));
+  HIP_TRY(hipStreamSynchronize(D->own_stream));
   return AMDAT_SUCCESS;
-}
-
-// Record i of `frame` of the last submission was refined from an invalid undistorted twin.
-static bool undistorted_invalid(const amdAprilTagsDetector_st* D, uint32_t frame, uint32_t i) {
-  return D->last_undistorted && D->h_udets[(size_t)frame * D->last_ostride + i].det.status != AMDAT_UNDISTORT_OK;
 }
 
 int amdAprilTagsSetPoseRefinement(amdAprilTagsHandle handle, uint32_t iterations) {
   if (!handle || iterations > AMDAT_MAX_POSE_ITERATIONS || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   static_assert(AMDAT_MAX_POSE_ITERATIONS == PR_MAX_ITERATIONS, "the header's bound is the kernel's");
-  const bool on = iterations > 0;
-  if (on) {
+  if (iterations > 0) {
     DeviceGuard guard(handle->device);
     if (!guard.ok) return AMDAT_HIP_ERROR;
-    if (!handle->d_pose_cfg && !dev_alloc(handle, handle->d_pose_cfg, 64)) return AMDAT_OUT_OF_MEMORY;
-    if (!handle->h_rposes && !host_alloc(handle, handle->h_rposes, (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseRefineRec)))
+    if (!ensure_dev(handle, handle->d_pose_cfg, 64) ||
+        !ensure_host(handle, handle->h_rposes, (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseRefineRec)))
       return AMDAT_OUT_OF_MEMORY;
-    // (no submission is in flight: nothing reads the count; it is pageable, so the copy is waited for before it goes)
-    const hipStream_t s = handle->own_stream;
-    HIP_TRY(hipMemcpyAsync(handle->d_pose_cfg, &iterations, sizeof(iterations), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    const int rc = upload_value(handle, handle->d_pose_cfg, &iterations, sizeof(iterations));
+    if (rc) return rc;
   }
-  if (on != (handle->pose_iterations > 0)) drop_graphs(handle);   // captured with or without the launch; the count itself lives in device memory
-  handle->pose_iterations = iterations;
-  return AMDAT_SUCCESS;
-}
-
-int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsRefinedPose_t* out, uint32_t capacity, uint32_t* n) {
-  if (!handle || !out || !n || handle->inflight.active || !handle->last_pose_refined || frame >= handle->last_n) return AMDAT_INVALID_ARGUMENT;
-  uint32_t k = handle->h_counters[frame].nout;
-  if (k > handle->last_ostride) k = handle->last_ostride;
-  *n = k;
-  if (capacity < k) return AMDAT_INVALID_ARGUMENT;
-  for (uint32_t i = 0; i < k; i++) {
-    out[i] = handle->h_rposes[(size_t)frame * handle->last_ostride + i].pose;
-    if (undistorted_invalid(handle, frame, i)) { out[i] = {}; out[i].status = AMDAT_POSE_DEGENERATE; }   // (section 7h: nothing of an invalid twin is handed out)
-  }
+  set_post_mode(handle, POST_SET_REFINE, iterations);
   return AMDAT_SUCCESS;
 }
 
 int amdAprilTagsSetPoseCovariance(amdAprilTagsHandle handle, double corner_sigma_px) {
   if (!handle || !std::isfinite(corner_sigma_px) || corner_sigma_px < 0.0 || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
-  const bool on = corner_sigma_px > 0.0;
-  if (on) {
+  if (corner_sigma_px > 0.0) {
     DeviceGuard guard(handle->device);
     if (!guard.ok) return AMDAT_HIP_ERROR;
-    if (!handle->d_cov_cfg && !dev_alloc(handle, handle->d_cov_cfg, 64)) return AMDAT_OUT_OF_MEMORY;
-    if (!handle->h_rcovs && !host_alloc(handle, handle->h_rcovs, (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseCovRec)))
+    if (!ensure_dev(handle, handle->d_cov_cfg, 64) ||
+        !ensure_host(handle, handle->h_rcovs, (size_t)handle->cfg.max_batch * handle->P.dcap * sizeof(PoseCovRec)) ||
+        !ensure_host(handle, handle->h_xcovs, (size_t)handle->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(PoseCovRec)))
       return AMDAT_OUT_OF_MEMORY;
-    if (!handle->h_xcovs && !host_alloc(handle, handle->h_xcovs, (size_t)handle->cfg.max_batch * AMDAT_MAX_BUNDLES * sizeof(PoseCovRec)))
-      return AMDAT_OUT_OF_MEMORY;
-    // (no submission is in flight: nothing reads the value; it is pageable, so the copy is waited for before it goes)
     const double sigma2 = corner_sigma_px * corner_sigma_px;
-    const hipStream_t s = handle->own_stream;
-    HIP_TRY(hipMemcpyAsync(handle->d_cov_cfg, &sigma2, sizeof(sigma2), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    const int rc = upload_value(handle, handle->d_cov_cfg, &sigma2, sizeof(sigma2));
+    if (rc) return rc;
   }
-  if (on != (handle->pose_cov_sigma > 0.0)) drop_graphs(handle);   // captured with the one or the other instance; sigma^2 itself lives in device memory
-  handle->pose_cov_sigma = corner_sigma_px;
+  set_post_mode(handle, POST_SET_COV, corner_sigma_px);
   return AMDAT_SUCCESS;
 }
 
-int amdAprilTagsGetRefinedPoseCovariances(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsPoseCovariance_t* out, uint32_t capacity, uint32_t* n) {
-  if (!handle || !out || !n || handle->inflight.active || !handle->last_pose_refined || !handle->last_pose_cov || frame >= handle->last_n)
-    return AMDAT_INVALID_ARGUMENT;
-  uint32_t k = handle->h_counters[frame].nout;
-  if (k > handle->last_ostride) k = handle->last_ostride;
+// Record i of `frame` of the last submission was refined from an invalid undistorted twin.
+static bool undistorted_invalid(const amdAprilTagsDetector_st* D, uint32_t frame, uint32_t i) {
+  return D->last.post.nundist && D->h_udets[(size_t)frame * D->last.ostride + i].det.status != AMDAT_UNDISTORT_OK;
+}
+
+// The per-frame getters: `field` of the first min(nout, ostride) records of `frame` in a block laid out as k_reconcile's, where
+// the last submission ran the stages `stages` (post_graph_key bits).  `invalid` rewrites what comes of an invalid twin (section 7h:
+// nothing of it is handed out).
+extern "C++" {   // (templates, inside the C ABI block)
+template <class Rec, class Out, class Invalid>
+static int get_frame_records(amdAprilTagsDetector_st* D, uint32_t stages, const HostBuf<Rec>& block, Out Rec::*field, uint32_t frame,
+                             Out* out, uint32_t capacity, uint32_t* n, Invalid invalid) {
+  if (!out || !n || D->inflight.active || (post_graph_key(D->last.post) & stages) != stages || frame >= D->last.n) return AMDAT_INVALID_ARGUMENT;
+  uint32_t k = D->h_counters[frame].nout;
+  if (k > D->last.ostride) k = D->last.ostride;
   *n = k;
   if (capacity < k) return AMDAT_INVALID_ARGUMENT;
+  const Rec* const recs = block + (size_t)frame * D->last.ostride;
   for (uint32_t i = 0; i < k; i++) {
-    out[i] = handle->h_rcovs[(size_t)frame * handle->last_ostride + i].c;
-    if (undistorted_invalid(handle, frame, i)) out[i] = {};   // (section 7h: all zero, valid = 0)
+    out[i] = recs[i].*field;
+    if (undistorted_invalid(D, frame, i)) invalid(out[i]);
   }
   return AMDAT_SUCCESS;
+}
+// The per-bundle getters: `field` of nframes x bundles records, bundles being the last submission's count of the one kind.
+template <class Rec, class Out>
+static int get_bundle_records(amdAprilTagsDetector_st* D, uint32_t stages, uint32_t PostMode::*count, const HostBuf<Rec>& block,
+                              Out Rec::*field, Out* out, uint32_t nframes) {
+  if (!out || D->inflight.active || (post_graph_key(D->last.post) & stages) != stages || nframes > D->last.n) return AMDAT_INVALID_ARGUMENT;
+  const size_t n = (size_t)nframes * D->last.post.*count;
+  for (size_t i = 0; i < n; i++) out[i] = block[i].*field;
+  return AMDAT_SUCCESS;
+}
+}  // extern "C++"
+
+int amdAprilTagsGetBundlePoses(amdAprilTagsHandle handle, amdAprilTagsBundlePose_t* out, uint32_t nframes) {
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_bundle_records(handle, POST_PLANAR, &PostMode::nbundles, handle->h_bposes, &BundlePoseRec::pose, out, nframes);
+}
+
+int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePoseEx_t* out, uint32_t nframes) {
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_bundle_records(handle, POST_RIGID, &PostMode::nrigid, handle->h_xposes, &RigidPoseRec::pose, out, nframes);
 }
 
 int amdAprilTagsGetBundlePoseCovariancesEx(amdAprilTagsHandle handle, amdAprilTagsPoseCovariance_t* out, uint32_t nframes) {
-  if (!handle || !out || handle->inflight.active || handle->last_nrigid == 0 || !handle->last_pose_cov || nframes > handle->last_n)
-    return AMDAT_INVALID_ARGUMENT;
-  const size_t n = (size_t)nframes * handle->last_nrigid;
-  for (size_t i = 0; i < n; i++) out[i] = handle->h_xcovs[i].c;
-  return AMDAT_SUCCESS;
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_bundle_records(handle, POST_RIGID | POST_COV, &PostMode::nrigid, handle->h_xcovs, &PoseCovRec::c, out, nframes);
+}
+
+int amdAprilTagsGetUndistortedDetections(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsUndistortedDetection_t* out, uint32_t capacity, uint32_t* n) {
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_frame_records(handle, POST_UNDISTORT, handle->h_udets, &UndistortRec::det, frame, out, capacity, n,
+                           [](amdAprilTagsUndistortedDetection_t&) {});   // (an invalid twin says so itself)
+}
+
+int amdAprilTagsGetRefinedPoses(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsRefinedPose_t* out, uint32_t capacity, uint32_t* n) {
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_frame_records(handle, POST_REFINE, handle->h_rposes, &PoseRefineRec::pose, frame, out, capacity, n,
+                           [](amdAprilTagsRefinedPose_t& o) { o = {}; o.status = AMDAT_POSE_DEGENERATE; });
+}
+
+int amdAprilTagsGetRefinedPoseCovariances(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsPoseCovariance_t* out, uint32_t capacity, uint32_t* n) {
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_frame_records(handle, POST_REFINE | POST_COV, handle->h_rcovs, &PoseCovRec::c, frame, out, capacity, n,
+                           [](amdAprilTagsPoseCovariance_t& o) { o = {}; });   // (all zero, valid = 0)
 }
 
 int amdAprilTagsDebugQuadSigmaTaps(float quad_sigma, uint8_t* taps, uint32_t capacity, uint32_t* ksz) {
@@ -1620,33 +1600,38 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
   mark();
   hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
                      D->h_counters, P);
-  // S9b: raw-frame mode -- the undistorted twin of every kept record (kernels_undistort.h); the three launches below then read the
-  // twins, which order and count as the raw records do
-  const bool undist = !D->undist_models.empty();
-  if (undist)
-    hipLaunchKernelGGL(k_undistort_records, dim3(n, UD_WAVES_PER_FRAME), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
-                       D->d_ucams, D->d_dets_u, D->h_udets, ostride, P);
-  const DetRec* const pose_dets = undist ? UD_POSE_RECORDS(D->d_dets, D->d_dets_u) : D->d_dets;   // (tools_hooks.h: d_dets_u in the product build)
-  if (D->nbundles)   // S10: one wave per (frame, bundle) on the kept records, straight behind k_reconcile (kernels_bundle.h)
-    hipLaunchKernelGGL(k_bundle_pose, dim3(n, AMDAT_MAX_BUNDLES), dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order,
-                       D->d_bundle_head, D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
-  // (amdAprilTagsSetPoseCovariance: the covariance instance of whichever of the two launches below runs; off, the launches as they were)
-  const bool cov = D->pose_cov_sigma > 0.0;
-  if (D->nrigid)   // S12: two waves per (frame, bundle), one chain each, in the planar kind's place (kernels_rigid.h)
-#define RIGID_LAUNCH(COV)                                                                                                           \
-  hipLaunchKernelGGL(k_bundle_rigid<COV>, dim3(n, AMDAT_MAX_BUNDLES), dim3(128), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, \
-                     D->d_rigid_head, D->d_rigid_members, D->d_rigid_table, D->h_xposes, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_xcovs)
-  {
-    if (cov) RIGID_LAUNCH(true); else RIGID_LAUNCH(false);
-  }
+  // The stages behind k_reconcile, as plan_post lists them (post_plan.h), one wave per block except the rigid kind's two
+  const PostPlan post = plan_post(D->last.post, n, ostride);
+  for (int i = 0; i < post.nsteps; i++) {
+    const PostStep& st = post.steps[i];
+    const dim3 grid(st.gx, st.gy);
+    // raw-frame mode: the pose launches read the twins, which order and count as the raw records do (tools_hooks.h: d_dets_u in the product build)
+    const DetRec* const pose_dets = st.twins ? UD_POSE_RECORDS(D->d_dets, D->d_dets_u) : D->d_dets;
+#define RIGID_LAUNCH(COV)                                                                                                          \
+  hipLaunchKernelGGL(k_bundle_rigid<COV>, grid, dim3(128), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, D->d_rigid_head, \
+                     D->d_rigid_members, D->d_rigid_table, D->h_xposes, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_xcovs)
+#define POSE_LAUNCH(COV)                                                                                                           \
+  hipLaunchKernelGGL(k_pose_refine<COV>, grid, dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, D->d_pose_cfg,    \
+                     D->h_rposes, ostride, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_rcovs)
+    switch (st.kernel) {
+      case POST_K_UNDISTORT:   // S9b: the undistorted twin of every kept record (kernels_undistort.h)
+        hipLaunchKernelGGL(k_undistort_records, grid, dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->d_ucams,
+                           D->d_dets_u, D->h_udets, ostride, P);
+        break;
+      case POST_K_PLANAR:      // S10: one wave per (frame, bundle) on the kept records (kernels_bundle.h)
+        hipLaunchKernelGGL(k_bundle_pose, grid, dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, D->d_bundle_head,
+                           D->d_bundle_members, D->d_bundle_table, D->h_bposes, P);
+        break;
+      case POST_K_RIGID:       // S12: two waves per (frame, bundle), one chain each, in the planar kind's place (kernels_rigid.h)
+        if (st.cov) RIGID_LAUNCH(true); else RIGID_LAUNCH(false);
+        break;
+      case POST_K_REFINE:      // S11: both minima of the records handed out, eight lanes per record (kernels_pose.h)
+        if (st.cov) POSE_LAUNCH(true); else POSE_LAUNCH(false);
+        break;
+    }
 #undef RIGID_LAUNCH
-#define POSE_LAUNCH(COV)                                                                                                            \
-  hipLaunchKernelGGL(k_pose_refine<COV>, dim3(n, pose_refine_waves(ostride)), dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, \
-                     D->d_order, D->d_pose_cfg, D->h_rposes, ostride, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_rcovs)
-  if (D->pose_iterations) {   // S11: both minima of the records handed out, eight lanes per record, beside the bundles (kernels_pose.h)
-    if (cov) POSE_LAUNCH(true); else POSE_LAUNCH(false);
-  }
 #undef POSE_LAUNCH
+  }
   mark();
   return AMDAT_SUCCESS;
 }
@@ -1654,8 +1639,8 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
 // Everything one submission enqueues on stream s (and the auxiliary streams forked from it): descriptor upload, clears,
 // the stage sequence, result download.  No host synchronisation inside, so the sequence can be stream-captured.
 static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride, hipStream_t s, uint32_t fmt, const std::function<void()>& mark) {
-  // (the setters refuse while a submission is in flight: a regrowth relaunch resizes and rectifies again)
-  const bool resize = !D->resize_sizes.empty(), rect = !resize && !D->rect_models.empty();
+  // (the snapshot begin_batch took: a regrowth relaunch resizes and rectifies again)
+  const bool resize = D->last.resized, rect = D->last.rectified;
   mark();
   // descriptor upload + clears in one small kernel (it reads the pinned descriptor block over the bus itself): a copy
   // command and a fill command ahead of the first kernel cost a one-frame call about 15 us, this launch 4
@@ -1666,7 +1651,7 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
                      static_cast<const uint32_t*>(D->h_front.p), static_cast<uint32_t*>(D->d_front.p),
                      resize || rect ? (int)(sizeof(FrontDesc) / 4) : 0,
                      static_cast<const uint32_t*>(D->h_ucams.p), static_cast<uint32_t*>(D->d_ucams.p),
-                     D->undist_models.empty() ? 0 : (int)(sizeof(UndistortCam) / 4));
+                     D->last.post.nundist ? (int)(sizeof(UndistortCam) / 4) : 0);
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
@@ -1836,39 +1821,25 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
   auto stamped = [&]() {
     for (uint32_t f = 0; f < D->launched_n; f++)
       if (static_cast<volatile FrameCounters*>(D->h_counters)[f].seq != D->seq) return false;
-    // bundles on: k_bundle_pose, the last kernel, stamps its records the same way
-    for (uint32_t r = 0; r < D->launched_n * D->nbundles; r++)
-      if (static_cast<volatile BundlePoseRec*>(D->h_bposes)[r].seq != D->seq) return false;
-    for (uint32_t r = 0; r < D->launched_n * D->nrigid; r++)   // rigid bundles on: k_bundle_rigid's records
-      if (static_cast<volatile RigidPoseRec*>(D->h_xposes)[r].seq != D->seq) return false;
-    // pose refinement on: k_pose_refine stamps every record it hands out (the counts are final: the frames' stamps were seen above)
-    if (D->pose_iterations)
-      for (uint32_t f = 0; f < D->launched_n; f++) {
-        uint32_t k = D->h_counters[f].nout;
-        if (k > D->last_ostride) k = D->last_ostride;
-        for (uint32_t i = 0; i < k; i++)
-          if (static_cast<volatile PoseRefineRec*>(D->h_rposes)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
-      }
-    // corner undistortion on: k_undistort_records stamps every record it hands out
-    if (!D->undist_models.empty())
-      for (uint32_t f = 0; f < D->launched_n; f++) {
-        uint32_t k = D->h_counters[f].nout;
-        if (k > D->last_ostride) k = D->last_ostride;
-        for (uint32_t i = 0; i < k; i++)
-          if (static_cast<volatile UndistortRec*>(D->h_udets)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
-      }
-    // pose covariance on: the covariance records beside both kinds carry the stamp as well
-    if (D->pose_cov_sigma > 0.0) {
-      for (uint32_t r = 0; r < D->launched_n * D->nrigid; r++)
-        if (static_cast<volatile PoseCovRec*>(D->h_xcovs)[r].seq != D->seq) return false;
-      if (D->pose_iterations)
+    // The stages behind k_reconcile stamp every record they hand out the same way: the blocks the submission's plan lists (the
+    // records' counts are final: the frames' stamps were seen above).  Per PostBlock: where it lies, its record size, the stamp's offset.
+    const struct { const void* p; size_t size, seq; } blocks[] = {
+        {D->h_udets.p, sizeof(UndistortRec), offsetof(UndistortRec, seq)}, {D->h_bposes.p, sizeof(BundlePoseRec), offsetof(BundlePoseRec, seq)},
+        {D->h_xposes.p, sizeof(RigidPoseRec), offsetof(RigidPoseRec, seq)}, {D->h_xcovs.p, sizeof(PoseCovRec), offsetof(PoseCovRec, seq)},
+        {D->h_rposes.p, sizeof(PoseRefineRec), offsetof(PoseRefineRec, seq)}, {D->h_rcovs.p, sizeof(PoseCovRec), offsetof(PoseCovRec, seq)}};
+    static_assert(POST_B_UDETS == 0 && POST_B_BPOSES == 1 && POST_B_XPOSES == 2 && POST_B_XCOVS == 3 && POST_B_RPOSES == 4 && POST_B_RCOVS == 5, "blocks[]");
+    const PostPlan post = plan_post(D->last.post, D->launched_n, D->last.ostride);
+    for (int i = 0; i < post.nsteps; i++)
+      for (int j = 0; j < post.steps[i].nwrites; j++) {
+        const PostWrite& w = post.steps[i].writes[j];
+        const char* const recs = static_cast<const char*>(blocks[w.block].p) + blocks[w.block].seq;
         for (uint32_t f = 0; f < D->launched_n; f++) {
-          uint32_t k = D->h_counters[f].nout;
-          if (k > D->last_ostride) k = D->last_ostride;
-          for (uint32_t i = 0; i < k; i++)
-            if (static_cast<volatile PoseCovRec*>(D->h_rcovs)[(size_t)f * D->last_ostride + i].seq != D->seq) return false;
+          uint32_t k = w.per_frame;   // POST_BY_BUNDLE: every entry of the frame
+          if (w.index == POST_BY_RECORD && D->h_counters[f].nout < k) k = D->h_counters[f].nout;
+          for (uint32_t r = 0; r < k; r++)
+            if (*reinterpret_cast<const volatile uint32_t*>(recs + ((size_t)f * w.per_frame + r) * blocks[w.block].size) != D->seq) return false;
         }
-    }
+      }
     return true;
   };
   if (!stamped()) {
@@ -1949,27 +1920,18 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   if (!guard.ok) return AMDAT_HIP_ERROR;
   if (D->unusable) return AMDAT_OUT_OF_MEMORY;   // (never launch on the half-allocated buffers of a failed regrowth)
   const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
-  D->last_resized = !D->resize_sizes.empty();
-  D->last_rectified = !D->last_resized && !D->rect_models.empty();   // (resized: the rectified plane is never formed)
-  if (D->last_resized || D->last_rectified) {   // from here on a mono8 submission of the front plane's slots at their target sizes
+  const bool resized = !D->resize_sizes.empty(), rectified = !resized && !D->rect_models.empty();   // (resized: the rectified plane is never formed)
+  if (resized || rectified) {   // from here on a mono8 submission of the front plane's slots at their target sizes
     images = fill_front(D, n, images, fmt);
     fmt = AMDAT_ENC_MONO8;
   }
   { const int crc = ensure_colour_plane(D, fmt, filt); if (crc) return crc; }
   fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
-  D->last_n = n;
-  D->last_nbundles = D->nbundles;
-  D->last_nrigid = D->nrigid;
   D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
-  D->last_pose_refined = D->pose_iterations > 0;
-  D->last_pose_cov = D->pose_cov_sigma > 0.0;
-  D->last_ostride = ostride;
-  D->last_undistorted = !D->undist_models.empty();
-  if (D->last_undistorted) {   // each slot's camera, beside the frame descriptors (the model describes the detected image)
-    const uint32_t ncams = (uint32_t)D->undist_models.size();
-    for (uint32_t i = 0; i < n; i++) D->h_ucams[i] = undistort_cam(D->undist_models[UD_MODEL_OF_SLOT(i, ncams)]);   // (tools_hooks.h: i % ncams)
-  }
+  D->last = {n, ostride, D->post, rectified, resized};
+  for (uint32_t i = 0; i < n && D->post.nundist; i++)   // each slot's camera, beside the frame descriptors (the model describes the detected image)
+    D->h_ucams[i] = undistort_cam(D->undist_models[UD_MODEL_OF_SLOT(i, D->post.nundist)]);   // (tools_hooks.h: i % ncams)
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
     D->pending_hash_grow = false;
     const GrowPlan g = plan_pending_hash(caps_of(D), D->grow);
@@ -2153,7 +2115,7 @@ int amdAprilTagsSetFrameSkews(amdAprilTagsHandle handle, uint32_t n, const float
 }
 
 int amdAprilTagsGetFrameFlags(amdAprilTagsHandle handle, uint32_t* flags, uint32_t n) {
-  if (!handle || !flags || n > handle->last_n || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  if (!handle || !flags || n > handle->last.n || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < n; i++) flags[i] = handle->h_counters[i].flags;
   return AMDAT_SUCCESS;
 }
@@ -2175,14 +2137,8 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
   rc = ensure_colour_plane(handle, fmt);
   if (rc) return rc;
   fill_frames(handle, n, images, nullptr, fmt);
-  handle->last_n = n;
-  handle->last_nbundles = 0;        // (never solves bundles)
-  handle->last_nrigid = 0;
-  handle->last_pose_refined = false;   // (never refines poses)
-  handle->last_pose_cov = false;
-  handle->last_undistorted = false;   // (never undistorts corners)
-  handle->last_rectified = false;   // (never rectifies)
-  handle->last_resized = false;     // (never resizes)
+  handle->last = {};   // (never runs the front stage or the stages behind k_reconcile)
+  handle->last.n = n;
   HIP_TRY(hipMemcpyAsync(handle->d_frames, handle->h_frames, n * sizeof(FrameDesc), hipMemcpyHostToDevice, s));
   if (handle->profiling) hipEventRecord(handle->ev[1], s);
   { DetParams P0 = handle->P; P0.frame0 = 0; launch_threshold(handle, P0, n, s, fmt); }
@@ -2301,7 +2257,7 @@ int amdAprilTagsStreamDestroy(amdAprilTagsStream stream) {
 
 int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsDebugBuffer what, void* host_dst,
                           size_t capacity, size_t* bytes) {
-  if (!handle || !bytes || frame >= handle->last_n || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  if (!handle || !bytes || frame >= handle->last.n || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   const DetParams& P = handle->P;
   DeviceGuard guard(handle->device);
   if (!guard.ok) return AMDAT_HIP_ERROR;
@@ -2330,7 +2286,7 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
     }
     case AMDAT_DBG_RECTIFIED:
     case AMDAT_DBG_RESIZED: {   // DW x DH dense: the frame's slot of the front plane, where the last submission formed that plane
-      if (what == AMDAT_DBG_RESIZED ? handle->resize_sizes.empty() || !handle->last_resized : handle->rect_models.empty() || !handle->last_rectified)
+      if (what == AMDAT_DBG_RESIZED ? handle->resize_sizes.empty() || !handle->last.resized : handle->rect_models.empty() || !handle->last.rectified)
         return AMDAT_INVALID_ARGUMENT;
       const FrontDesc& f = handle->h_front[frame];
       const size_t n0 = (size_t)f.DW * f.DH;
@@ -2381,10 +2337,40 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
   return AMDAT_SUCCESS;
 }
 
-// k_reconcile alone, on records the caller chooses: they go into batch slot 0's record list with that slot's ndets, the slot's
-// descriptor carries the handle's intrinsics and a fresh sequence number, and the kept records come back through the pinned buffer
-// as after a submission.  Nothing of the last submission can be inspected afterwards (its slot 0 is overwritten): last_n is 0 until
-// the next one, whose prologue rewrites descriptors and counters anyway.
+// One stage alone on batch slot 0, for the two entry points below.  The slot's descriptor carries the handle's intrinsics and a fresh
+// sequence number, its counters are `fc`; `enqueue(s, P)` uploads what else the stage reads and launches it; `stamped(seq)` says
+// whether its results have arrived, asked after the stream wait and once more after a device-wide one.  Nothing of the last
+// submission can be inspected afterwards (its slot 0 is overwritten): the snapshot is empty, last.n 0, until the next one, whose
+// prologue rewrites descriptors and counters anyway.
+extern "C++" {
+template <class Enqueue, class Stamped>
+static int debug_slot0(amdAprilTagsDetector_st* D, const FrameCounters& fc, Enqueue enqueue, Stamped stamped) {
+  const hipStream_t s = D->own_stream;
+  HIP_TRY(hipDeviceSynchronize());
+  D->last = {};
+  FrameDesc fd;
+  memset(&fd, 0, sizeof(fd));
+  fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;
+  fd.cx = (double)D->cfg.intrinsics.cx; fd.cy = (double)D->cfg.intrinsics.cy;
+  fd.skew = (double)(D->frame_skew.empty() ? D->cfg.skew : D->frame_skew[0]);
+  fd.seq = ++D->seq;
+  HIP_TRY(hipMemcpyAsync(D->d_frames, &fd, sizeof(fd), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(D->d_counters, &fc, sizeof(fc), hipMemcpyHostToDevice, s));
+  DetParams P = D->P;
+  P.frame0 = 0;
+  { const int rc = enqueue(s, P); if (rc) return rc; }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));   // (the pageable sources above are read before this returns)
+  if (!stamped(fd.seq)) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (!stamped(fd.seq)) return AMDAT_HIP_ERROR;
+  }
+  return AMDAT_SUCCESS;
+}
+}  // extern "C++"
+
+// k_reconcile alone, on records the caller chooses: they go into batch slot 0's record list with that slot's ndets, and the kept
+// records come back through the pinned buffer as after a submission.
 int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
                                amdAprilTagsDetectionEx_t* records_out, uint32_t capacity, uint32_t* nout) {
   if (!handle || !nout || handle->inflight.active || (n && !records_in) || (capacity && !records_out)) return AMDAT_INVALID_ARGUMENT;
@@ -2393,32 +2379,18 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
   amdAprilTagsDetector_st* D = handle;
   DeviceGuard guard(D->device);
   if (!guard.ok) return AMDAT_HIP_ERROR;
-  const hipStream_t s = D->own_stream;
-  HIP_TRY(hipDeviceSynchronize());
-  D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_pose_cov = false; D->last_rectified = false; D->last_resized = false;
-  D->last_undistorted = false;
-  FrameDesc fd;
-  memset(&fd, 0, sizeof(fd));
-  fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;
-  fd.cx = (double)D->cfg.intrinsics.cx; fd.cy = (double)D->cfg.intrinsics.cy;
-  fd.skew = (double)(D->frame_skew.empty() ? D->cfg.skew : D->frame_skew[0]);
-  fd.seq = ++D->seq;
   FrameCounters fc;
   memset(&fc, 0, sizeof(fc));
   fc.ndets = n;
-  HIP_TRY(hipMemcpyAsync(D->d_frames, &fd, sizeof(fd), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(D->d_counters, &fc, sizeof(fc), hipMemcpyHostToDevice, s));
-  if (n) HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
-  DetParams P = D->P;
-  P.frame0 = 0;
-  hipLaunchKernelGGL(k_reconcile, dim3(1), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, P.dcap,
-                     D->h_counters, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s));
-  if (static_cast<volatile FrameCounters*>(D->h_counters)[0].seq != fd.seq) {
-    HIP_TRY(hipDeviceSynchronize());
-    if (static_cast<volatile FrameCounters*>(D->h_counters)[0].seq != fd.seq) return AMDAT_HIP_ERROR;
-  }
+  const int rc = debug_slot0(D, fc,
+      [&](hipStream_t s, const DetParams& P) -> int {
+        if (n) HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_reconcile, dim3(1), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, P.dcap,
+                           D->h_counters, P);
+        return AMDAT_SUCCESS;
+      },
+      [&](uint32_t seq) { return static_cast<volatile FrameCounters*>(D->h_counters)[0].seq == seq; });
+  if (rc) return rc;
   const uint32_t nk = D->h_counters[0].nout;
   *nout = nk;
   const uint32_t k = nk < capacity ? nk : capacity;
@@ -2427,7 +2399,7 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
 }
 
 // k_undistort_records alone, on records the caller chooses: they become batch slot 0's kept records in the order given (the order list
-// is the identity), under `cam`; the slot's descriptor carries the handle's intrinsics and a fresh sequence number.
+// is the identity), under `cam`.
 int amdAprilTagsDebugUndistort(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
                                const amdAprilTagsCameraModelEx_t* cam, amdAprilTagsUndistortedDetection_t* out,
                                amdAprilTagsDetectionEx_t* twins_out) {
@@ -2438,40 +2410,29 @@ int amdAprilTagsDebugUndistort(amdAprilTagsHandle handle, uint32_t n, const amdA
   DeviceGuard guard(D->device);
   if (!guard.ok) return AMDAT_HIP_ERROR;
   { const int rc = ensure_undistort_buffers(D); if (rc) return rc; }
-  const hipStream_t s = D->own_stream;
-  HIP_TRY(hipDeviceSynchronize());
-  D->last_n = 0; D->last_nbundles = 0; D->last_nrigid = 0; D->last_pose_refined = false; D->last_pose_cov = false; D->last_rectified = false; D->last_resized = false;
-  D->last_undistorted = false;
-  FrameDesc fd;
-  memset(&fd, 0, sizeof(fd));
-  fd.fx = (double)D->cfg.intrinsics.fx; fd.fy = (double)D->cfg.intrinsics.fy;
-  fd.cx = (double)D->cfg.intrinsics.cx; fd.cy = (double)D->cfg.intrinsics.cy;
-  fd.skew = (double)(D->frame_skew.empty() ? D->cfg.skew : D->frame_skew[0]);
-  fd.seq = ++D->seq;
   FrameCounters fc;
   memset(&fc, 0, sizeof(fc));
   fc.ndets = n; fc.nout = n;
   const UndistortCam uc = undistort_cam(*cam);
   std::vector<uint16_t> ident(n);
   for (uint32_t i = 0; i < n; i++) ident[i] = (uint16_t)i;
-  HIP_TRY(hipMemcpyAsync(D->d_frames, &fd, sizeof(fd), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(D->d_counters, &fc, sizeof(fc), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(D->d_ucams, &uc, sizeof(uc), hipMemcpyHostToDevice, s));
-  if (n) {
-    HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(D->d_order, ident.data(), (size_t)n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-  }
-  DetParams P = D->P;
-  P.frame0 = 0;
-  hipLaunchKernelGGL(k_undistort_records, dim3(1, UD_WAVES_PER_FRAME), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
-                     D->d_ucams, D->d_dets_u, D->h_udets, P.dcap, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s));   // (the pageable sources above are read before this returns)
-  for (uint32_t i = 0; i < n; i++)
-    if (static_cast<volatile UndistortRec*>(D->h_udets)[i].seq != fd.seq) {
-      HIP_TRY(hipDeviceSynchronize());
-      if (static_cast<volatile UndistortRec*>(D->h_udets)[i].seq != fd.seq) return AMDAT_HIP_ERROR;
-    }
+  const int rc = debug_slot0(D, fc,
+      [&](hipStream_t s, const DetParams& P) -> int {
+        HIP_TRY(hipMemcpyAsync(D->d_ucams, &uc, sizeof(uc), hipMemcpyHostToDevice, s));
+        if (n) {
+          HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
+          HIP_TRY(hipMemcpyAsync(D->d_order, ident.data(), (size_t)n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_undistort_records, dim3(1, UD_WAVES_PER_FRAME), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
+                           D->d_ucams, D->d_dets_u, D->h_udets, P.dcap, P);
+        return AMDAT_SUCCESS;
+      },
+      [&](uint32_t seq) {
+        for (uint32_t i = 0; i < n; i++)
+          if (static_cast<volatile UndistortRec*>(D->h_udets)[i].seq != seq) return false;
+        return true;
+      });
+  if (rc) return rc;
   if (out) for (uint32_t i = 0; i < n; i++) out[i] = D->h_udets[i].det;
   if (twins_out && n) HIP_TRY(hipMemcpy(twins_out, D->d_dets_u, (size_t)n * sizeof(DetRec), hipMemcpyDeviceToHost));
   return AMDAT_SUCCESS;
