@@ -466,6 +466,56 @@ int amdAprilTagsSetBundlesEx(amdAprilTagsHandle handle, uint32_t nbundles, const
  * submission in flight. */
 int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePoseEx_t* out, uint32_t nframes);
 
+/* Camera rigs: one pose per instant and rigid bundle from the tags ALL cameras of a calibrated rig saw at that instant, inside the
+ * submission (DESIGN.md section 7j has every operation; csrc/rig_pose.h states it once for device and host, tests/rig_pose_ref.py in
+ * Python).  A camera's extrinsics give the RIG frame in the CAMERA frame: X_cam = R X_rig + t, R row-major.  R must be a rotation as
+ * it stands (the rule of amdAprilTagsBundleMemberEx_t). */
+typedef struct { double R[9]; double t[3]; } amdAprilTagsRigCamera_t;
+/* Batch slot i of a submission is camera `camera` of group `group`: the frames of one group were taken at one instant. */
+typedef struct { uint32_t group; uint32_t camera; } amdAprilTagsRigSlot_t;
+#define AMDAT_RIG_NO_CAMERA 0xFFFFFFFFu      /* the slot is detected as usual and belongs to no group */
+#define AMDAT_MAX_RIG_CAMERAS 16u
+#define AMDAT_MAX_RIG_OBSERVATIONS 64u   /* per (group, bundle): one lane of the solving wave holds one observation */
+/* One record per (group, bundle).  An observation is one used record of one of the group's frames: the group's slots are walked in
+ * ascending batch-slot order and each frame's kept records in their canonical order; classification, gates and the per-frame
+ * duplicate rule are amdAprilTagsSetBundles' (a tag seen by two cameras is two observations).  nobs: the observations solved over,
+ * at most AMDAT_MAX_RIG_OBSERVATIONS, which the bundle's min_tags gates; ndropped: the used records beyond them; nskipped: the
+ * records a gate or the duplicate rule kept out, over all the group's frames; ncams: the distinct cameras among the nobs.
+ * seed_frame, seed: the batch slot of the observation with the largest pixel area and its record's index in that frame's canonical
+ * order; its homography pose, moved into the rig frame, starts both chains.  status, chosen and the *_alt fields as
+ * amdAprilTagsBundlePoseEx_t's.  R (row-major), t: the bundle frame in the RIG frame.  err: the object-space error
+ * E = sum |(I - F_j)(R P_j + t - o_j)|^2 over the 4 * nobs corners, F_j the projector onto the corner's viewing ray in the rig frame
+ * and o_j its camera's centre; sq_err_sum: the squared pixel reprojection errors of the same corners, each under its own camera. */
+typedef struct {
+  uint32_t group, bundle, status, nobs, nskipped, ndropped, ncams, seed_frame, seed, chosen;
+  double R[9], t[3], err, sq_err_sum;
+  double R_alt[9], t_alt[3], err_alt, sq_err_sum_alt;
+} amdAprilTagsRigBundlePose_t;
+/* ncams = 0 turns the mode off (the default: nothing is launched or allocated, and no record of any other stage changes).  Otherwise
+ * every following submission in which amdAprilTagsSetBundlesEx is on solves, in one small launch behind the other pose launches, one
+ * pose per group and rigid bundle over all observations of the group's cameras at once: the object-space iteration of
+ * amdAprilTagsSetBundlesEx with a ray origin per camera, two chains of the bundle's `iterations` steps, the same outcome rule.  The
+ * per-frame rigid records are computed as before.  With amdAprilTagsSetBundlesEx off nothing is launched.  With
+ * amdAprilTagsSetCornerUndistortion on the observations are the undistorted twins.  amdAprilTagsSetPoseCovariance leaves the rig
+ * record alone.  The extrinsics are host state of the handle and travel with every submission's descriptors.
+ * Callable whenever no submission is in flight.  AMDAT_INVALID_ARGUMENT: null handle, null cams with ncams > 0, ncams above
+ * AMDAT_MAX_RIG_CAMERAS, a non-finite entry, an R with max |R R^T - I| > 1e-6 or det R <= 0, a submission in flight;
+ * AMDAT_OUT_OF_MEMORY: the buffers could not be allocated.  A refused call leaves the previous setting in force.  Turning the mode
+ * on or off retires the handle's captured launch graphs, against the same budget of 24 as amdAprilTagsSetQuadSigma; new extrinsics
+ * do not. */
+int amdAprilTagsSetRig(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsRigCamera_t* cams);
+/* The slot map of the submissions that follow: slots[i] for batch slot i < n; a slot beyond n, and every slot where n = 0, follows
+ * the default map: camera i % ncams of group i / ncams.  Host state, like the extrinsics: no graph is retired.
+ * AMDAT_INVALID_ARGUMENT: null handle, null slots with n > 0, n above the handle's max_batch, a submission in flight.  While the rig
+ * is on, a SUBMISSION is refused with AMDAT_INVALID_ARGUMENT, nothing enqueued, where a slot names a group index at or above its
+ * frame count or a camera index at or above ncams (AMDAT_RIG_NO_CAMERA excepted), or where two slots name one (group, camera). */
+int amdAprilTagsSetRigSlots(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsRigSlot_t* slots);
+/* The rig records of the last completed submission: ngroups x nbundles, group-major (out[g * nbundles + b]), nbundles being
+ * amdAprilTagsSetBundlesEx'.  Every group index below the submission's frame count has its records: a group no slot belongs to reads
+ * AMDAT_BUNDLE_TOO_FEW_TAGS with zeros.  AMDAT_INVALID_ARGUMENT: null handle or out, the last submission did not run this mode (the
+ * rig or the rigid bundles were off), ngroups beyond the last submission's frame count, a submission in flight. */
+int amdAprilTagsGetRigBundlePoses(amdAprilTagsHandle handle, amdAprilTagsRigBundlePose_t* out, uint32_t ngroups);
+
 /* Orthogonal-iteration tag pose with both minima, inside the submission (AprilRobotics' estimate_tag_pose: the object-space iteration
  * of Lu, Hager and Mjolsness from two starts, the lower error returned).  Off by default; amdAprilTagsID_t and
  * amdAprilTagsDetectionEx_t carry the homography pose whether it is on or off.

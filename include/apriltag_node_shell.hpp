@@ -133,6 +133,22 @@ struct RigidBundlePose {
   std::array<double, 36> covariance{};
 };
 
+// One camera of a calibrated rig (amdAprilTagsSetRig): the RIG frame in the CAMERA frame, X_cam = R X_rig + t, R row-major and a
+// rotation as it stands (the library refuses max |R R^T - I| > 1e-6 or det R <= 0).
+struct RigCamera {
+  std::array<double, 9> R{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+  std::array<double, 3> t{};
+};
+// The detector's record of one rigid bundle for one round of a rig (amdAprilTagsRigBundlePose_t): the bundle frame in the rig frame
+// from the tags of all the round's cameras.  seed_stream: the stream of the seed observation.
+struct RigBundlePose {
+  std::string name;
+  uint32_t status = 0, nobs = 0, nskipped = 0, ndropped = 0, ncams = 0, seed_stream = 0, seed = 0, chosen = 0;
+  std::array<double, 9> R{}, R_alt{};   // row-major
+  std::array<double, 3> t{}, t_alt{};
+  double err = 0, sq_err_sum = 0, err_alt = 0, sq_err_sum_alt = 0;
+};
+
 // Parameters declared in the constructor of the reference node (src/apriltag_node.cpp:564-568).
 struct NodeOptions {
   int max_tags = 64;
@@ -196,6 +212,15 @@ struct NodeOptions {
   // z; camera optical frame), copied without conversion -- and every RigidBundlePose carries its `covariance` the same way.  A record
   // whose covariance is not valid keeps zeros.  0 (the default): off, the covariance all zero as the reference node leaves it.
   double pose_covariance_sigma_px = 0;
+  // Extension, AprilTagMultiCameraNode only (AprilTagNode ignores both): the streams are the cameras of one calibrated rig
+  // (amdAprilTagsSetRig, set once when the handle is created), rig_cameras[s] being stream s's extrinsics -- one per stream, with
+  // rigid_bundles set.  Every Flush is one instant: it sends a slot map with every served stream in group 0 as its own camera (a
+  // stream without a staged frame is simply absent), and, behind the per-stream transforms, one TransformStamped per SOLVED bundle
+  // from the rig record's chosen pose -- child frame "rig_bundle:<name>", parent rig_frame_id, the stamp of the round's first served
+  // stream, handed to the transforms callback with that stream's -- and keeps the round's records (last_rig_bundle_poses).  Empty
+  // (the default): off.
+  std::vector<RigCamera> rig_cameras;
+  std::string rig_frame_id = "rig";
 };
 
 class AprilTagNode {
@@ -264,6 +289,8 @@ class AprilTagMultiCameraNode {
   // NodeOptions::bundles: the records of the last frame published for `stream`, one per bundle in the options' order
   const std::vector<BundlePose>& last_bundle_poses(uint32_t stream) const;
   const std::vector<RigidBundlePose>& last_rigid_bundle_poses(uint32_t stream) const;
+  // NodeOptions::rig_cameras: the rig records of the last round, one per rigid bundle in the options' order (empty: the rig is off)
+  const std::vector<RigBundlePose>& last_rig_bundle_poses() const;
 
  private:
   struct Impl;

@@ -165,7 +165,7 @@ def build_stress(force=False):
 
 
 MUTANTS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40,
-           41, 42, 43, 44, 45)   # csrc/tools_hooks.h, AMDAT_MUTATE
+           41, 42, 43, 44, 45, 46, 47, 48)   # csrc/tools_hooks.h, AMDAT_MUTATE
 MUTANT_JOBS = 16   # compilers build_mutants runs at a time
 
 
@@ -194,14 +194,17 @@ def build_mutants(force=False):
     general form with every left neighbour a source, 36 k_cluster_select with > against min_cluster_points, 37 k_quad_finish's area
     limit as 1.0 * w * w, 38 k_quad_finish without the lower angle test, 39 k_quad_finish without the winding term,
     40 fit_border_unwanted without its normal_border statement, 41 .. 44 the cut to max_nmaxima corners keeping nine in k_fit_small and
-    in k_fit_quads with up to 64, up to 64 * FQ_SEL_REGS and more maxima, 45 the corner search without its dot test),
+    in k_fit_quads with up to 64, up to 64 * FQ_SEL_REGS and more maxima, 45 the corner search without its dot test, 46 the rig pose's translation
+    statement without the ray origin, 47 the rig pose's ray direction with Rc in place of its transpose, 48 k_bundle_rig's observation
+    slots cut at 63),
     shipped like the stress build so that the GPU suite itself shows, under the driver's eyes, that its stage tests FAIL on each of them
     (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds, tests/test_per_frame_sizes_gpu.py for 6,
     tests/test_fit_classes_gpu.py for 7 and 8, tests/test_rectify_submission_gpu.py for 9 and 10,
     tests/test_resize_submission_gpu.py for 11 and 12, tests/test_camera_models_gpu.py for 13 and 14, tests/test_bundles_gpu.py for 15 and 16,
     tests/test_pose_refine_gpu.py for 17 and 18, tests/test_rigid_bundles_gpu.py for 19 and 20, tests/test_decode_stage_gpu.py for
     21 .. 24, tests/test_pose_covariance_gpu.py for 25 .. 27, tests/test_corner_undistortion_gpu.py for 28 .. 30,
-    tests/test_integer_stages_gpu.py for 31 .. 36, tests/test_fit_rules_gpu.py for 37 .. 45).  Never loaded by the product path.
+    tests/test_integer_stages_gpu.py for 31 .. 36, tests/test_fit_rules_gpu.py for 37 .. 45,
+    tests/test_rig_bundles_gpu.py for 46 .. 48).  Never loaded by the product path.
     At most MUTANT_JOBS compilers run at a time."""
     from concurrent.futures import ThreadPoolExecutor
     err = []

@@ -96,6 +96,40 @@ BUNDLE_DEGENERATE = 3
 MAX_RIGID_BUNDLE_MEMBERS = 64
 
 
+class RigCamera(C.Structure):
+    """amdAprilTagsRigCamera_t: the rig frame in the camera frame, X_cam = R X_rig + t (R row-major)."""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class RigSlot(C.Structure):
+    """amdAprilTagsRigSlot_t."""
+    _fields_ = [("group", C.c_uint32), ("camera", C.c_uint32)]
+
+
+class RigBundlePose(C.Structure):
+    """amdAprilTagsRigBundlePose_t."""
+    _fields_ = [("group", C.c_uint32), ("bundle", C.c_uint32), ("status", C.c_uint32), ("nobs", C.c_uint32), ("nskipped", C.c_uint32),
+                ("ndropped", C.c_uint32), ("ncams", C.c_uint32), ("seed_frame", C.c_uint32), ("seed", C.c_uint32), ("chosen", C.c_uint32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double), ("sq_err_sum", C.c_double),
+                ("R_alt", C.c_double * 9), ("t_alt", C.c_double * 3), ("err_alt", C.c_double), ("sq_err_sum_alt", C.c_double)]
+
+
+RIG_NO_CAMERA = 0xFFFFFFFF
+MAX_RIG_CAMERAS, MAX_RIG_OBSERVATIONS = 16, 64
+
+
+def rig_cameras(cams):
+    """[(R (3 x 3), t (3))] as an array of RigCamera; None for an empty list."""
+    cams = list(cams or [])
+    if not cams:
+        return None
+    arr = (RigCamera * len(cams))()
+    for i, (R, t) in enumerate(cams):
+        arr[i].R = (C.c_double * 9)(*[float(v) for v in np.asarray(R, dtype=np.float64).reshape(-1)])
+        arr[i].t = (C.c_double * 3)(*[float(v) for v in np.asarray(t, dtype=np.float64).reshape(-1)])
+    return arr
+
+
 class RefinedPose(C.Structure):
     """amdAprilTagsRefinedPose_t."""
     _fields_ = [("status", C.c_uint32), ("chosen", C.c_uint32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("err", C.c_double),
@@ -181,7 +215,8 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsDebugLastGraphNodes", "amdAprilTagsSetPoseRefinement", "amdAprilTagsGetRefinedPoses",
            "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx", "amdAprilTagsDebugReconcile",
            "amdAprilTagsSetPoseCovariance", "amdAprilTagsGetRefinedPoseCovariances", "amdAprilTagsGetBundlePoseCovariancesEx",
-           "amdAprilTagsSetCornerUndistortion", "amdAprilTagsGetUndistortedDetections", "amdAprilTagsDebugUndistort"]
+           "amdAprilTagsSetCornerUndistortion", "amdAprilTagsGetUndistortedDetections", "amdAprilTagsDebugUndistort",
+           "amdAprilTagsSetRig", "amdAprilTagsSetRigSlots", "amdAprilTagsGetRigBundlePoses"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
@@ -278,7 +313,10 @@ def lib():
     L.amdAprilTagsSetCornerUndistortion.argtypes = [H, C.c_uint32, C.POINTER(CameraModelEx)]
     L.amdAprilTagsGetUndistortedDetections.argtypes = [H, C.c_uint32, C.POINTER(UndistortedDetection), C.c_uint32, C.POINTER(C.c_uint32)]
     L.amdAprilTagsDebugUndistort.argtypes = [H, C.c_uint32, C.c_void_p, C.POINTER(CameraModelEx), C.c_void_p, C.c_void_p]
-    L.amdAprilTagsDebugQuadSigmaTaps.argtypes = [C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.amdAprilTagsSetRig.argtypes = [H, C.c_uint32, C.POINTER(RigCamera)]
+    L.amdAprilTagsSetRigSlots.argtypes = [H, C.c_uint32, C.POINTER(RigSlot)]
+    L.amdAprilTagsGetRigBundlePoses.argtypes = [H, C.POINTER(RigBundlePose), C.c_uint32]
+    L.amdAprilTagsDebugQuadSigmaTaps.argtypes =[C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int or name in ("amdAprilTagsFamilyFromName", "amdAprilTagsEncodingFromName", "amdAprilTagsDistortionFromName"):

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "kernels_bundle.h"
 #include "kernels_rigid.h"
+#include "kernels_rig.h"
 #include "kernels_cc.h"
 #include "kernels_cluster.h"
 #include "kernels_decode.h"
@@ -310,6 +311,14 @@ struct amdAprilTagsDetector_st {
   DevBuf<UndistortCam> d_ucams;
   DevBuf<DetRec> d_dets_u;                              // max_batch x dcap, laid out and indexed as d_dets
   HostBuf<UndistortRec> h_udets;                        // pinned, max_batch x dcap: frame * ostride + record, as k_reconcile writes h_out
+  // amdAprilTagsSetRig / amdAprilTagsSetRigSlots: batch slot i of a submission is camera rig_slots[i].camera of group
+  // rig_slots[i].group (beyond the list: camera i % nrig of group i / nrig); each slot's group, camera and extrinsics travel through
+  // the pinned block h_rig, which k_prologue uploads with the frame descriptors
+  std::vector<amdAprilTagsRigCamera_t> rig_cams;        // post.nrig of them
+  std::vector<amdAprilTagsRigSlot_t> rig_slots;
+  HostBuf<RigSlotDev> h_rig;                            // pinned, one per batch slot
+  DevBuf<RigSlotDev> d_rig;
+  HostBuf<RigPoseRec> h_gposes;                         // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_rig writes group * nrigid + bundle
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1186,6 +1195,56 @@ int amdAprilTagsSetPoseCovariance(amdAprilTagsHandle handle, double corner_sigma
   return AMDAT_SUCCESS;
 }
 
+// The camera rig.  The first call that turns it on allocates the slot descriptors and the pinned record block; the extrinsics and
+// the slot map are host state that fill_rig writes into every submission's descriptors.
+int amdAprilTagsSetRig(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsRigCamera_t* cams) {
+  if (!handle || handle->inflight.active || (ncams && !cams) || ncams > AMDAT_MAX_RIG_CAMERAS) return AMDAT_INVALID_ARGUMENT;
+  static_assert(AMDAT_MAX_RIG_OBSERVATIONS == RG_SLOTS, "the header's bound is the kernel's: one lane holds one observation");
+  for (uint32_t c = 0; c < ncams; c++) {
+    for (int e = 0; e < 9; e++) if (!std::isfinite(cams[c].R[e])) return AMDAT_INVALID_ARGUMENT;
+    for (int e = 0; e < 3; e++) if (!std::isfinite(cams[c].t[e])) return AMDAT_INVALID_ARGUMENT;
+    if (!rigid_is_rotation(cams[c].R)) return AMDAT_INVALID_ARGUMENT;
+  }
+  if (ncams > 0) {
+    DeviceGuard guard(handle->device);
+    if (!guard.ok) return AMDAT_HIP_ERROR;
+    const size_t B = handle->cfg.max_batch;
+    static_assert(sizeof(RigSlotDev) % 4 == 0, "k_prologue copies words");
+    if (!ensure_host(handle, handle->h_rig, B * sizeof(RigSlotDev)) || !ensure_dev(handle, handle->d_rig, B * sizeof(RigSlotDev)) ||
+        !ensure_host(handle, handle->h_gposes, B * AMDAT_MAX_BUNDLES * sizeof(RigPoseRec)))
+      return AMDAT_OUT_OF_MEMORY;
+  }
+  set_post_mode(handle, POST_SET_RIG, ncams);   // (the extrinsics travel through the descriptors)
+  handle->rig_cams.assign(cams, cams + ncams);
+  return AMDAT_SUCCESS;
+}
+
+int amdAprilTagsSetRigSlots(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsRigSlot_t* slots) {
+  if (!handle || handle->inflight.active || (n && !slots) || n > handle->cfg.max_batch) return AMDAT_INVALID_ARGUMENT;
+  handle->rig_slots.assign(slots, slots + n);
+  return AMDAT_SUCCESS;
+}
+
+// The rig descriptors of a submission of n frames: each slot's group, camera and extrinsics.  AMDAT_INVALID_ARGUMENT, with nothing
+// enqueued: a group index at or above n, a camera index at or above the rig's count, one (group, camera) named by two slots.
+static int fill_rig(amdAprilTagsDetector_st* D, uint32_t n) {
+  const uint32_t ncams = D->post.nrig;
+  for (uint32_t i = 0; i < n; i++) {
+    amdAprilTagsRigSlot_t sl = {i / ncams, i % ncams};
+    if (i < D->rig_slots.size()) sl = D->rig_slots[i];
+    RigSlotDev& r = D->h_rig[i];
+    memset(&r, 0, sizeof(r));
+    r.group = sl.group; r.camera = sl.camera;
+    if (sl.camera == AMDAT_RIG_NO_CAMERA) continue;
+    if (sl.group >= n || sl.camera >= ncams) return AMDAT_INVALID_ARGUMENT;
+    for (uint32_t j = 0; j < i; j++)
+      if (D->h_rig[j].camera == sl.camera && D->h_rig[j].group == sl.group) return AMDAT_INVALID_ARGUMENT;
+    for (int e = 0; e < 9; e++) r.R[e] = D->rig_cams[sl.camera].R[e];
+    for (int e = 0; e < 3; e++) r.t[e] = D->rig_cams[sl.camera].t[e];
+  }
+  return AMDAT_SUCCESS;
+}
+
 // Record i of `frame` of the last submission was refined from an invalid undistorted twin.
 static bool undistorted_invalid(const amdAprilTagsDetector_st* D, uint32_t frame, uint32_t i) {
   return D->last.post.nundist && D->h_udets[(size_t)frame * D->last.ostride + i].det.status != AMDAT_UNDISTORT_OK;
@@ -1234,6 +1293,12 @@ int amdAprilTagsGetBundlePosesEx(amdAprilTagsHandle handle, amdAprilTagsBundlePo
 int amdAprilTagsGetBundlePoseCovariancesEx(amdAprilTagsHandle handle, amdAprilTagsPoseCovariance_t* out, uint32_t nframes) {
   if (!handle) return AMDAT_INVALID_ARGUMENT;
   return get_bundle_records(handle, POST_RIGID | POST_COV, &PostMode::nrigid, handle->h_xcovs, &PoseCovRec::c, out, nframes);
+}
+
+// (ngroups x bundles: a group index per frame of the submission, every entry written)
+int amdAprilTagsGetRigBundlePoses(amdAprilTagsHandle handle, amdAprilTagsRigBundlePose_t* out, uint32_t ngroups) {
+  if (!handle) return AMDAT_INVALID_ARGUMENT;
+  return get_bundle_records(handle, POST_RIGID | POST_RIG, &PostMode::nrigid, handle->h_gposes, &RigPoseRec::pose, out, ngroups);
 }
 
 int amdAprilTagsGetUndistortedDetections(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsUndistortedDetection_t* out, uint32_t capacity, uint32_t* n) {
@@ -1487,11 +1552,13 @@ static void launch_threshold(amdAprilTagsDetector_st* D, const DetParams& P, uin
 __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ host_frames, uint32_t* __restrict__ frames,
                                                  uint32_t* __restrict__ workctl, uint32_t* __restrict__ counters, int fd_words, int fc_words,
                                                  const uint32_t* __restrict__ host_front, uint32_t* __restrict__ front, int front_words,
-                                                 const uint32_t* __restrict__ host_ucams, uint32_t* __restrict__ ucams, int ucam_words) {
+                                                 const uint32_t* __restrict__ host_ucams, uint32_t* __restrict__ ucams, int ucam_words,
+                                                 const uint32_t* __restrict__ host_rig, uint32_t* __restrict__ rig, int rig_words) {
   const int frame = (int)blockIdx.x, t = (int)threadIdx.x;
   for (int i = t; i < fd_words; i += 64) frames[frame * fd_words + i] = host_frames[frame * fd_words + i];
   for (int i = t; i < front_words; i += 64) front[frame * front_words + i] = host_front[frame * front_words + i];   // (no front stage: no words)
   for (int i = t; i < ucam_words; i += 64) ucams[frame * ucam_words + i] = host_ucams[frame * ucam_words + i];   // (no corner undistortion: no words)
+  for (int i = t; i < rig_words; i += 64) rig[frame * rig_words + i] = host_rig[frame * rig_words + i];   // (no camera rig: no words)
   for (int i = t; i < fc_words; i += 64) counters[frame * fc_words + i] = 0u;
   if (frame == 0 && t < 32) workctl[t] = 0u;
 }
@@ -1628,6 +1695,10 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
       case POST_K_REFINE:      // S11: both minima of the records handed out, eight lanes per record (kernels_pose.h)
         if (st.cov) POSE_LAUNCH(true); else POSE_LAUNCH(false);
         break;
+      case POST_K_RIG:         // S13: two waves per (group, bundle) over the records of all the group's frames (kernels_rig.h)
+        hipLaunchKernelGGL(k_bundle_rig, grid, dim3(128), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, D->d_rigid_head,
+                           D->d_rigid_members, D->d_rigid_table, D->d_rig, D->h_gposes, P);
+        break;
     }
 #undef RIGID_LAUNCH
 #undef POSE_LAUNCH
@@ -1651,7 +1722,9 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
                      static_cast<const uint32_t*>(D->h_front.p), static_cast<uint32_t*>(D->d_front.p),
                      resize || rect ? (int)(sizeof(FrontDesc) / 4) : 0,
                      static_cast<const uint32_t*>(D->h_ucams.p), static_cast<uint32_t*>(D->d_ucams.p),
-                     D->last.post.nundist ? (int)(sizeof(UndistortCam) / 4) : 0);
+                     D->last.post.nundist ? (int)(sizeof(UndistortCam) / 4) : 0,
+                     reinterpret_cast<const uint32_t*>(D->h_rig.p), reinterpret_cast<uint32_t*>(D->d_rig.p),
+                     D->last.post.nrig ? (int)(sizeof(RigSlotDev) / 4) : 0);
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
@@ -1826,8 +1899,9 @@ static int finish_once(amdAprilTagsDetector_st* D, hipStream_t s) {
     const struct { const void* p; size_t size, seq; } blocks[] = {
         {D->h_udets.p, sizeof(UndistortRec), offsetof(UndistortRec, seq)}, {D->h_bposes.p, sizeof(BundlePoseRec), offsetof(BundlePoseRec, seq)},
         {D->h_xposes.p, sizeof(RigidPoseRec), offsetof(RigidPoseRec, seq)}, {D->h_xcovs.p, sizeof(PoseCovRec), offsetof(PoseCovRec, seq)},
-        {D->h_rposes.p, sizeof(PoseRefineRec), offsetof(PoseRefineRec, seq)}, {D->h_rcovs.p, sizeof(PoseCovRec), offsetof(PoseCovRec, seq)}};
-    static_assert(POST_B_UDETS == 0 && POST_B_BPOSES == 1 && POST_B_XPOSES == 2 && POST_B_XCOVS == 3 && POST_B_RPOSES == 4 && POST_B_RCOVS == 5, "blocks[]");
+        {D->h_rposes.p, sizeof(PoseRefineRec), offsetof(PoseRefineRec, seq)}, {D->h_rcovs.p, sizeof(PoseCovRec), offsetof(PoseCovRec, seq)},
+        {D->h_gposes.p, sizeof(RigPoseRec), offsetof(RigPoseRec, seq)}};
+    static_assert(POST_B_UDETS == 0 && POST_B_BPOSES == 1 && POST_B_XPOSES == 2 && POST_B_XCOVS == 3 && POST_B_RPOSES == 4 && POST_B_RCOVS == 5 && POST_B_GPOSES == 6, "blocks[]");
     const PostPlan post = plan_post(D->last.post, D->launched_n, D->last.ostride);
     for (int i = 0; i < post.nsteps; i++)
       for (int j = 0; j < post.steps[i].nwrites; j++) {
@@ -1919,6 +1993,7 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   DeviceGuard guard(D->device);
   if (!guard.ok) return AMDAT_HIP_ERROR;
   if (D->unusable) return AMDAT_OUT_OF_MEMORY;   // (never launch on the half-allocated buffers of a failed regrowth)
+  if (D->post.nrig) { const int rrc = fill_rig(D, n); if (rrc) return rrc; }   // (refused before anything of the submission is written)
   const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
   const bool resized = !D->resize_sizes.empty(), rectified = !resized && !D->rect_models.empty();   // (resized: the rectified plane is never formed)
   if (resized || rectified) {   // from here on a mono8 submission of the front plane's slots at their target sizes

@@ -51,6 +51,9 @@ struct DetectorApi {
   decltype(&amdAprilTagsGetBundlePoses) get_bundle_poses = nullptr;
   decltype(&amdAprilTagsSetBundlesEx) set_bundles_ex = nullptr;
   decltype(&amdAprilTagsGetBundlePosesEx) get_bundle_poses_ex = nullptr;
+  decltype(&amdAprilTagsSetRig) set_rig = nullptr;
+  decltype(&amdAprilTagsSetRigSlots) set_rig_slots = nullptr;
+  decltype(&amdAprilTagsGetRigBundlePoses) get_rig_bundle_poses = nullptr;
   decltype(&amdAprilTagsSetPoseRefinement) set_pose_refinement = nullptr;
   decltype(&amdAprilTagsGetRefinedPoses) get_refined_poses = nullptr;
   decltype(&amdAprilTagsSetPoseCovariance) set_pose_covariance = nullptr;
@@ -101,6 +104,9 @@ DetectorApi& api() {
   BIND(get_bundle_poses, "amdAprilTagsGetBundlePoses")
   BIND(set_bundles_ex, "amdAprilTagsSetBundlesEx")
   BIND(get_bundle_poses_ex, "amdAprilTagsGetBundlePosesEx")
+  BIND(set_rig, "amdAprilTagsSetRig")
+  BIND(set_rig_slots, "amdAprilTagsSetRigSlots")
+  BIND(get_rig_bundle_poses, "amdAprilTagsGetRigBundlePoses")
   BIND(set_pose_refinement, "amdAprilTagsSetPoseRefinement")
   BIND(get_refined_poses, "amdAprilTagsGetRefinedPoses")
   BIND(set_pose_covariance, "amdAprilTagsSetPoseCovariance")
@@ -421,6 +427,56 @@ bool collect_rigid_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, 
       tf.transform.rotation = quaternion_from_colmajor(o);
       tfs[f]->push_back(tf);
     }
+  }
+  return true;
+}
+
+// NodeOptions::rig_cameras on a freshly created handle of S streams: one extrinsic per stream, beside rigid_bundles.
+void apply_rig(amdAprilTagsHandle detector, const NodeOptions& opt, uint32_t S) {
+  if (opt.rig_cameras.empty()) return;
+  if (opt.rig_cameras.size() != S) throw std::runtime_error("'rig_cameras' must give one camera per stream");
+  if (opt.rigid_bundles.empty()) throw std::runtime_error("'rig_cameras' is set without 'rigid_bundles': the rig solves rigid bundles");
+  std::vector<amdAprilTagsRigCamera_t> cams(S);
+  for (uint32_t s = 0; s < S; s++) {
+    for (int i = 0; i < 9; i++) cams[s].R[i] = opt.rig_cameras[s].R[i];
+    for (int i = 0; i < 3; i++) cams[s].t[i] = opt.rig_cameras[s].t[i];
+  }
+  const int error = api().set_rig(detector, S, cams.data());
+  if (error != 0) throw std::runtime_error("'rig_cameras' refused (error code " + std::to_string(error) + ")");
+}
+
+// NodeOptions::rig_cameras: the records of amdAprilTagsGetRigBundlePoses for group 0, the round, and one transform per solved bundle
+// from the chosen pose under the rig frame.  who[i]: the stream of batch slot i.
+bool collect_rig_bundles(amdAprilTagsHandle detector, const NodeOptions& opt, const std::vector<uint32_t>& who, const Header& first,
+                         std::vector<RigBundlePose>* poses, std::vector<TransformStamped>* tfs) {
+  poses->clear();
+  const size_t nb = opt.rigid_bundles.size();
+  if (opt.rig_cameras.empty() || nb == 0) return true;
+  std::vector<amdAprilTagsRigBundlePose_t> recs(nb);
+  if (api().get_rig_bundle_poses(detector, recs.data(), 1) != 0) return false;
+  for (size_t b = 0; b < nb; b++) {
+    const amdAprilTagsRigBundlePose_t& r = recs[b];
+    RigBundlePose p;
+    p.name = opt.rigid_bundles[b].name;
+    p.status = r.status; p.nobs = r.nobs; p.nskipped = r.nskipped; p.ndropped = r.ndropped; p.ncams = r.ncams;
+    p.seed_stream = r.seed_frame < who.size() ? who[r.seed_frame] : 0; p.seed = r.seed; p.chosen = r.chosen;
+    p.err = r.err; p.sq_err_sum = r.sq_err_sum; p.err_alt = r.err_alt; p.sq_err_sum_alt = r.sq_err_sum_alt;
+    for (int i = 0; i < 9; i++) { p.R[i] = r.R[i]; p.R_alt[i] = r.R_alt[i]; }
+    for (int i = 0; i < 3; i++) { p.t[i] = r.t[i]; p.t_alt[i] = r.t_alt[i]; }
+    poses->push_back(p);
+    if (r.status != AMDAT_BUNDLE_SOLVED) continue;
+    TransformStamped tf;
+    tf.header = first;
+    tf.header.frame_id = opt.rig_frame_id;
+    tf.child_frame_id = "rig_bundle:" + p.name;
+    tf.transform.translation.x = r.t[0];
+    tf.transform.translation.y = r.t[1];
+    tf.transform.translation.z = r.t[2];
+    float o[9];   // column-major float, the form a tag's orientation has
+    for (int rr = 0; rr < 3; rr++)
+      for (int c = 0; c < 3; c++) o[c * 3 + rr] = static_cast<float>(r.R[rr * 3 + c]);
+    tf.transform.rotation = quaternion_from_colmajor(o);
+    tfs->push_back(tf);
   }
   return true;
 }
@@ -814,6 +870,7 @@ struct AprilTagMultiCameraNode::Impl {
   std::vector<Slot> slots;
   std::vector<std::vector<BundlePose>> last_bundles;   // per stream (NodeOptions::bundles)
   std::vector<std::vector<RigidBundlePose>> last_rigid;   // per stream (NodeOptions::rigid_bundles)
+  std::vector<RigBundlePose> last_rig;                 // of the last round (NodeOptions::rig_cameras)
 
   void Initialize(const CameraInfo& info) {
     if (opt.max_tags <= 0) throw std::runtime_error("'max_tags' must be positive");
@@ -848,6 +905,7 @@ struct AprilTagMultiCameraNode::Impl {
     apply_rigid_bundles(detector, opt);
     apply_pose_refinement(detector, opt);
     apply_pose_covariance(detector, opt);
+    apply_rig(detector, opt, S);
     width = cfg.width;
     height = cfg.height;
     pitch = (static_cast<size_t>(width) + 63) & ~static_cast<size_t>(63);
@@ -946,6 +1004,7 @@ void AprilTagMultiCameraNode::set_auto_flush(bool on) { impl_->auto_flush = on; 
 uint32_t AprilTagMultiCameraNode::num_streams() const { return impl_->S; }
 const std::vector<BundlePose>& AprilTagMultiCameraNode::last_bundle_poses(uint32_t stream) const { return impl_->last_bundles.at(stream); }
 const std::vector<RigidBundlePose>& AprilTagMultiCameraNode::last_rigid_bundle_poses(uint32_t stream) const { return impl_->last_rigid.at(stream); }
+const std::vector<RigBundlePose>& AprilTagMultiCameraNode::last_rig_bundle_poses() const { return impl_->last_rig; }
 const NodeOptions& AprilTagMultiCameraNode::options() const { return impl_->opt; }
 
 bool AprilTagMultiCameraNode::CameraImageCallback(uint32_t stream, const Image& image, const CameraInfo& camera_info) {
@@ -1020,6 +1079,15 @@ uint32_t AprilTagMultiCameraNode::Flush() {
       return 0;
     }
   }
+  if (!I.opt.rig_cameras.empty()) {   // one instant: every served stream is its own camera of group 0 (host state of the handle)
+    std::vector<amdAprilTagsRigSlot_t> rig_slots(n);
+    for (uint32_t i = 0; i < n; i++) rig_slots[i] = {0u, who[i]};
+    if (api().set_rig_slots(I.detector, n, rig_slots.data()) != 0) {   // (a round whose slot map was refused must not run with a stale one)
+      std::fprintf(stderr, "[apriltag_node] rig slot map refused: round dropped\n");
+      for (uint32_t s : who) I.slots[s].pending = false;
+      return 0;
+    }
+  }
   const int error = api().detect_batch(I.detector, n, imgs.data(), intr.data(), tags.data(), counts.data(), max_tags, nullptr);
   for (uint32_t s : who) I.slots[s].pending = false;
   if (error != 0) {
@@ -1057,6 +1125,12 @@ uint32_t AprilTagMultiCameraNode::Flush() {
     std::fprintf(stderr, "[apriltag_node] rigid bundle records not available: round dropped\n");
     return 0;
   }
+  std::vector<RigBundlePose> rig;
+  if (!collect_rig_bundles(I.detector, I.opt, who, *headers[0], &rig, tf_ptrs[0])) {
+    std::fprintf(stderr, "[apriltag_node] rig bundle records not available: round dropped\n");
+    return 0;
+  }
+  I.last_rig = rig;
   for (uint32_t i = 0; i < n; i++) {
     I.last_bundles[who[i]] = poses[i];
     I.last_rigid[who[i]] = rigid[i];
@@ -1564,6 +1638,55 @@ MultiShellHarness* node_shell_multi_create_rigid_bundles(int num_streams, int ma
     if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
     return nullptr;
   }
+}
+// NodeOptions::rig_cameras through the flat view: twelve doubles per stream -- R row-major, then t -- beside rigid_bundles
+struct NodeShellRigBundlePose {
+  char name[32];
+  uint32_t status, nobs, nskipped, ndropped, ncams, seed_stream, seed, chosen;
+  double R[9], t[3], err, sq_err_sum, R_alt[9], t_alt[3], err_alt, sq_err_sum_alt;
+};
+MultiShellHarness* node_shell_multi_create_rig(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                               const char* backends, int decimate, int auto_flush, int nbundles,
+                                               const NodeShellRigidBundle* bundles, int ncams, const double* cams12, const char* rig_frame_id,
+                                               char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    set_rigid_bundle_options(&o, nbundles, bundles);
+    for (int c = 0; c < ncams; c++) {
+      amd::isaac_ros::apriltag::RigCamera cam;
+      for (int i = 0; i < 9; i++) cam.R[i] = cams12[12 * c + i];
+      for (int i = 0; i < 3; i++) cam.t[i] = cams12[12 * c + 9 + i];
+      o.rig_cameras.push_back(cam);
+    }
+    if (rig_frame_id) o.rig_frame_id = rig_frame_id;
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+int node_shell_multi_last_rig_bundle_poses(MultiShellHarness* h, NodeShellRigBundlePose* out, int max_out) {
+  const std::vector<amd::isaac_ros::apriltag::RigBundlePose>& poses = h->node->last_rig_bundle_poses();
+  const int n = static_cast<int>(poses.size());
+  for (int i = 0; i < n && i < max_out; i++) {
+    NodeShellRigBundlePose& o = out[i];
+    std::memset(&o, 0, sizeof(o));
+    std::strncpy(o.name, poses[i].name.c_str(), sizeof(o.name) - 1);
+    o.status = poses[i].status; o.nobs = poses[i].nobs; o.nskipped = poses[i].nskipped; o.ndropped = poses[i].ndropped;
+    o.ncams = poses[i].ncams; o.seed_stream = poses[i].seed_stream; o.seed = poses[i].seed; o.chosen = poses[i].chosen;
+    for (int k = 0; k < 9; k++) { o.R[k] = poses[i].R[k]; o.R_alt[k] = poses[i].R_alt[k]; }
+    for (int k = 0; k < 3; k++) { o.t[k] = poses[i].t[k]; o.t_alt[k] = poses[i].t_alt[k]; }
+    o.err = poses[i].err; o.sq_err_sum = poses[i].sq_err_sum; o.err_alt = poses[i].err_alt; o.sq_err_sum_alt = poses[i].sq_err_sum_alt;
+  }
+  return n;
 }
 int node_shell_multi_last_rigid_bundle_poses(MultiShellHarness* h, int stream, NodeShellRigidBundlePose* out, int max_out) {
   return copy_rigid_bundle_poses(h->node->last_rigid_bundle_poses(static_cast<uint32_t>(stream)), out, max_out);

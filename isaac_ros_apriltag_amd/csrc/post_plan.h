@@ -7,16 +7,17 @@
 
 #include "../../include/apriltag_amd.h"   // AMDAT_MAX_BUNDLES
 
-// What the five setters set.  The undistortion models and the device-resident layouts, iteration count and sigma^2 stay with the handle.
+// What the six setters set.  The undistortion models and the device-resident layouts, iteration count and sigma^2 stay with the handle.
 struct PostMode {
   uint32_t nbundles = 0;          // amdAprilTagsSetBundles: planar bundles, 0: off
   uint32_t nrigid = 0;            // amdAprilTagsSetBundlesEx: rigid bundles, 0: off (one kind is on at a time)
   uint32_t pose_iterations = 0;   // amdAprilTagsSetPoseRefinement, 0: off
   double cov_sigma = 0.0;         // amdAprilTagsSetPoseCovariance: corner sigma in pixels, 0: off
   uint32_t nundist = 0;           // amdAprilTagsSetCornerUndistortion: camera models, 0: off
+  uint32_t nrig = 0;              // amdAprilTagsSetRig: rig cameras, 0: off (the stage runs where the rigid kind is on)
 };
 
-enum PostSetting { POST_SET_PLANAR, POST_SET_RIGID, POST_SET_REFINE, POST_SET_COV, POST_SET_UNDISTORT };
+enum PostSetting { POST_SET_PLANAR, POST_SET_RIGID, POST_SET_REFINE, POST_SET_COV, POST_SET_UNDISTORT, POST_SET_RIG };
 
 // The mode after a setter's request (a count, or the sigma).  Turning one bundle kind on turns the other off; turning it off leaves
 // the other alone.
@@ -28,6 +29,7 @@ static inline PostMode post_apply(PostMode m, PostSetting what, double value) {
     case POST_SET_REFINE: m.pose_iterations = count; break;
     case POST_SET_COV: m.cov_sigma = value; break;
     case POST_SET_UNDISTORT: m.nundist = count; break;
+    case POST_SET_RIG: m.nrig = count; break;
   }
   return m;
 }
@@ -35,18 +37,19 @@ static inline PostMode post_apply(PostMode m, PostSetting what, double value) {
 // What a captured graph holds of the mode: each stage on or off.  Counts, layouts, the iteration number, sigma and the models live
 // in device memory or travel through the descriptors, so a setter retires the graphs if and only if this key changes -- the
 // covariance bit included where neither pose launch runs.
-enum : uint32_t { POST_UNDISTORT = 1u, POST_PLANAR = 2u, POST_RIGID = 4u, POST_REFINE = 8u, POST_COV = 16u };
+enum : uint32_t { POST_UNDISTORT = 1u, POST_PLANAR = 2u, POST_RIGID = 4u, POST_REFINE = 8u, POST_COV = 16u, POST_RIG = 32u };
 static inline uint32_t post_graph_key(const PostMode& m) {
   return (m.nundist ? POST_UNDISTORT : 0u) | (m.nbundles ? POST_PLANAR : 0u) | (m.nrigid ? POST_RIGID : 0u) |
-         (m.pose_iterations ? POST_REFINE : 0u) | (m.cov_sigma > 0.0 ? POST_COV : 0u);
+         (m.pose_iterations ? POST_REFINE : 0u) | (m.cov_sigma > 0.0 ? POST_COV : 0u) | (m.nrig ? POST_RIG : 0u);
 }
 
-// The launches: k_undistort_records, k_bundle_pose, k_bundle_rigid<cov>, k_pose_refine<cov>.
-enum PostKernel { POST_K_UNDISTORT, POST_K_PLANAR, POST_K_RIGID, POST_K_REFINE };
-// The pinned blocks they write: h_udets, h_bposes, h_xposes, h_xcovs, h_rposes, h_rcovs.
-enum PostBlock { POST_B_UDETS, POST_B_BPOSES, POST_B_XPOSES, POST_B_XCOVS, POST_B_RPOSES, POST_B_RCOVS };
-// How a block is indexed: frame * per_frame + bundle, every entry written; or frame * per_frame + record, the first
-// min(nout, per_frame) of a frame written, as k_reconcile writes its own.
+// The launches: k_undistort_records, k_bundle_pose, k_bundle_rigid<cov>, k_pose_refine<cov>, k_bundle_rig.
+enum PostKernel { POST_K_UNDISTORT, POST_K_PLANAR, POST_K_RIGID, POST_K_REFINE, POST_K_RIG };
+// The pinned blocks they write: h_udets, h_bposes, h_xposes, h_xcovs, h_rposes, h_rcovs, h_gposes.
+enum PostBlock { POST_B_UDETS, POST_B_BPOSES, POST_B_XPOSES, POST_B_XCOVS, POST_B_RPOSES, POST_B_RCOVS, POST_B_GPOSES };
+// How a block is indexed: frame * per_frame + bundle, every entry written (h_gposes: group * per_frame + bundle, a group index per
+// frame of the submission, every entry written); or frame * per_frame + record, the first min(nout, per_frame) of a frame written,
+// as k_reconcile writes its own.
 enum PostIndex { POST_BY_BUNDLE, POST_BY_RECORD };
 
 constexpr uint32_t POST_UD_WAVES = 16;           // kernels_undistort.h: UD_WAVES_PER_FRAME
@@ -67,7 +70,7 @@ struct PostStep {
 };
 struct PostPlan {
   int nsteps;
-  PostStep steps[4];    // in enqueue order, all on the submission stream
+  PostStep steps[5];    // in enqueue order, all on the submission stream
 };
 
 // What a submission of n frames with `ostride` record slots per frame launches behind k_reconcile.
@@ -93,5 +96,8 @@ static inline PostPlan plan_post(const PostMode& m, uint32_t n, uint32_t ostride
     writes(s, POST_B_RPOSES, POST_BY_RECORD, ostride);
     if (cov) writes(s, POST_B_RCOVS, POST_BY_RECORD, ostride);
   }
+  // the camera rig, behind the other pose launches and only beside the rigid kind: one block per (group, bundle) over every frame's
+  // records, raw or twins as they read them, never a covariance
+  if (m.nrig && m.nrigid) writes(step(POST_K_RIG, false, twins, AMDAT_MAX_BUNDLES), POST_B_GPOSES, POST_BY_BUNDLE, m.nrigid);
   return p;
 }

@@ -85,7 +85,13 @@
 //                               wrong only where a corner of the chosen set is the tenth largest maximum
 //                           45 = fq_corner_search without its dot test: a corner choice whose first two sides are nearly parallel is
 //                               admitted
-//                           (4 .. 45 change values only: no address, index bound or launch size; 43 and 44 run their removal loop
+//                           46 = the translation statement of the rig pose (rig_pose.h) leaves the ray origin out: wrong wherever a
+//                               camera of the rig is not at the rig's origin
+//                           47 = the ray direction of the rig pose takes Rc in place of its transpose: wrong wherever a camera of the
+//                               rig is turned against the rig frame
+//                           48 = k_bundle_rig cuts the observation slots at 63: wrong only where a (group, bundle) has 64 or more
+//                               used observations
+//                           (4 .. 48 change values only: no address, index bound or launch size; 43 and 44 run their removal loop
 //                           one round less)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
@@ -101,7 +107,8 @@
 //                           tests/test_pose_covariance_gpu.py::test_the_pose_covariance_tests_fail_on_the_wrong_builds for 25 .. 27,
 //                           tests/test_corner_undistortion_gpu.py::test_the_undistortion_tests_fail_on_the_wrong_builds for 28 .. 30,
 //                           tests/test_integer_stages_gpu.py::test_integer_stage_tests_fail_on_the_wrong_builds for 31 .. 36,
-//                           tests/test_fit_rules_gpu.py::test_the_fit_rule_tests_fail_on_the_wrong_builds for 37 .. 45)
+//                           tests/test_fit_rules_gpu.py::test_the_fit_rule_tests_fail_on_the_wrong_builds for 37 .. 45,
+//                           tests/test_rig_bundles_gpu.py::test_the_rig_tests_fail_on_the_wrong_builds for 46 .. 48)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -290,6 +297,24 @@
 #define RIGID_NPTS(n) ((void)(n), 4.0)
 #else
 #define RIGID_NPTS(n) (n)
+#endif
+
+// ---- camera rigs (rig_pose.h, kernels_rig.h): the ray origin as the translation statement sees it, entry (i, k) of the matrix that
+// ---- carries a viewing ray into the rig frame (Rc^T), and the number of observation slots a solve fills ------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 46
+#define RIG_T_ORIGIN(o) ((void)(o), 0.0)
+#else
+#define RIG_T_ORIGIN(o) (o)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 47
+#define RIG_RAY_R(R, i, k) ((R)[3 * (i) + (k)])
+#else
+#define RIG_RAY_R(R, i, k) ((R)[3 * (k) + (i)])
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 48
+#define RIG_SLOT_CUT 63u
+#else
+#define RIG_SLOT_CUT 64u
 #endif
 
 // ---- pose_covariance.h: the skew term of J_u; the pose the second quad of k_pose_refine<true> evaluates at (own: its chain's entry,

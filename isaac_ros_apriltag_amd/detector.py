@@ -51,7 +51,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, **caps):
+                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, rig=None, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -103,6 +103,8 @@ class AprilTagDetector:
                 self.set_pose_refinement(pose_refinement)
             if pose_covariance:
                 self.set_pose_covariance(pose_covariance)
+            if rig:
+                self.set_rig(rig)
         except Exception:
             self.close()
             raise
@@ -181,6 +183,37 @@ class AprilTagDetector:
                   "sq_err_sum": float(r.sq_err_sum), "R_alt": np.array(list(r.R_alt)).reshape(3, 3), "t_alt": np.array(list(r.t_alt)),
                   "err_alt": float(r.err_alt), "sq_err_sum_alt": float(r.sq_err_sum_alt)}
                  for r in out[f * self.nbundles_ex:(f + 1) * self.nbundles_ex]] for f in range(n)]
+
+    def set_rig(self, cams):
+        """amdAprilTagsSetRig: cams is a list of (R, t), one per camera of a calibrated rig, the RIG frame in the CAMERA frame
+        (X_cam = R X_rig + t).  Every following submission in which set_bundles_ex is on solves one pose per group of frames (the
+        cameras of one instant: set_rig_slots) and rigid bundle, in the rig frame, over the tags of all the group's cameras at once;
+        the per-frame records stay as they are.  None or [] turns it off.  rig_bundle_poses(ngroups) hands out the records."""
+        arr = capi.rig_cameras(cams)
+        capi._check("amdAprilTagsSetRig", self._L.amdAprilTagsSetRig(self._h, len(arr) if arr is not None else 0, arr))
+
+    def set_rig_slots(self, slots):
+        """amdAprilTagsSetRigSlots: slots is a list of (group, camera) for batch slots 0 .. len(slots) - 1 of the submissions that
+        follow (camera capi.RIG_NO_CAMERA: the slot belongs to no group); the slots beyond, and all of them for None or [], follow
+        the default map: camera i % ncams of group i / ncams."""
+        slots = list(slots or [])
+        arr = (capi.RigSlot * max(len(slots), 1))()
+        for i, (g, c) in enumerate(slots):
+            arr[i].group, arr[i].camera = int(g), int(c)
+        capi._check("amdAprilTagsSetRigSlots", self._L.amdAprilTagsSetRigSlots(self._h, len(slots), arr if slots else None))
+
+    def rig_bundle_poses(self, ngroups):
+        """amdAprilTagsGetRigBundlePoses: the rig records of the first ngroups groups of the last completed submission, a list per
+        group of {"group", "bundle", "status", "nobs", "nskipped", "ndropped", "ncams", "seed_frame", "seed", "chosen", "R" (3x3), "t",
+        "err", "sq_err_sum", "R_alt", "t_alt", "err_alt", "sq_err_sum_alt"} in the order of set_bundles_ex."""
+        nb = self.nbundles_ex
+        out = (capi.RigBundlePose * max(ngroups * nb, 1))()
+        capi._check("amdAprilTagsGetRigBundlePoses", self._L.amdAprilTagsGetRigBundlePoses(self._h, out, ngroups))
+        ints = ("group", "bundle", "status", "nobs", "nskipped", "ndropped", "ncams", "seed_frame", "seed", "chosen")
+        return [[dict({k: int(getattr(r, k)) for k in ints}, R=np.array(list(r.R)).reshape(3, 3), t=np.array(list(r.t)), err=float(r.err),
+                      sq_err_sum=float(r.sq_err_sum), R_alt=np.array(list(r.R_alt)).reshape(3, 3), t_alt=np.array(list(r.t_alt)),
+                      err_alt=float(r.err_alt), sq_err_sum_alt=float(r.sq_err_sum_alt))
+                 for r in out[g * nb:(g + 1) * nb]] for g in range(ngroups)]
 
     def set_pose_refinement(self, iterations):
         """amdAprilTagsSetPoseRefinement: every following submission refines the records it hands out by orthogonal iteration from two

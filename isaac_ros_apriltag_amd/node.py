@@ -218,6 +218,14 @@ def _unpack_rigid_bundle_poses(out, n):
              "R_alt": list(p.R_alt), "t_alt": list(p.t_alt), "err_alt": float(p.err_alt), "sq_err_sum_alt": float(p.sq_err_sum_alt)} for p in out[:n]]
 
 
+class ShellRigBundlePose(C.Structure):
+    """NodeShellRigBundlePose: the rig record of one rigid bundle for one round (include/apriltag_node_shell.hpp: RigBundlePose)."""
+    _fields_ = [("name", C.c_char * 32), ("status", C.c_uint32), ("nobs", C.c_uint32), ("nskipped", C.c_uint32), ("ndropped", C.c_uint32),
+                ("ncams", C.c_uint32), ("seed_stream", C.c_uint32), ("seed", C.c_uint32), ("chosen", C.c_uint32), ("R", C.c_double * 9),
+                ("t", C.c_double * 3), ("err", C.c_double), ("sq_err_sum", C.c_double), ("R_alt", C.c_double * 9), ("t_alt", C.c_double * 3),
+                ("err_alt", C.c_double), ("sq_err_sum_alt", C.c_double)]
+
+
 def _unpack_transforms(out, n):
     return [{"child_frame_id": t.child_frame_id.decode(), "frame_id": t.frame_id.decode(), "stamp": (t.sec, t.nanosec),
              "translation": list(t.translation), "rotation_xyzw": list(t.rotation_xyzw)} for t in out[:n]]
@@ -296,8 +304,11 @@ class AprilTagMultiCameraNode:
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
                  auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None, pose_refinement=0,
-                 rigid_bundles=None, pose_covariance=0.0):
-        """max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
+                 rigid_bundles=None, pose_covariance=0.0, rig_cameras=None, rig_frame_id="rig"):
+        """rig_cameras (NodeOptions::rig_cameras, with rigid_bundles and nothing else): [(R, t)] per stream, the rig frame in the
+        camera frame -- every round is one instant of the rig: one "rig_bundle:<name>" transform per solved bundle under rig_frame_id
+        behind the first served stream's transforms, and rig_bundle_poses() hands out the records.
+        max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
         sizes); 0: one size, the first frame's, and frames of another size are dropped.  rectify (NodeOptions): every stream's frames are
         undistorted inside the submission with the plumb_bob model of its CameraInfo (on_frame: D, distortion_model, P12); "full"
         (NodeOptions::rectify_full): with any of the three distortion models and the rotation R of its CameraInfo; "corners"
@@ -316,6 +327,23 @@ class AprilTagMultiCameraNode:
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags, self.num_streams = max_tags, num_streams
+        if rig_cameras:
+            if bundles or pose_refinement or quad_sigma or max_width or max_height or rectify or resize or pose_covariance:
+                raise ValueError("rig_cameras is served with rigid_bundles by this view, and with nothing else")
+            arr = _shell_rigid_bundles(rigid_bundles or [])
+            flat = [float(v) for (R, t) in rig_cameras for part in (R, t) for row in part for v in (row if hasattr(row, "__iter__") else (row,))]
+            if len(flat) != 12 * len(rig_cameras):
+                raise ValueError("rig_cameras: every camera is (R of nine entries, t of three)")
+            self._L.node_shell_multi_create_rig.restype = C.c_void_p
+            self._L.node_shell_multi_create_rig.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int,
+                                                            C.POINTER(ShellRigidBundle), C.c_int, C.POINTER(C.c_double), C.c_char_p, C.c_char_p,
+                                                            C.c_size_t]
+            self._h = self._L.node_shell_multi_create_rig(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                          1 if auto_flush else 0, len(arr), arr, len(rig_cameras), (C.c_double * len(flat))(*flat),
+                                                          rig_frame_id.encode(), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if pose_covariance:
             if bundles or quad_sigma or max_width or max_height or rectify or resize or not (pose_refinement or rigid_bundles):
                 raise ValueError("pose_covariance is served with pose_refinement and / or rigid_bundles by this view, and with nothing else")
@@ -407,6 +435,17 @@ class AprilTagMultiCameraNode:
     def covariances(self, stream):
         """detection.pose.pose.covariance of the last message published for `stream`: one 6 x 6 array per detection."""
         return _covariances(lambda out, n: self._L.node_shell_multi_last_covariances(self._h, stream, out, n), self.max_tags)
+
+    def rig_bundle_poses(self, max_out=8):
+        """NodeOptions::rig_cameras: the rig records of the last round, one per rigid bundle."""
+        out = (ShellRigBundlePose * max_out)()
+        self._L.node_shell_multi_last_rig_bundle_poses.restype = C.c_int
+        self._L.node_shell_multi_last_rig_bundle_poses.argtypes = [C.c_void_p, C.POINTER(ShellRigBundlePose), C.c_int]
+        n = min(self._L.node_shell_multi_last_rig_bundle_poses(self._h, out, max_out), max_out)
+        ints = ("status", "nobs", "nskipped", "ndropped", "ncams", "seed_stream", "seed", "chosen")
+        return [dict({k: int(getattr(p, k)) for k in ints}, name=p.name.decode(), R=list(p.R), t=list(p.t), err=float(p.err),
+                     sq_err_sum=float(p.sq_err_sum), R_alt=list(p.R_alt), t_alt=list(p.t_alt), err_alt=float(p.err_alt),
+                     sq_err_sum_alt=float(p.sq_err_sum_alt)) for p in out[:n]]
 
     def rigid_bundle_covariances(self, stream, max_out=8):
         return _covariances(lambda out, n: self._L.node_shell_multi_last_rigid_covariances(self._h, stream, out, n), max_out)

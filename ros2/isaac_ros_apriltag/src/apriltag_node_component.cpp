@@ -106,6 +106,20 @@ public:
     // pose_refinement_iterations > 0 the published pose.pose.covariance is then the first-order covariance of the chosen pose (x, y, z,
     // rotation about x, y, z in the camera optical frame), zeros where it could not be formed.  0: off, covariance all zero
     opt.pose_covariance_sigma_px = declare_parameter<double>("pose_covariance_sigma_px", 0.0);
+    // camera rigs (one pose per instant and rigid bundle from the tags of all cameras of a calibrated rig): rig_cameras holds twelve
+    // numbers per camera -- R row-major, then t, the rig frame in the camera frame, X_cam = R X_rig + t -- and rig_frame_id names the
+    // parent frame of the "rig_bundle:<name>" transforms.  They are the batching front end's (shell::AprilTagMultiCameraNode, one
+    // camera per stream); this single-camera component carries them in its options and ignores them, as the shell's AprilTagNode does
+    {
+      const std::vector<double> cams = declare_parameter<std::vector<double>>("rig_cameras", std::vector<double>());
+      for (size_t i = 0; i + 11 < cams.size(); i += 12) {
+        shell::RigCamera c;
+        for (size_t k = 0; k < 9; k++) {c.R[k] = cams[i + k];}
+        for (size_t k = 0; k < 3; k++) {c.t[k] = cams[i + 9 + k];}
+        opt.rig_cameras.push_back(c);
+      }
+      opt.rig_frame_id = declare_parameter<std::string>("rig_frame_id", "rig");
+    }
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
     tf_broadcaster_ = std::make_unique<tf2_ros::TransformBroadcaster>(this);
