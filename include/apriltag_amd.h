@@ -90,9 +90,30 @@ typedef enum {
   AMDAT_ENC_RGB8 = 1,
   AMDAT_ENC_BGR8 = 2,
   AMDAT_ENC_RGBA8 = 3,
-  AMDAT_ENC_BGRA8 = 4
+  AMDAT_ENC_BGRA8 = 4,
+  /* Raw formats, under their names in sensor_msgs/image_encodings: one sample per pixel, 8 bits or a
+   * little-endian uint16.  A Bayer name lists the colours of pixels (0,0), (1,0) of row 0, then (0,1), (1,1) of row 1.  A submission of
+   * such frames converts them to gray in one launch of its own, into a plane the handle owns, and is a mono8 submission from there on:
+   * every record equals the record of the same handle given the converted plane as a mono8 frame (amdAprilTagsConvertRawToMono8 gives
+   * that plane), with rectification, resize and every later stage on or off.  Taken by amdAprilTagsDetectBatchColor[Ex] and
+   * amdAprilTagsSubmitBatchColor; the single-frame amdAprilTagsDetectColor keeps to the five values above.  The sample is the byte, or min(255, s >> shift) of a 16-bit
+   * sample s (amdAprilTagsSetRawShift); mono16 is the sample; a Bayer frame is demosaiced bilinearly, its neighbours reflected about the
+   * border, and turned into gray with the BT.601 weights of amdAprilTagsConvertToMono8.  A window into a Bayer image names the pattern at
+   * the window's first pixel.  At submit, with nothing enqueued: AMDAT_INVALID_ARGUMENT for a pitch below bytes per sample x width and
+   * for an odd pointer or pitch of a 16-bit encoding; AMDAT_SIZE_MISMATCH for a Bayer frame below 2 x 2; AMDAT_OUT_OF_MEMORY when the
+   * plane could not be allocated. */
+  AMDAT_ENC_BAYER_RGGB8 = 5,
+  AMDAT_ENC_BAYER_BGGR8 = 6,
+  AMDAT_ENC_BAYER_GBRG8 = 7,
+  AMDAT_ENC_BAYER_GRBG8 = 8,
+  AMDAT_ENC_MONO16 = 9,
+  AMDAT_ENC_BAYER_RGGB16 = 10,
+  AMDAT_ENC_BAYER_BGGR16 = 11,
+  AMDAT_ENC_BAYER_GBRG16 = 12,
+  AMDAT_ENC_BAYER_GRBG16 = 13
 } amdAprilTagsEncoding;
-/* "mono8", "rgb8", "bgr8", "rgba8", "bgra8" -> amdAprilTagsEncoding; -1 for any other string. */
+/* "mono8", "rgb8", "bgr8", "rgba8", "bgra8", "bayer_rggb8", "bayer_bggr8", "bayer_gbrg8", "bayer_grbg8", "mono16", "bayer_rggb16",
+ * "bayer_bggr16", "bayer_gbrg16", "bayer_grbg16" -> amdAprilTagsEncoding; -1 for any other string ("yuv422" among them). */
 int amdAprilTagsEncodingFromName(const char* name);
 
 /* Field NAMES follow cuAprilTagsImageInput_t as the reference assigns them (width, height, dev_ptr, pitch:
@@ -216,7 +237,9 @@ int amdAprilTagsDetect(amdAprilTagsHandle handle, const amdAprilTagsImageInput_t
 /* The same call on a colour frame, as the reference's cuAprilTags branch makes it (uchar3 rgb8 / bgr8 device image,
  * src/apriltag_node.cpp:469-493): the gray value is the fixed-point BT.601 statement of amdAprilTagsConvertToMono8, formed by the
  * threshold pass's loader; results equal those of the mono8 call on the converted frame bit for bit.  encoding AMDAT_ENC_MONO8
- * is amdAprilTagsDetect. */
+ * is amdAprilTagsDetect.  This call keeps to the five encodings of the reference's table (AMDAT_UNSUPPORTED beyond AMDAT_ENC_BGRA8, as
+ * before the raw formats existed); a Bayer or 16-bit frame goes through amdAprilTagsDetectBatchColor[Ex] or amdAprilTagsSubmitBatchColor
+ * with n = 1. */
 int amdAprilTagsDetectColor(amdAprilTagsHandle handle, const amdAprilTagsImageInput_t* img_input, amdAprilTagsEncoding encoding,
                             amdAprilTagsID_t* tags_out, uint32_t* num_tags, uint32_t max_tags, amdAprilTagsStream stream);
 
@@ -633,9 +656,20 @@ int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 int amdAprilTagsGetFrameFlags(amdAprilTagsHandle handle, uint32_t* flags, uint32_t n);
 
 /* Colour -> mono8 on the device.  encoding: "mono8","rgb8","bgr8","rgba8","bgra8"
- * (src/apriltag_node.cpp:76-82). */
+ * (src/apriltag_node.cpp:76-82), or a raw format's name (amdAprilTagsConvertRawToMono8 at shift 8). */
 int amdAprilTagsConvertToMono8(const void* src_dev, size_t src_pitch, const char* encoding, uint32_t width,
                                uint32_t height, uint8_t* dst_dev, size_t dst_pitch, amdAprilTagsStream stream);
+
+/* The same for the raw formats (AMDAT_ENC_BAYER_RGGB8 .. AMDAT_ENC_BAYER_GRBG16), which amdAprilTagsConvertToMono8 takes by name at
+ * shift 8: the plane a submission of such frames detects on.  shift: 0 .. 8, read by the 16-bit encodings.  dst at any address and
+ * pitch >= width; src at any address and pitch for 8-bit samples, both even for 16-bit ones.  AMDAT_UNSUPPORTED: another encoding;
+ * AMDAT_SIZE_MISMATCH: a Bayer frame below 2 x 2, a dimension above 16384; AMDAT_INVALID_ARGUMENT otherwise. */
+int amdAprilTagsConvertRawToMono8(const void* src_dev, size_t src_pitch, amdAprilTagsEncoding encoding, uint32_t shift, uint32_t width,
+                                  uint32_t height, uint8_t* dst_dev, size_t dst_pitch, amdAprilTagsStream stream);
+/* The shift of the 16-bit encodings' samples for the handle's submissions: 0 .. 8, default 8 (the high byte); a sensor with 12
+ * significant bits sets 4.  Host state that travels with the submission's descriptors: no captured launch sequence is retired.
+ * AMDAT_INVALID_ARGUMENT: a null handle, shift > 8, a submission in flight. */
+int amdAprilTagsSetRawShift(amdAprilTagsHandle handle, uint32_t shift);
 
 /* ---- front steps of the usual graph (camera -> rectify -> resize -> apriltag; reference README.md:16-29,
  * launch/isaac_ros_apriltag_usb_cam.launch.py:43-63) on mono8 device images ------------------------- */

@@ -27,7 +27,8 @@ int amdAprilTagsGetStageMs(amdAprilTagsHandle handle, float* ms);
 int amdAprilTagsThresholdOnly(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsImageInput_t* images,
                               amdAprilTagsStream stream);
 /* The same on colour frames: at tile_size 4, decimate 1 the one-pass kernel with the colour loader (3 or 4 bytes read, the gray
- * plane and the threshold image written: 5 or 6 bytes per pixel), otherwise the conversion launch and the mono8 pass. */
+ * plane and the threshold image written: 5 or 6 bytes per pixel), otherwise the conversion launch and the mono8 pass.
+ * AMDAT_UNSUPPORTED for the raw formats (AMDAT_ENC_BAYER_RGGB8 ..): the roofline launch never runs a front step. */
 int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsImageInput_t* images,
                                    amdAprilTagsEncoding encoding, amdAprilTagsStream stream);
 
@@ -76,7 +77,9 @@ typedef enum {
                             * amdAprilTagsSetResize is on as well: the resize samples the rectification in place, that plane is never formed */
   AMDAT_DBG_RESIZED = 10,  /* u8  dw*dh dense (the frame's TARGET size): its slot of the last submission (amdAprilTagsSetResize);
                             * AMDAT_INVALID_ARGUMENT when the last submission did not resize */
-  AMDAT_DBG_DETS = 11      /* amdAprilTagsDetectionEx_t x min(ndets, max_detections): the frame's decoded records as k_decode_wave wrote
+  AMDAT_DBG_RAW_GRAY = 12, /* u8  w*h dense (the frame's SOURCE size): its converted plane of the last submission, where that was a
+                            * submission of Bayer or 16-bit frames (AMDAT_INVALID_ARGUMENT otherwise) */
+  AMDAT_DBG_DETS = 11,     /* amdAprilTagsDetectionEx_t x min(ndets, max_detections): the frame's decoded records as k_decode_wave wrote
                             * them, BEFORE reconcile -- family, id, hamming, decision_margin, H, c, p; R and t are zero; the order is
                             * arbitrary (atomic slots).  AMDAT_DBG_COUNTS' ndets counts every decoded quad, beyond the capacity too */
 } amdAprilTagsDebugBuffer;

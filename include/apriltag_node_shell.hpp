@@ -34,6 +34,7 @@ struct Image {
   uint32_t step = 0;
   const uint8_t* data = nullptr;
   bool is_device = false;
+  bool is_bigendian = false;   // sensor_msgs/Image.is_bigendian: read for the 16-bit encodings, whose big-endian frames are dropped
 };
 
 struct CameraInfo {
@@ -164,6 +165,12 @@ struct NodeOptions {
   // a superset: mono8 is what north_star feeds the detector, and the library's colour entry point reads rgba8 / bgra8 as well.
   // true: cuAprilTags mode refuses everything but rgb8 / bgr8 with the reference's own text.
   bool strict_cuapriltags_encodings = false;
+  // Extension (AprilTagNode): beside the five, the node hands the raw formats of industrial cameras through as they arrive --
+  // "bayer_rggb8", "bayer_bggr8", "bayer_gbrg8", "bayer_grbg8", "mono16", "bayer_rggb16", "bayer_bggr16", "bayer_gbrg16",
+  // "bayer_grbg16" -- and the submission turns them into gray.  raw_shift: the sample of a 16-bit encoding is
+  // min(255, s >> raw_shift), 0 .. 8 (amdAprilTagsSetRawShift; a sensor with 12 significant bits sets 4).  A 16-bit frame with
+  // is_bigendian set is dropped; strict_cuapriltags_encodings refuses all nine as it refuses mono8.
+  uint32_t raw_shift = 8;
   // AprilTagMultiCameraNode only (AprilTagNode, the single-camera shape of the reference, ignores them): the largest frame of a mixed
   // rig.  Both set: the handle is created at max_width x max_height with per-frame image sizes on (amdAprilTagsSetPerFrameSizes), and
   // streams of every admissible size are batched together.  0 (the default): one size, the first frame's; other sizes are dropped.

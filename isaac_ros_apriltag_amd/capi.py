@@ -17,6 +17,7 @@ SLOT_TAG36H10, SLOT_CUSTOM0 = 3, 4   # registrable slots: 3 (tag36h10: no built-
 (DBG_GRAY, DBG_THRESH, DBG_LABEL, DBG_CSIZE, DBG_CLUSTERS, DBG_POINTS, DBG_QUADS, DBG_COUNTS) = range(8)
 DBG_RECTIFIED = 9   # u8 W0 x H0: the frame's rectified plane (amdAprilTagsSetRectification)
 DBG_RESIZED = 10    # u8 dw x dh: the frame's resized plane (amdAprilTagsSetResize)
+DBG_RAW_GRAY = 12   # u8 w x h at the source size: the frame's converted plane (a submission of Bayer or 16-bit frames)
 DBG_DETS = 11       # DET_DTYPE x min(ndets, max_detections): the frame's decoded records before reconcile, in no order
 # the records of the stage buffers as numpy sees them (include/apriltag_amd_debug.h; DET_DTYPE is amdAprilTagsDetectionEx_t)
 CLUSTER_DTYPE = np.dtype([("key", "<u8"), ("start", "<u4"), ("count", "<u4")])
@@ -216,12 +217,18 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetBundlesEx", "amdAprilTagsGetBundlePosesEx", "amdAprilTagsDebugReconcile",
            "amdAprilTagsSetPoseCovariance", "amdAprilTagsGetRefinedPoseCovariances", "amdAprilTagsGetBundlePoseCovariancesEx",
            "amdAprilTagsSetCornerUndistortion", "amdAprilTagsGetUndistortedDetections", "amdAprilTagsDebugUndistort",
-           "amdAprilTagsSetRig", "amdAprilTagsSetRigSlots", "amdAprilTagsGetRigBundlePoses"]
+           "amdAprilTagsSetRig", "amdAprilTagsSetRigSlots", "amdAprilTagsGetRigBundlePoses",
+           "amdAprilTagsConvertRawToMono8", "amdAprilTagsSetRawShift"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
-ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4}   # amdAprilTagsEncoding
+ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4,   # amdAprilTagsEncoding
+             "bayer_rggb8": 5, "bayer_bggr8": 6, "bayer_gbrg8": 7, "bayer_grbg8": 8, "mono16": 9,
+             "bayer_rggb16": 10, "bayer_bggr16": 11, "bayer_gbrg16": 12, "bayer_grbg16": 13}
+RAW_ENCODINGS = tuple(n for n, v in ENCODINGS.items() if v >= 5)   # one sample per pixel: Bayer patterns and mono16
 DISTORTIONS = {"plumb_bob": 0, "rational_polynomial": 1, "equidistant": 2}   # amdAprilTagsDistortion
 DISTORTION_COEFFS = {"plumb_bob": 5, "rational_polynomial": 8, "equidistant": 4}
 ENC_CHANNELS = {"mono8": 1, "rgb8": 3, "bgr8": 3, "rgba8": 4, "bgra8": 4}
+ENC_CHANNELS.update({n: 1 for n in RAW_ENCODINGS})
+ENC_SAMPLE_BYTES = {n: (2 if n.endswith("16") else 1) for n in ENCODINGS}
 
 _lib = None
 
@@ -316,6 +323,8 @@ def lib():
     L.amdAprilTagsSetRig.argtypes = [H, C.c_uint32, C.POINTER(RigCamera)]
     L.amdAprilTagsSetRigSlots.argtypes = [H, C.c_uint32, C.POINTER(RigSlot)]
     L.amdAprilTagsGetRigBundlePoses.argtypes = [H, C.POINTER(RigBundlePose), C.c_uint32]
+    L.amdAprilTagsConvertRawToMono8.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, H]
+    L.amdAprilTagsSetRawShift.argtypes = [H, C.c_uint32]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes =[C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)

@@ -32,6 +32,7 @@
 #include "kernels_pose.h"
 #include "kernels_quad.h"
 #include "kernels_quad_small.h"
+#include "kernels_raw.h"
 #include "kernels_threshold.h"
 #include "kernels_undistort.h"
 #include "launch_plan.h"
@@ -239,6 +240,7 @@ struct amdAprilTagsDetector_st {
   uint32_t graph_max_frames = 8;
   struct GraphEntry { hipGraphExec_t exec = nullptr; uint32_t n = 0, ostride = 0, fmt = 0; hipStream_t stream = nullptr; uint64_t last_use = 0;
                       bool general = false;      // general: captured with the general front kernel (rect_general)
+                      uint32_t raw = 0;          // raw: captured with the raw conversion launch of that instance in front (RAW_KIND_*; fmt is mono8 then)
                       uint32_t nodes = 0; };     // the graph's nodes (amdAprilTagsDebugLastGraphNodes)
   GraphEntry graphs[6];
   std::vector<hipGraphExec_t> retired_graphs;   // see drop_graphs
@@ -268,6 +270,7 @@ struct amdAprilTagsDetector_st {
     PostMode post;
     bool rectified = false;        // it formed the rectified plane (AMDAT_DBG_RECTIFIED)
     bool resized = false;          // it resized (AMDAT_DBG_RESIZED)
+    uint32_t raw = 0;              // it converted Bayer or 16-bit frames into d_raw with this instance (RAW_KIND_*; AMDAT_DBG_RAW_GRAY)
   } last;
   // quad_sigma (amdAprilTagsSetQuadSigma): the filter runs while qs_ksz > 1; qs.tk are the taps of the k_quad_sigma<qs_kh> instance
   uint32_t qs_ksz = 1;
@@ -285,6 +288,17 @@ struct amdAprilTagsDetector_st {
   HostBuf<FrontDesc> h_front;                           // pinned, one per batch slot: k_prologue uploads them with the frame descriptors
   DevBuf<FrontDesc> d_front;
   std::vector<amdAprilTagsImageInput_t> front_imgs;     // the plane's slots as the mono8 images of the submission (fill_front)
+  // Raw formats (raw_formats.h): frame i of a Bayer or 16-bit submission is converted into slot i of d_raw by k_raw_to_mono8_frames, ahead
+  // of the front stage, and the rest sees that slot as a mono8 frame.  The plane has max_batch slots at the largest source size seen so
+  // far (with amdAprilTagsSetResize a source may exceed the handle's size); it is allocated by the first raw submission and regrown
+  // before the enqueue when a larger source arrives.  Its pointers travel through the descriptor block: no captured graph carries them.
+  DevBuf<uint8_t> d_raw;
+  size_t raw_pitch = 0;                                 // a multiple of 64
+  uint32_t raw_w = 0, raw_h = 0;                        // the slot's extent
+  uint32_t raw_shift = RAW_MAX_SHIFT;                   // amdAprilTagsSetRawShift: host state that travels with the descriptors
+  HostBuf<RawDesc> h_rawdesc;                           // pinned, one per batch slot
+  DevBuf<RawDesc> d_rawdesc;
+  std::vector<amdAprilTagsImageInput_t> raw_imgs;       // the plane's slots as the mono8 images of the submission (fill_raw)
   // What the post stages own, each set allocated by the first call that turns its stage on -- the layouts at their largest size,
   // the iteration count and sigma^2 in device memory -- so that a later value changes no launch argument.
   // amdAprilTagsSetBundles (bundle_layout.h):
@@ -383,7 +397,11 @@ static uint32_t quad_sigma_taps(float sigma, uint8_t k[QS_MAX_KSZ]) {
   return (uint32_t)ksz;
 }
 
-static inline uint32_t enc_channels(uint32_t fmt) { return fmt == AMDAT_ENC_MONO8 ? 1u : (fmt <= AMDAT_ENC_BGR8 ? 3u : 4u); }
+// bytes per pixel of an encoding
+static inline uint32_t enc_channels(uint32_t fmt) {
+  if (raw_is_raw(fmt)) return raw_bytes_per_sample(fmt);
+  return fmt == AMDAT_ENC_MONO8 ? 1u : (fmt <= AMDAT_ENC_BGR8 ? 3u : 4u);
+}
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -392,8 +410,11 @@ extern "C" {
 
 int amdAprilTagsEncodingFromName(const char* name) {
   if (!name) return -1;
-  static const char* const kNames[5] = {"mono8", "rgb8", "bgr8", "rgba8", "bgra8"};   // src/apriltag_node.cpp:76-82
-  for (int i = 0; i < 5; i++) if (!strcmp(name, kNames[i])) return i;
+  // src/apriltag_node.cpp:76-82, then the raw formats under their names in sensor_msgs/image_encodings (raw_formats.h)
+  static const char* const kNames[14] = {"mono8", "rgb8", "bgr8", "rgba8", "bgra8", "bayer_rggb8", "bayer_bggr8", "bayer_gbrg8", "bayer_grbg8",
+                                         "mono16", "bayer_rggb16", "bayer_bggr16", "bayer_gbrg16", "bayer_grbg16"};
+  static_assert(AMDAT_ENC_BAYER_RGGB8 == (int)RAW_ENC_FIRST && AMDAT_ENC_MONO16 == (int)RAW_ENC_MONO16 && AMDAT_ENC_BAYER_GRBG16 == (int)RAW_ENC_LAST, "raw_formats.h");
+  for (int i = 0; i < 14; i++) if (!strcmp(name, kNames[i])) return i;
   return -1;
 }
 
@@ -1359,7 +1380,7 @@ int amdAprilTagsGetStageMs(amdAprilTagsHandle handle, float* ms) {
 static int check_images(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt = AMDAT_ENC_MONO8,
                         bool resizing = false) {
   if (n == 0 || !images) return AMDAT_INVALID_ARGUMENT;
-  if (fmt > AMDAT_ENC_BGRA8) return AMDAT_UNSUPPORTED;
+  if (fmt > AMDAT_ENC_BAYER_GRBG16) return AMDAT_UNSUPPORTED;
   if (n > D->cfg.max_batch) return AMDAT_BATCH_TOO_LARGE;
   const uint32_t nsizes = (uint32_t)D->resize_sizes.size();
   for (uint32_t i = 0; i < n; i++) {
@@ -1378,6 +1399,8 @@ static int check_images(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
       if (w < D->cfg.tile_size || h < D->cfg.tile_size) return AMDAT_SIZE_MISMATCH;
     }
     if (images[i].pitch < (size_t)images[i].width * enc_channels(fmt)) return AMDAT_INVALID_ARGUMENT;
+    if (raw_is_16(fmt) && (((uintptr_t)images[i].dev_ptr | images[i].pitch) & 1u)) return AMDAT_INVALID_ARGUMENT;   // (aligned 16-bit loads)
+    if (raw_is_bayer(fmt) && (images[i].width < 2 || images[i].height < 2)) return AMDAT_SIZE_MISMATCH;   // (the reflect rule)
     if ((uint64_t)images[i].pitch * images[i].height > 0x7FFFFFFFull) return AMDAT_INVALID_ARGUMENT;   // 32-bit pixel offsets on the device
     if (images[i].pitch >= (1u << 24)) return AMDAT_INVALID_ARGUMENT;   // (row offsets are formed with 24-bit multiplies: a 16 MB row is no image)
   }
@@ -1441,6 +1464,33 @@ static void fill_frames(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTa
     D->h_frames[i].cx = (double)k.cx; D->h_frames[i].cy = (double)k.cy;
     D->h_frames[i].skew = (double)(i < D->frame_skew.size() ? D->frame_skew[i] : D->cfg.skew);
   }
+}
+
+// A Bayer or 16-bit submission (raw_formats.h): the plane d_raw at the largest source size seen so far -- allocated here by the first
+// such submission, regrown here when a larger source arrives (nothing is in flight: begin_batch) -- the descriptors of the conversion
+// launch, and the plane's slots as the mono8 images the rest of the submission is filled from.  nullptr: the plane could not be allocated.
+static const amdAprilTagsImageInput_t* fill_raw(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTagsImageInput_t* images, uint32_t fmt) {
+  const size_t B = D->cfg.max_batch;
+  if (!ensure_dev(D, D->d_rawdesc, B * sizeof(RawDesc)) || !ensure_host(D, D->h_rawdesc, B * sizeof(RawDesc))) return nullptr;
+  D->raw_imgs.resize(B);
+  uint32_t mw = D->raw_w, mh = D->raw_h;
+  for (uint32_t i = 0; i < n; i++) { mw = std::max(mw, images[i].width); mh = std::max(mh, images[i].height); }
+  if (!D->d_raw || mw > D->raw_w || mh > D->raw_h) {
+    const size_t pitch = ((size_t)mw + 63) & ~(size_t)63;
+    if (!dev_regrow(D, D->d_raw, B * pitch * mh)) return nullptr;
+    D->raw_pitch = pitch; D->raw_w = mw; D->raw_h = mh;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    RawDesc& r = D->h_rawdesc[i];
+    r.src = images[i].dev_ptr;
+    r.dst = D->d_raw + (size_t)i * D->raw_pitch * D->raw_h;
+    r.src_pitch = (uint32_t)images[i].pitch; r.dst_pitch = (uint32_t)D->raw_pitch;
+    r.enc = fmt; r.shift = D->raw_shift;
+    r.w = (int32_t)images[i].width; r.h = (int32_t)images[i].height;
+    r.store = RAW_STORE_PLANE; r.pad = 0;
+    D->raw_imgs[i] = {images[i].width, images[i].height, r.dst, D->raw_pitch};
+  }
+  return D->raw_imgs.data();
 }
 
 // Rectification or resize on: the descriptors of the front kernel for the caller's frames (encoding fmt) -- each slot's target size,
@@ -1553,12 +1603,14 @@ __global__ __launch_bounds__(64) void k_prologue(const uint32_t* __restrict__ ho
                                                  uint32_t* __restrict__ workctl, uint32_t* __restrict__ counters, int fd_words, int fc_words,
                                                  const uint32_t* __restrict__ host_front, uint32_t* __restrict__ front, int front_words,
                                                  const uint32_t* __restrict__ host_ucams, uint32_t* __restrict__ ucams, int ucam_words,
-                                                 const uint32_t* __restrict__ host_rig, uint32_t* __restrict__ rig, int rig_words) {
+                                                 const uint32_t* __restrict__ host_rig, uint32_t* __restrict__ rig, int rig_words,
+                                                 const uint32_t* __restrict__ host_raw, uint32_t* __restrict__ raw, int raw_words) {
   const int frame = (int)blockIdx.x, t = (int)threadIdx.x;
   for (int i = t; i < fd_words; i += 64) frames[frame * fd_words + i] = host_frames[frame * fd_words + i];
   for (int i = t; i < front_words; i += 64) front[frame * front_words + i] = host_front[frame * front_words + i];   // (no front stage: no words)
   for (int i = t; i < ucam_words; i += 64) ucams[frame * ucam_words + i] = host_ucams[frame * ucam_words + i];   // (no corner undistortion: no words)
   for (int i = t; i < rig_words; i += 64) rig[frame * rig_words + i] = host_rig[frame * rig_words + i];   // (no camera rig: no words)
+  for (int i = t; i < raw_words; i += 64) raw[frame * raw_words + i] = host_raw[frame * raw_words + i];   // (no raw conversion: no words)
   for (int i = t; i < fc_words; i += 64) counters[frame * fc_words + i] = 0u;
   if (frame == 0 && t < 32) workctl[t] = 0u;
 }
@@ -1724,7 +1776,19 @@ static int enqueue_submission(amdAprilTagsDetector_st* D, uint32_t n, uint32_t o
                      static_cast<const uint32_t*>(D->h_ucams.p), static_cast<uint32_t*>(D->d_ucams.p),
                      D->last.post.nundist ? (int)(sizeof(UndistortCam) / 4) : 0,
                      reinterpret_cast<const uint32_t*>(D->h_rig.p), reinterpret_cast<uint32_t*>(D->d_rig.p),
-                     D->last.post.nrig ? (int)(sizeof(RigSlotDev) / 4) : 0);
+                     D->last.post.nrig ? (int)(sizeof(RigSlotDev) / 4) : 0,
+                     reinterpret_cast<const uint32_t*>(D->h_rawdesc.p), reinterpret_cast<uint32_t*>(D->d_rawdesc.p),
+                     D->last.raw ? (int)(sizeof(RawDesc) / 4) : 0);
+  // raw formats: the first launch behind the descriptors turns the caller's Bayer or 16-bit frames into the mono8 slots of d_raw that the
+  // descriptors name (a regrowth relaunch converts again).  The grid is the handle's size: its blocks stride over a larger source.
+  if (D->last.raw) {
+    const dim3 g((D->cfg.width + RAW_BW - 1) / RAW_BW, (D->cfg.height + RAW_BH - 1) / RAW_BH, n);
+    switch (D->last.raw) {
+      case RAW_KIND_BAYER8: hipLaunchKernelGGL(k_raw_to_mono8_frames<RAW_KIND_BAYER8>, g, dim3(256), 0, s, D->d_rawdesc); break;
+      case RAW_KIND_MONO16: hipLaunchKernelGGL(k_raw_to_mono8_frames<RAW_KIND_MONO16>, g, dim3(256), 0, s, D->d_rawdesc); break;
+      default: hipLaunchKernelGGL(k_raw_to_mono8_frames<RAW_KIND_BAYER16>, g, dim3(256), 0, s, D->d_rawdesc); break;
+    }
+  }
   if (D->fq_counters) HIP_TRY(hipMemsetAsync(D->d_fqprof, 0, (64 + 8) * 8, s));
   // rectification: the caller's frames, whatever their encoding, become the mono8 slots of the rectified plane the descriptors name
   // (the grid is the handle's size; blocks beyond a frame's own extent return)
@@ -1833,7 +1897,7 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
   if (n <= 8 && !prof && D->path_mode != AMDAT_PATH_THROUGHPUT) {
     amdAprilTagsDetector_st::GraphEntry* hit = nullptr;
     for (auto& g : D->graphs)
-      if (g.exec && g.n == n && g.ostride == ostride && g.stream == s && g.fmt == fmt && g.general == D->rect_general) hit = &g;
+      if (g.exec && g.n == n && g.ostride == ostride && g.stream == s && g.fmt == fmt && g.general == D->rect_general && g.raw == D->last.raw) hit = &g;
     if (hit) {
       D->graph_misses = 0;
       hit->last_use = ++D->graph_clock;
@@ -1857,7 +1921,7 @@ static int launch_once(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostride,
       if (ok && hipGraphGetNodes(graph, nullptr, &nodes) != hipSuccess) { nodes = 0; (void)hipGetLastError(); }
       if (ok) ok = hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0) == hipSuccess;
       if (graph) hipGraphDestroy(graph);
-      if (ok) { slot->n = n; slot->ostride = ostride; slot->fmt = fmt; slot->stream = s; slot->general = D->rect_general; slot->nodes = (uint32_t)nodes; slot->last_use = ++D->graph_clock; hit = slot; }
+      if (ok) { slot->n = n; slot->ostride = ostride; slot->fmt = fmt; slot->stream = s; slot->general = D->rect_general; slot->raw = D->last.raw; slot->nodes = (uint32_t)nodes; slot->last_use = ++D->graph_clock; hit = slot; }
       else {
         // A capture can be invalidated from OUTSIDE the library: on this runtime a legacy-stream call of any other host thread on
         // the same device (a plain hipMemcpy) while this thread captures fails that call and poisons the capture, in every capture
@@ -1996,6 +2060,12 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   if (D->post.nrig) { const int rrc = fill_rig(D, n); if (rrc) return rrc; }   // (refused before anything of the submission is written)
   const bool filt = D->qs_ksz > 1;   // (the setter refuses while a submission is in flight: a regrowth relaunch filters the same way)
   const bool resized = !D->resize_sizes.empty(), rectified = !resized && !D->rect_models.empty();   // (resized: the rectified plane is never formed)
+  const uint32_t raw = (uint32_t)raw_kind(fmt);
+  if (raw) {   // from here on a mono8 submission of the raw plane's slots (the front stage reads them as its mono8 source)
+    images = fill_raw(D, n, images, fmt);
+    if (!images) return AMDAT_OUT_OF_MEMORY;
+    fmt = AMDAT_ENC_MONO8;
+  }
   if (resized || rectified) {   // from here on a mono8 submission of the front plane's slots at their target sizes
     images = fill_front(D, n, images, fmt);
     fmt = AMDAT_ENC_MONO8;
@@ -2004,7 +2074,7 @@ static int begin_batch(amdAprilTagsDetector_st* D, uint32_t n, const amdAprilTag
   fill_frames(D, n, images, intr, fmt, filt);   // image pointers, pitches and intrinsics travel through the pinned descriptor block
   D->last_path = latency_set(n, D->P.W, D->P.H, D->path_mode) ? AMDAT_PATH_LATENCY : AMDAT_PATH_THROUGHPUT;
   if (ostride > D->P.dcap) ostride = D->P.dcap;
-  D->last = {n, ostride, D->post, rectified, resized};
+  D->last = {n, ostride, D->post, rectified, resized, raw};
   for (uint32_t i = 0; i < n && D->post.nundist; i++)   // each slot's camera, beside the frame descriptors (the model describes the detected image)
     D->h_ucams[i] = undistort_cam(D->undist_models[UD_MODEL_OF_SLOT(i, D->post.nundist)]);   // (tools_hooks.h: i % ncams)
   if (D->pending_hash_grow) {   // the pair table of the previous submission was crowded: grow it now (its buffers are dead)
@@ -2134,6 +2204,9 @@ int amdAprilTagsDetectBatch(amdAprilTagsHandle handle, uint32_t n, const amdApri
 
 int amdAprilTagsDetectColor(amdAprilTagsHandle handle, const amdAprilTagsImageInput_t* img_input, amdAprilTagsEncoding encoding,
                             amdAprilTagsID_t* tags_out, uint32_t* num_tags, uint32_t max_tags, amdAprilTagsStream stream) {
+  // The cuAprilTagsDetect-shaped call keeps to the reference's encoding table, as it always has: the raw formats go through the batched
+  // forms (n = 1 for one frame).
+  if ((uint32_t)encoding > AMDAT_ENC_BGRA8) return AMDAT_UNSUPPORTED;
   return amdAprilTagsDetectBatchColor(handle, 1, img_input, encoding, nullptr, tags_out, num_tags, max_tags, stream);
 }
 
@@ -2189,6 +2262,13 @@ int amdAprilTagsSetFrameSkews(amdAprilTagsHandle handle, uint32_t n, const float
   return AMDAT_SUCCESS;
 }
 
+// The shift of 16-bit samples (raw_formats.h): host state that travels with the descriptors, so no graph is retired.
+int amdAprilTagsSetRawShift(amdAprilTagsHandle handle, uint32_t shift) {
+  if (!handle || shift > RAW_MAX_SHIFT || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
+  handle->raw_shift = shift;
+  return AMDAT_SUCCESS;
+}
+
 int amdAprilTagsGetFrameFlags(amdAprilTagsHandle handle, uint32_t* flags, uint32_t n) {
   if (!handle || !flags || n > handle->last.n || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < n; i++) flags[i] = handle->h_counters[i].flags;
@@ -2204,6 +2284,7 @@ int amdAprilTagsThresholdOnlyColor(amdAprilTagsHandle handle, uint32_t n, const 
                                    amdAprilTagsStream stream) {
   if (!handle || handle->inflight.active) return AMDAT_INVALID_ARGUMENT;
   const uint32_t fmt = (uint32_t)encoding;
+  if (raw_is_raw(fmt)) return AMDAT_UNSUPPORTED;   // (the roofline launch: it never runs a front step)
   int rc = check_images(handle, n, images, fmt);
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : handle->own_stream;
@@ -2243,8 +2324,39 @@ int amdAprilTagsConvertToMono8(const void* src_dev, size_t src_pitch, const char
     hipLaunchKernelGGL((k_to_mono8<4, 0, 2>), grid, block, 0, s, src, src_pitch, dst_dev, dst_pitch, width, height);
   } else if (!strcmp(encoding, "bgra8")) {
     hipLaunchKernelGGL((k_to_mono8<4, 2, 0>), grid, block, 0, s, src, src_pitch, dst_dev, dst_pitch, width, height);
+  } else if (raw_is_raw((uint32_t)amdAprilTagsEncodingFromName(encoding))) {   // (the raw formats at the default shift)
+    return amdAprilTagsConvertRawToMono8(src_dev, src_pitch, (amdAprilTagsEncoding)amdAprilTagsEncodingFromName(encoding), RAW_MAX_SHIFT, width, height,
+                                         dst_dev, dst_pitch, stream);
   } else {
     return AMDAT_UNSUPPORTED;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  return AMDAT_SUCCESS;
+}
+
+// The stand-alone form of the raw conversion: the device function of k_raw_to_mono8_frames for one frame, into a caller's plane at any
+// address and pitch (the bytes beyond `width` of a row are left as they are).
+int amdAprilTagsConvertRawToMono8(const void* src_dev, size_t src_pitch, amdAprilTagsEncoding encoding, uint32_t shift, uint32_t width, uint32_t height,
+                                  uint8_t* dst_dev, size_t dst_pitch, amdAprilTagsStream stream) {
+  const uint32_t fmt = (uint32_t)encoding;
+  if (!src_dev || !dst_dev || width == 0 || height == 0 || shift > RAW_MAX_SHIFT || dst_pitch < width) return AMDAT_INVALID_ARGUMENT;
+  if (!raw_is_raw(fmt)) return AMDAT_UNSUPPORTED;
+  if (width > 16384 || height > 16384 || (raw_is_bayer(fmt) && (width < 2 || height < 2))) return AMDAT_SIZE_MISMATCH;
+  if (src_pitch < (size_t)width * raw_bytes_per_sample(fmt) || src_pitch >= (1u << 24) || dst_pitch >= (1u << 24)) return AMDAT_INVALID_ARGUMENT;
+  if (raw_is_16(fmt) && (((uintptr_t)src_dev | src_pitch) & 1u)) return AMDAT_INVALID_ARGUMENT;
+  RawDesc d;
+  d.src = (const uint8_t*)src_dev; d.dst = dst_dev;
+  d.src_pitch = (uint32_t)src_pitch; d.dst_pitch = (uint32_t)dst_pitch;
+  d.enc = fmt; d.shift = shift;
+  d.w = (int32_t)width; d.h = (int32_t)height;
+  d.store = (((uintptr_t)dst_dev | dst_pitch) & 3u) ? RAW_STORE_BYTES : RAW_STORE_DWORD; d.pad = 0;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g((width + RAW_BW - 1) / RAW_BW, (height + RAW_BH - 1) / RAW_BH);
+  switch (raw_kind(fmt)) {
+    case RAW_KIND_BAYER8: hipLaunchKernelGGL(k_raw_to_mono8<RAW_KIND_BAYER8>, g, dim3(256), 0, s, d); break;
+    case RAW_KIND_MONO16: hipLaunchKernelGGL(k_raw_to_mono8<RAW_KIND_MONO16>, g, dim3(256), 0, s, d); break;
+    default: hipLaunchKernelGGL(k_raw_to_mono8<RAW_KIND_BAYER16>, g, dim3(256), 0, s, d); break;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
@@ -2367,6 +2479,16 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
       const size_t n0 = (size_t)f.DW * f.DH;
       tmp.resize(n0);
       HIP_TRY(hipMemcpy2D(tmp.data(), f.DW, f.dst, f.dst_pitch, f.DW, f.DH, hipMemcpyDeviceToHost));
+      *bytes = n0;
+      if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
+      return AMDAT_SUCCESS;
+    }
+    case AMDAT_DBG_RAW_GRAY: {   // w x h dense at the source size: the frame's slot of d_raw, where the last submission converted into it
+      if (!handle->last.raw) return AMDAT_INVALID_ARGUMENT;
+      const RawDesc& r = handle->h_rawdesc[frame];
+      const size_t n0 = (size_t)r.w * r.h;
+      tmp.resize(n0);
+      HIP_TRY(hipMemcpy2D(tmp.data(), r.w, r.dst, r.dst_pitch, r.w, r.h, hipMemcpyDeviceToHost));
       *bytes = n0;
       if (host_dst) memcpy(host_dst, tmp.data(), n0 < capacity ? n0 : capacity);
       return AMDAT_SUCCESS;

@@ -61,6 +61,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsGetBundlePoseCovariancesEx) get_bundle_pose_covariances_ex = nullptr;
   decltype(&amdAprilTagsSetCornerUndistortion) set_corner_undistortion = nullptr;
   decltype(&amdAprilTagsGetUndistortedDetections) get_undistorted_detections = nullptr;
+  decltype(&amdAprilTagsSetRawShift) set_raw_shift = nullptr;
 };
 
 DetectorApi& api() {
@@ -114,6 +115,7 @@ DetectorApi& api() {
   BIND(get_bundle_pose_covariances_ex, "amdAprilTagsGetBundlePoseCovariancesEx")
   BIND(set_corner_undistortion, "amdAprilTagsSetCornerUndistortion")
   BIND(get_undistorted_detections, "amdAprilTagsGetUndistortedDetections")
+  BIND(set_raw_shift, "amdAprilTagsSetRawShift")
 #undef BIND
   return a;
 }
@@ -487,6 +489,15 @@ int bytes_per_pixel(const std::string& enc) {
   if (enc == "rgba8" || enc == "bgra8") return 4;
   return 0;
 }
+// The raw formats the single-stream node hands through beside the five above: bytes per sample, 0 for any
+// other string.  (The multi-stream shell converts into its batch slots itself and keeps to the five.)
+int raw_bytes_per_sample(const std::string& enc) {
+  static const char* const k8[] = {"bayer_rggb8", "bayer_bggr8", "bayer_gbrg8", "bayer_grbg8"};
+  static const char* const k16[] = {"mono16", "bayer_rggb16", "bayer_bggr16", "bayer_gbrg16", "bayer_grbg16"};
+  for (const char* n : k8) if (enc == n) return 1;
+  for (const char* n : k16) if (enc == n) return 2;
+  return 0;
+}
 
 // `backends` is the reference's VPI backend flag string: one name or a comma-separated list
 // (test/isaac_ros_apriltag_backends_compare_test.py:33-37 uses 'CPU', 'CUDA', 'PVA').  Names the reference's
@@ -698,6 +709,8 @@ struct AprilTagNode::Impl {
       throw std::runtime_error("Failed to create AprilTags detector (error code " + std::to_string(error) + ")");
     }
     apply_quad_sigma(detector, opt.quad_sigma);
+    if (api().set_raw_shift(detector, opt.raw_shift) != 0)
+      throw std::runtime_error("'raw_shift' " + std::to_string(opt.raw_shift) + " refused (0 .. 8)");
     if (rectifying(opt)) {
       const CameraModelEx model = stream_model(opt, info);
       const int rerr = apply_models(detector, opt, &model, 1);
@@ -721,11 +734,18 @@ struct AprilTagNode::Impl {
   }
 
   void OnCameraFrame(const Image& image, const CameraInfo& info) {
-    const int bpp = bytes_per_pixel(image.encoding);
+    int bpp = bytes_per_pixel(image.encoding);
     if (cuapriltags_mode && opt.strict_cuapriltags_encodings && image.encoding != "rgb8" && image.encoding != "bgr8") {
       // the reference's cuAprilTags branch, text and all (src/apriltag_node.cpp:469-476)
       std::fprintf(stderr, "[apriltag_node] Unsupported image encoding: %s (only 'rgb8' or 'bgr8' supported)\n", image.encoding.c_str());
       throw std::runtime_error("cuAprilTags detector only supports 'rgb8' or 'bgr8' image input");
+    }
+    if (bpp == 0) {   // a Bayer or 16-bit frame goes to the detector as it arrived, as a colour frame does: the submission converts it
+      bpp = raw_bytes_per_sample(image.encoding);
+      if (bpp == 2 && image.is_bigendian) {   // (the library reads little-endian samples; big-endian ones are out of scope)
+        std::fprintf(stderr, "[apriltag_node] Unsupported image encoding: %s with big-endian samples: frame dropped\n", image.encoding.c_str());
+        return;
+      }
     }
     if (bpp == 0) {
       // (a superset of the reference's cuAprilTags branch, which takes rgb8 / bgr8 only: NodeOptions::strict_cuapriltags_encodings)
@@ -772,8 +792,12 @@ struct AprilTagNode::Impl {
     uint32_t num_detections = 0;
     std::vector<amdAprilTagsID_t> tags(static_cast<size_t>(opt.max_tags));
     const int enc = api().encoding_from_name(image.encoding.c_str());
-    const int error = api().detect_color(detector, &input, static_cast<amdAprilTagsEncoding>(enc), tags.data(), &num_detections,
-                                         static_cast<uint32_t>(opt.max_tags), stream);
+    // (the single-frame call keeps to the reference's five encodings: a raw frame is a batch of one)
+    const int error = raw_bytes_per_sample(image.encoding)
+                          ? api().detect_batch_color(detector, 1, &input, static_cast<amdAprilTagsEncoding>(enc), nullptr, tags.data(),
+                                                     &num_detections, static_cast<uint32_t>(opt.max_tags), stream)
+                          : api().detect_color(detector, &input, static_cast<amdAprilTagsEncoding>(enc), tags.data(), &num_detections,
+                                               static_cast<uint32_t>(opt.max_tags), stream);
     if (error != 0) {
       // the reference logs and drops the frame (src/apriltag_node.cpp:494-497)
       std::fprintf(stderr, "[apriltag_node] Failed to run AprilTags detector (error code %d)\n", error);
@@ -1157,6 +1181,7 @@ struct NodeShellHarness {
   AprilTagDetectionArray last;
   std::vector<TransformStamped> last_tf;
   int publishes = 0;
+  bool is_bigendian = false;   // node_shell_set_bigendian
 };
 
 struct NodeShellDetection {
@@ -1246,6 +1271,28 @@ NodeShellHarness* node_shell_create_opts(int max_tags, double size, int tile_siz
     return nullptr;
   }
 }
+
+// NodeOptions::raw_shift through the flat view, beside the options of node_shell_create_ex
+NodeShellHarness* node_shell_create_raw(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                        int decimate, int strict_cuapriltags_encodings, uint32_t raw_shift, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.strict_cuapriltags_encodings = strict_cuapriltags_encodings != 0;
+    o.raw_shift = raw_shift;
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+// sensor_msgs/Image.is_bigendian of the frames fed from here on (node_shell_on_frame and its kin keep their signatures)
+void node_shell_set_bigendian(NodeShellHarness* h, int is_bigendian) { h->is_bigendian = is_bigendian != 0; }
 
 NodeShellHarness* node_shell_create_ex(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
                                        int decimate, int strict_cuapriltags_encodings, double quad_sigma, char* err, size_t err_len) {
@@ -1498,6 +1545,7 @@ int node_shell_on_frame_full(NodeShellHarness* h, const uint8_t* data, int is_de
     Image img;
     img.header.frame_id = "image_frame"; img.header.stamp.sec = sec; img.header.stamp.nanosec = nanosec;
     img.width = width; img.height = height; img.step = step; img.encoding = encoding; img.data = data; img.is_device = is_device != 0;
+    img.is_bigendian = h->is_bigendian;
     CameraInfo info;
     info.header.frame_id = frame_id; info.header.stamp.sec = info_sec; info.header.stamp.nanosec = info_nanosec;
     info.width = width; info.height = height;

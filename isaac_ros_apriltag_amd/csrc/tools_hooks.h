@@ -91,8 +91,13 @@
 //                               rig is turned against the rig frame
 //                           48 = k_bundle_rig cuts the observation slots at 63: wrong only where a (group, bundle) has 64 or more
 //                               used observations
-//                           (4 .. 48 change values only: no address, index bound or launch size; 43 and 44 run their removal loop
-//                           one round less)
+//                           49 = the raw formats' reflect rule (raw_formats.h) clamps at the right and bottom edge, n - 1 in place of
+//                               2 (n - 1) - i (an index inside the frame): wrong only in the last column and row of a Bayer frame
+//                           50 = the green sites of blue rows take the horizontal average for red and the vertical one for blue
+//                           51 = the sample of a 16-bit encoding is (s >> shift) & 255: wrong only where s >= 256 << shift
+//                           52 = the 16-bit Bayer instance ignores the x phase: grbg16 and bggr16 are demosaiced as rggb16 and gbrg16
+//                           (4 .. 52 change values only: no address outside the frame, index bound or launch size; 43 and 44 run their
+//                           removal loop one round less)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -108,7 +113,8 @@
 //                           tests/test_corner_undistortion_gpu.py::test_the_undistortion_tests_fail_on_the_wrong_builds for 28 .. 30,
 //                           tests/test_integer_stages_gpu.py::test_integer_stage_tests_fail_on_the_wrong_builds for 31 .. 36,
 //                           tests/test_fit_rules_gpu.py::test_the_fit_rule_tests_fail_on_the_wrong_builds for 37 .. 45,
-//                           tests/test_rig_bundles_gpu.py::test_the_rig_tests_fail_on_the_wrong_builds for 46 .. 48)
+//                           tests/test_rig_bundles_gpu.py::test_the_rig_tests_fail_on_the_wrong_builds for 46 .. 48,
+//                           tests/test_raw_formats_gpu.py::test_the_raw_format_tests_fail_on_the_wrong_builds for 49 .. 52)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -480,6 +486,30 @@
 #define FQ_SOUND_EXIT_PREFILTER 0
 #else
 #define FQ_SOUND_EXIT_PREFILTER 1
+#endif
+
+// ---- raw formats (raw_formats.h, kernels_raw.h): the reflected index beyond the far border; which green sites have their red
+// ---- neighbours east and west (yr: the site's row is a red row); the saturation of a shifted 16-bit sample; the x phase an instance
+// ---- of BPS bytes per sample takes ---------------------------------------------------------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 49
+#define RAW_REFLECT_FAR(i, n) ((n) - 1)
+#else
+#define RAW_REFLECT_FAR(i, n) (2 * ((n) - 1) - (i))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 50
+#define RAW_GREEN_RED_HORIZONTAL(yr) true
+#else
+#define RAW_GREEN_RED_HORIZONTAL(yr) (yr)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 51
+#define RAW_SATURATE(s) ((s) & 255u)
+#else
+#define RAW_SATURATE(s) ((s) < 255u ? (s) : 255u)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 52
+#define RAW_XPHASE(BPS, px) ((BPS) == 2 ? 0u : (px))
+#else
+#define RAW_XPHASE(BPS, px) (px)
 #endif
 
 // ---- launch sequence (detector.hip) ---------------------------------------------------------------------------------------

@@ -11,13 +11,17 @@ import numpy as np
 from . import capi
 
 
-def _as_images(frames, width, height, channels=1, per_frame=False):
+def _as_images(frames, width, height, channels=1, per_frame=False, sample_bytes=1):
     """frames: torch uint8 CUDA tensor [n,H,W] / [H,W] (colour: [n,H,W,C] / [H,W,C], interleaved), or a list of such tensors,
     or a list of (dev_ptr, pitch) pairs or (dev_ptr, pitch, width, height) tuples.  width, height: the handle's size, which a
     two-element pair means; with per_frame (the handle's per-frame sizes mode) a tensor brings its own size, from its shape.
     A four-element tuple always names its own size -- a window is (pointer to its first pixel, the full image's pitch, its
-    width, its height).  Returns (ctypes array, keepalive)."""
+    width, its height).  sample_bytes 2 (the 16-bit encodings): tensors of a 16-bit integer type, the pitch their row stride x 2;
+    a tuple's pitch is in bytes as ever.  Returns (ctypes array, keepalive)."""
     items = []
+    if sample_bytes != 1:
+        for t in ([frames] if hasattr(frames, "data_ptr") else [f for f in frames if hasattr(f, "data_ptr")]):
+            assert t.element_size() == sample_bytes, "expected %d-byte samples" % sample_bytes
     if hasattr(frames, "data_ptr"):
         t = frames
         if t.dim() == (2 if channels == 1 else 3):
@@ -28,7 +32,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
             assert t.dim() == 4 and t.shape[3] == channels and t.stride(3) == 1 and t.stride(2) == channels, "expected [n,H,W,C] interleaved"
         w, h = (int(t.shape[2]), int(t.shape[1])) if per_frame else (width, height)
         for i in range(t.shape[0]):
-            items.append((t[i].data_ptr(), t.stride(1), w, h))
+            items.append((t[i].data_ptr(), t.stride(1) * sample_bytes, w, h))
     else:
         for f in frames:
             if hasattr(f, "data_ptr"):
@@ -37,7 +41,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
                 else:
                     assert f.dim() == 3 and f.shape[2] == channels and f.stride(2) == 1 and f.stride(1) == channels
                 w, h = (int(f.shape[1]), int(f.shape[0])) if per_frame else (width, height)
-                items.append((f.data_ptr(), f.stride(0), w, h))
+                items.append((f.data_ptr(), f.stride(0) * sample_bytes, w, h))
             elif len(f) == 4:
                 items.append((int(f[0]), int(f[1]), int(f[2]), int(f[3])))
             else:
@@ -51,7 +55,7 @@ def _as_images(frames, width, height, channels=1, per_frame=False):
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, rig=None, **caps):
+                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, rig=None, raw_shift=None, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -105,6 +109,8 @@ class AprilTagDetector:
                 self.set_pose_covariance(pose_covariance)
             if rig:
                 self.set_rig(rig)
+            if raw_shift is not None:
+                self.set_raw_shift(raw_shift)
         except Exception:
             self.close()
             raise
@@ -112,6 +118,11 @@ class AprilTagDetector:
     def set_quad_sigma(self, sigma):
         """quad_sigma (amdAprilTagsSetQuadSigma): blur (> 0) or sharpen (< 0) of the working image; takes effect with the next submission."""
         capi._check("amdAprilTagsSetQuadSigma", self._L.amdAprilTagsSetQuadSigma(self._h, float(sigma)))
+
+    def set_raw_shift(self, shift):
+        """amdAprilTagsSetRawShift: the sample of the 16-bit encodings ("mono16", "bayer_*16") is min(255, s >> shift); 0 .. 8, default 8,
+        4 for a sensor with 12 significant bits.  Takes effect with the next submission."""
+        capi._check("amdAprilTagsSetRawShift", self._L.amdAprilTagsSetRawShift(self._h, int(shift)))
 
     def set_per_frame_sizes(self, enable=True):
         """amdAprilTagsSetPerFrameSizes: every frame of a submission brings its own size, up to the handle's (width, height are then
@@ -314,8 +325,10 @@ class AprilTagDetector:
 
     # ---- detection --------------------------------------------------------------------------------
     def detect_batch_ex(self, frames, max_dets=64, intrinsics=None, stream=None, encoding="mono8"):
-        """encoding != "mono8": frames are interleaved colour ([n,H,W,C]) and go through amdAprilTagsDetectBatchColorEx."""
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes or self.resizing)
+        """encoding != "mono8": frames are interleaved colour ([n,H,W,C]), or for the raw formats ("bayer_rggb8" .. "bayer_grbg16",
+        "mono16") one sample per pixel ([n,H,W], uint8 or a 16-bit integer type), and go through amdAprilTagsDetectBatchColorEx."""
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes or self.resizing,
+                                capi.ENC_SAMPLE_BYTES.get(encoding, 1))
         n = len(imgs)
         out = (capi.DetectionEx * (n * max_dets))()
         cnt = (C.c_uint32 * n)()
@@ -343,7 +356,8 @@ class AprilTagDetector:
 
     # ---- prepared submissions: argument marshalling done once, the timed call is only the C ABI call ----
     def prepare(self, frames, max_dets=64, intrinsics=None, encoding="mono8"):
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes or self.resizing)
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes or self.resizing,
+                                capi.ENC_SAMPLE_BYTES.get(encoding, 1))
         n = len(imgs)
         intr = None
         if intrinsics is not None:
@@ -404,7 +418,8 @@ class AprilTagDetector:
         return out, [int(c) for c in cnt]
 
     def threshold_only(self, frames, stream=None, encoding="mono8"):
-        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes)
+        imgs, keep = _as_images(frames, self.width, self.height, capi.ENC_CHANNELS[encoding], self.per_frame_sizes,
+                                capi.ENC_SAMPLE_BYTES.get(encoding, 1))
         if encoding == "mono8":
             capi._check("amdAprilTagsThresholdOnly", self._L.amdAprilTagsThresholdOnly(self._h, len(imgs), imgs, stream))
         else:
@@ -467,13 +482,16 @@ class AprilTagDetector:
         return int(nb.value)
 
     def debug(self, frame, what):
+        """amdAprilTagsDebugCopy; what: a capi.DBG_* selector, or "raw_gray" for capi.DBG_RAW_GRAY."""
+        if what == "raw_gray":
+            what = capi.DBG_RAW_GRAY
         nbytes = C.c_size_t()
         capi._check("amdAprilTagsDebugCopy", self._L.amdAprilTagsDebugCopy(self._h, frame, what, None, 0, C.byref(nbytes)))
         buf = np.empty(max(nbytes.value, 1), dtype=np.uint8)
         capi._check("amdAprilTagsDebugCopy",
                     self._L.amdAprilTagsDebugCopy(self._h, frame, what, buf.ctypes.data, buf.size, C.byref(nbytes)))
         buf = buf[:nbytes.value]
-        if what in (capi.DBG_GRAY, capi.DBG_THRESH, capi.DBG_RECTIFIED, capi.DBG_RESIZED):
+        if what in (capi.DBG_GRAY, capi.DBG_THRESH, capi.DBG_RECTIFIED, capi.DBG_RESIZED, capi.DBG_RAW_GRAY):
             return buf
         if what in (capi.DBG_LABEL, capi.DBG_CSIZE, capi.DBG_POINTS, capi.DBG_COUNTS):
             return buf.view(np.uint32)

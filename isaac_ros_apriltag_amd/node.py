@@ -61,6 +61,11 @@ def lib():
         L.node_shell_create_ex.restype = C.c_void_p
         L.node_shell_create_ex.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double,
                                            C.c_char_p, C.c_size_t]
+        L.node_shell_create_raw.restype = C.c_void_p
+        L.node_shell_create_raw.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32,
+                                            C.c_char_p, C.c_size_t]
+        L.node_shell_set_bigendian.restype = None
+        L.node_shell_set_bigendian.argtypes = [C.c_void_p, C.c_int]
         L.node_shell_create_opts.restype = C.c_void_p
         L.node_shell_create_opts.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int,
                                              C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
@@ -470,8 +475,10 @@ class AprilTagNode:
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
                  strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None, pose_refinement=0,
-                 rigid_bundles=None, pose_covariance=0.0):
-        """quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
+                 rigid_bundles=None, pose_covariance=0.0, raw_shift=None):
+        """raw_shift (NodeOptions::raw_shift, alone among the extensions but for strict_cuapriltags_encodings): the shift of the 16-bit
+        encodings' samples, 0 .. 8; the raw formats themselves ("bayer_rggb8" .. "bayer_grbg16", "mono16") are taken by every view.
+        quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
         (on_frame: D, distortion_model, P12), and the pose is computed with Knew; "full" (NodeOptions::rectify_full): with any of the
         three distortion models and the rotation R of that CameraInfo; "corners" (NodeOptions::undistort_corners): the frames are
@@ -489,6 +496,14 @@ class AprilTagNode:
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags = max_tags
+        if raw_shift is not None:
+            if bundles or pose_refinement or quad_sigma or rectify or resize or rigid_bundles or pose_covariance:
+                raise ValueError("raw_shift is served alone by this view, or with strict_cuapriltags_encodings")
+            self._h = self._L.node_shell_create_raw(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                    1 if strict_cuapriltags_encodings else 0, int(raw_shift), err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if pose_refinement and rectify == "corners" and not (bundles or quad_sigma or resize or rigid_bundles or strict_cuapriltags_encodings):
             # (NodeOptions::undistort_corners beside pose_refinement and, where given, pose_covariance: served together by this view)
             self._h = self._L.node_shell_create_undistort_refined(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
@@ -570,8 +585,9 @@ class AprilTagNode:
         return _covariances(lambda out, n: self._L.node_shell_last_rigid_covariances(self._h, out, n), max_out)
 
     def on_frame(self, data_ptr, is_device, encoding, width, height, step, K9, frame_id="tf_camera", stamp=(1, 0),
-                 info_stamp=None, D=None, distortion_model=None, P12=None, R=None):
+                 info_stamp=None, D=None, distortion_model=None, P12=None, R=None, is_bigendian=False):
         info_stamp = stamp if info_stamp is None else info_stamp
+        self._L.node_shell_set_bigendian(self._h, 1 if is_bigendian else 0)
         out = (ShellDetection * self.max_tags)()
         fid = C.create_string_buffer(128)
         err = C.create_string_buffer(1024)

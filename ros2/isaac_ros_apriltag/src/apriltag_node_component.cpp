@@ -48,6 +48,10 @@ public:
     opt.backends = declare_parameter<std::string>("backends", "CUDA");  // name or comma list; exactly "CUDA" = cuAprilTags mode
     opt.decimate = static_cast<uint32_t>(declare_parameter<int>("decimate", 1));
     opt.quad_sigma = declare_parameter<double>("quad_sigma", 0.0);   // AprilRobotics quad_sigma (apriltag_ros `blur` / `sigma`)
+    // Bayer and 16-bit image topics ("bayer_rggb8" .. "bayer_grbg16", "mono16") are taken as they arrive and turned into gray inside the
+    // detector's submission, in place of an image_proc debayer node in front of this one.  raw_shift: the sample of a 16-bit encoding is
+    // min(255, s >> raw_shift), 0 .. 8; a sensor with 12 significant bits sets 4
+    opt.raw_shift = static_cast<uint32_t>(declare_parameter<int>("raw_shift", 8));
     // the image topic is the camera's distorted image: undistorted inside the detector's submission with camera_info's plumb_bob model
     // (K, D; the rectified camera is the left 3x3 of P), in place of a RectifyNode in front of this one
     opt.rectify = declare_parameter<bool>("rectify", false);
@@ -190,6 +194,7 @@ private:
     img.step = image->step;
     img.data = image->data.data();
     img.is_device = false;
+    img.is_bigendian = image->is_bigendian != 0;
     shell::CameraInfo info;
     info.header.frame_id = camera_info->header.frame_id;
     info.header.stamp.sec = camera_info->header.stamp.sec;
