@@ -649,6 +649,34 @@ int amdAprilTagsSetCornerUndistortion(amdAprilTagsHandle handle, uint32_t ncams,
  * frame; their number through *n.  The shape and the refusals of amdAprilTagsGetRefinedPoses. */
 int amdAprilTagsGetUndistortedDetections(amdAprilTagsHandle handle, uint32_t frame, amdAprilTagsUndistortedDetection_t* out, uint32_t capacity, uint32_t* n);
 
+/* ---- The tag table: which tags a deployment has and how big each one is (apriltag_ros: standalone_tags; ROS 2 apriltag_ros: tag.ids /
+ * tag.sizes).  Without a table every tag has the handle's tag_size and every decoded tag is reported.  An entry gives tag `id` of
+ * family families[family_index] of the handle's configuration the edge `size` in metres; id AMDAT_TAG_ID_ANY stands for every id of
+ * that family that has no entry of its own, and size 0 for the handle's tag_size ("listed, at the default size").  The record's pose
+ * (R, t of amdAprilTagsDetectionEx_t), the pose of its undistorted twin, its refined pose and its covariance are those of a tag of
+ * its own size: exactly what a handle with that tag_size reports for the record.  Bundles are not touched: their members carry
+ * sizes of their own.
+ * listed_only = 1: a decoded tag that the table does not list is dropped ahead of the cut to max_tags, like a duplicate: it is in no
+ * count, no record list and no stage behind (twins, bundles, rigs, refined poses, covariances); AMDAT_FLAG_DETS_OVERFLOW and the
+ * AMDAT_DBG_DETS buffer still speak of the records before that.  The members of configured bundles are NOT listed implicitly: with
+ * listed_only they must be in the table, or the bundles never see them.
+ * n = 0 turns the table off and frees its device buffer (49 168 bytes, allocated by the first call with n > 0).  Entries, count and
+ * flag live in device memory: changing them retires no captured launch graph; only setting a table where there was none, or
+ * turning it off, does (against the same budget of 24 as amdAprilTagsSetQuadSigma).  Takes effect with the next submission.
+ * AMDAT_INVALID_ARGUMENT, with the previous table left in force and no graph retired: a null handle, n > 0 with entries == NULL,
+ * n > AMDAT_MAX_TAG_ENTRIES, listed_only > 1, a non-zero reserved, a family_index at or beyond the handle's family count, an id at
+ * or beyond the family's code count other than AMDAT_TAG_ID_ANY, a negative or non-finite size, two entries for one (family_index,
+ * id), a submission in flight. */
+#define AMDAT_MAX_TAG_ENTRIES 4096u
+#define AMDAT_TAG_ID_ANY 0xFFFFu
+typedef struct {
+  uint32_t family_index;
+  uint32_t id;
+  float size;
+  uint32_t reserved;
+} amdAprilTagsTagEntry_t;
+int amdAprilTagsSetTagTable(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsTagEntry_t* entries, uint32_t listed_only);
+
 /* Device memory the handle owns, in bytes. */
 int amdAprilTagsGetDeviceBytes(amdAprilTagsHandle handle, size_t* bytes);
 

@@ -92,7 +92,9 @@ int amdAprilTagsDebugCopy(amdAprilTagsHandle handle, uint32_t frame, amdAprilTag
  * records go into batch slot 0's list, the kernel runs on the handle's own stream with the handle's intrinsics, skew and tag size,
  * and the call waits.  The kept records come back in their final order, R and t filled: min(*nout, capacity) of them, the kept count
  * through *nout.  n above max_detections: AMDAT_INVALID_ARGUMENT.  The last submission's buffers cannot be inspected afterwards
- * (amdAprilTagsDebugCopy and the getters refuse until the next submission); the handle itself stays usable. */
+ * (amdAprilTagsDebugCopy and the getters refuse until the next submission); the handle itself stays usable.
+ * With a tag table (amdAprilTagsSetTagTable) the kernel runs with it: every record's pose at its own size, and with listed_only the
+ * unlisted records dropped; `family` of a record is the index into the handle's family list, as in device memory. */
 int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
                                amdAprilTagsDetectionEx_t* records_out, uint32_t capacity, uint32_t* nout);
 /* k_undistort_records alone on records the caller chooses (amdAprilTagsSetCornerUndistortion's stage; the mode itself may be off): n <=
@@ -100,7 +102,7 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
  * the setter); the kernel runs on the handle's own stream with the handle's intrinsics, skew and tag size, and the call waits.  Both
  * outputs come back, n each: `out` the public records, `twins_out` the twins as the pose launches read them from device memory
  * (hamming INT32_MAX where invalid); either may be null.  The last submission's buffers cannot be inspected afterwards, as with
- * amdAprilTagsDebugReconcile. */
+ * amdAprilTagsDebugReconcile.  With a tag table the twins' poses carry each record's own size (listed_only does not act here). */
 int amdAprilTagsDebugUndistort(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsDetectionEx_t* records_in,
                                const amdAprilTagsCameraModelEx_t* cam, amdAprilTagsUndistortedDetection_t* out,
                                amdAprilTagsDetectionEx_t* twins_out);

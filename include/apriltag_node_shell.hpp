@@ -150,6 +150,15 @@ struct RigBundlePose {
   double err = 0, sq_err_sum = 0, err_alt = 0, sq_err_sum_alt = 0;
 };
 
+// One tag of a deployment (NodeOptions::tags; apriltag_ros: standalone_tags [{id, size, name}]; ROS 2 apriltag_ros: tag.ids /
+// tag.sizes / tag.frames).
+struct TagSpec {
+  std::string family;   // empty: NodeOptions::tag_family (the node decodes that one family: another name is refused)
+  uint32_t id = 0;
+  double size = 0;      // the tag's edge in metres; 0: NodeOptions::size
+  std::string frame;    // the TF child frame of the tag; empty: "family:id".  At most 47 characters.
+};
+
 // Parameters declared in the constructor of the reference node (src/apriltag_node.cpp:564-568).
 struct NodeOptions {
   int max_tags = 64;
@@ -228,6 +237,16 @@ struct NodeOptions {
   // (the default): off.
   std::vector<RigCamera> rig_cameras;
   std::string rig_frame_id = "rig";
+  // Extension: the tag table (amdAprilTagsSetTagTable), set once when the handle is created.  Every listed tag's pose -- the homography
+  // pose, and with the other extensions its twin's, its refined pose and its covariance -- is that of a tag of its own size, and its
+  // transform's child frame is its `frame` where that is not empty; a tag without an entry keeps NodeOptions::size and "family:id".
+  // The message's family and id fields do not change.  tags_listed_only: a tag without an entry is not reported at all -- no
+  // detection, no transform, no place among max_tags (members of `bundles` / `rigid_bundles` included: list them).  Refused when
+  // the node is constructed: a family other than tag_family, a frame above 47 characters, two entries for one id, a negative or
+  // non-finite size, more than 4096 entries; an id beyond the family's codes is refused when the handle is created.  Empty (the
+  // default): off.
+  std::vector<TagSpec> tags;
+  bool tags_listed_only = false;
 };
 
 class AprilTagNode {

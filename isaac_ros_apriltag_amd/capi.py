@@ -167,6 +167,39 @@ UNDISTORT_OK, UNDISTORT_INVALID = 0, 1
 UNDISTORT_ITERATIONS = 20
 
 
+class TagEntry(C.Structure):
+    """amdAprilTagsTagEntry_t."""
+    _fields_ = [("family_index", C.c_uint32), ("id", C.c_uint32), ("size", C.c_float), ("reserved", C.c_uint32)]
+
+
+MAX_TAG_ENTRIES = 4096
+TAG_ID_ANY = 0xFFFF
+
+
+def tag_entries(tags, families):
+    """The amdAprilTagsTagEntry_t array of tags = [(family, id, size)] for a handle of `families` (names): family is a name of that
+    list or an index into it; id an int, "*" (every id of the family without an entry of its own) or an inclusive (first, last)
+    range, which becomes one entry per id; size in metres, 0 for the handle's tag_size.  None for an empty list."""
+    rows = []
+    for fam, tid, size in (tags or []):
+        fi = families.index(fam) if isinstance(fam, str) else int(fam)
+        if isinstance(tid, str):
+            if tid != "*":
+                raise ValueError("tag id %r: an int, \"*\" or (first, last)" % (tid,))
+            ids = [TAG_ID_ANY]
+        elif isinstance(tid, (tuple, list)):
+            ids = list(range(int(tid[0]), int(tid[1]) + 1))
+        else:
+            ids = [int(tid)]
+        rows += [(fi, i, float(size)) for i in ids]
+    if not rows:
+        return None
+    arr = (TagEntry * len(rows))()
+    for e, (fi, i, size) in zip(arr, rows):
+        e.family_index, e.id, e.size, e.reserved = fi, i, size, 0
+    return arr
+
+
 class Float2(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float)]
 
@@ -218,7 +251,7 @@ EXPORTS = ["amdAprilTagsDefaultConfig", "amdCreateAprilTagsDetector", "amdCreate
            "amdAprilTagsSetPoseCovariance", "amdAprilTagsGetRefinedPoseCovariances", "amdAprilTagsGetBundlePoseCovariancesEx",
            "amdAprilTagsSetCornerUndistortion", "amdAprilTagsGetUndistortedDetections", "amdAprilTagsDebugUndistort",
            "amdAprilTagsSetRig", "amdAprilTagsSetRigSlots", "amdAprilTagsGetRigBundlePoses",
-           "amdAprilTagsConvertRawToMono8", "amdAprilTagsSetRawShift"]
+           "amdAprilTagsConvertRawToMono8", "amdAprilTagsSetRawShift", "amdAprilTagsSetTagTable"]
 PATH_AUTO, PATH_LATENCY, PATH_THROUGHPUT = 0, 1, 2
 ENCODINGS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4,   # amdAprilTagsEncoding
              "bayer_rggb8": 5, "bayer_bggr8": 6, "bayer_gbrg8": 7, "bayer_grbg8": 8, "mono16": 9,
@@ -325,6 +358,7 @@ def lib():
     L.amdAprilTagsGetRigBundlePoses.argtypes = [H, C.POINTER(RigBundlePose), C.c_uint32]
     L.amdAprilTagsConvertRawToMono8.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, H]
     L.amdAprilTagsSetRawShift.argtypes = [H, C.c_uint32]
+    L.amdAprilTagsSetTagTable.argtypes = [H, C.c_uint32, C.POINTER(TagEntry), C.c_uint32]
     L.amdAprilTagsDebugQuadSigmaTaps.argtypes =[C.c_float, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTS:
         fn = getattr(L, name)

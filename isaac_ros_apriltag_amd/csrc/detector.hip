@@ -333,6 +333,10 @@ struct amdAprilTagsDetector_st {
   HostBuf<RigSlotDev> h_rig;                            // pinned, one per batch slot
   DevBuf<RigSlotDev> d_rig;
   HostBuf<RigPoseRec> h_gposes;                         // pinned, max_batch x AMDAT_MAX_BUNDLES: k_bundle_rig writes group * nrigid + bundle
+  // amdAprilTagsSetTagTable (tag_table.h): header, keys and sizes in one buffer of TT_BYTES, allocated by the first call with
+  // entries and freed by the call without; null: no table.  k_reconcile, k_undistort_records and k_pose_refine take the pointer
+  // as an argument, so a captured graph holds whether a table exists and nothing of its contents.
+  DevBuf<uint8_t> d_tag_table;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1216,6 +1220,44 @@ int amdAprilTagsSetPoseCovariance(amdAprilTagsHandle handle, double corner_sigma
   return AMDAT_SUCCESS;
 }
 
+// The tag table (tag_table.h).  Built and checked on the host first: a refused call has touched nothing.  The contents go into the
+// handle's buffer, which no launch reads now (no submission is in flight); only a table where there was none, or none where there
+// was one, changes a launch argument and retires the graphs.
+int amdAprilTagsSetTagTable(amdAprilTagsHandle handle, uint32_t n, const amdAprilTagsTagEntry_t* entries, uint32_t listed_only) {
+  if (!handle || handle->inflight.active || (n && !entries) || n > AMDAT_MAX_TAG_ENTRIES || listed_only > 1u) return AMDAT_INVALID_ARGUMENT;
+  amdAprilTagsDetector_st* D = handle;
+  std::vector<uint8_t> image(TT_BYTES, 0);
+  if (n) {
+    uint32_t ncodes[AT_MAX_FAMILIES] = {};
+    static_assert(AT_MAX_FAMILIES == TT_MAX_FAMILIES, "tag_table.h: a family index takes two bits of the key");
+    for (int i = 0; i < D->P.nfam; i++) ncodes[i] = D->P.fam[i].ncodes;
+    std::vector<TagTableEntry> list(n);
+    for (uint32_t i = 0; i < n; i++) {
+      if (entries[i].reserved) return AMDAT_INVALID_ARGUMENT;
+      list[i] = {entries[i].family_index, entries[i].id, entries[i].size};
+    }
+    TagTableHeader head = {n, listed_only, {0u, 0u}};
+    memcpy(image.data(), &head, sizeof(head));
+    static_assert(sizeof(TagTableHeader) == TT_KEYS_OFFSET && TT_SIZES_OFFSET % 8 == 0, "tag_table.h: the buffer's layout");
+    if (tt_build((uint32_t)D->P.nfam, ncodes, n, list.data(), reinterpret_cast<uint32_t*>(image.data() + TT_KEYS_OFFSET),
+                 reinterpret_cast<double*>(image.data() + TT_SIZES_OFFSET)))
+      return AMDAT_INVALID_ARGUMENT;
+  }
+  DeviceGuard guard(D->device);
+  if (!guard.ok) return AMDAT_HIP_ERROR;
+  const bool had = D->d_tag_table.p != nullptr;
+  if (n) {
+    if (!ensure_dev(D, D->d_tag_table, TT_BYTES)) return AMDAT_OUT_OF_MEMORY;
+    const int rc = upload_value(D, D->d_tag_table.p, image.data(), TT_BYTES);
+    if (rc) { if (!had) dev_free(D, D->d_tag_table); return rc; }
+  } else if (had) {
+    HIP_TRY(hipStreamSynchronize(D->own_stream));
+    dev_free(D, D->d_tag_table);
+  }
+  if (had != (n > 0)) drop_graphs(D);
+  return AMDAT_SUCCESS;
+}
+
 // The camera rig.  The first call that turns it on allocates the slot descriptors and the pinned record block; the extrinsics and
 // the slot map are host state that fill_rig writes into every submission's descriptors.
 int amdAprilTagsSetRig(amdAprilTagsHandle handle, uint32_t ncams, const amdAprilTagsRigCamera_t* cams) {
@@ -1718,7 +1760,7 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
                      DECODE_PARAMS(P, D->qs_ksz > 1));   // (tools_hooks.h: P in the product build)
   mark();
   hipLaunchKernelGGL(k_reconcile, dim3(n), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, ostride,
-                     D->h_counters, P);
+                     D->h_counters, P, (const void*)D->d_tag_table.p);
   // The stages behind k_reconcile, as plan_post lists them (post_plan.h), one wave per block except the rigid kind's two
   const PostPlan post = plan_post(D->last.post, n, ostride);
   for (int i = 0; i < post.nsteps; i++) {
@@ -1731,11 +1773,11 @@ static int issue_pipeline(amdAprilTagsDetector_st* D, uint32_t n, uint32_t ostri
                      D->d_rigid_members, D->d_rigid_table, D->h_xposes, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_xcovs)
 #define POSE_LAUNCH(COV)                                                                                                           \
   hipLaunchKernelGGL(k_pose_refine<COV>, grid, dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, D->d_pose_cfg,    \
-                     D->h_rposes, ostride, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_rcovs)
+                     D->h_rposes, ostride, P, (const double*)D->d_cov_cfg, (PoseCovRec*)D->h_rcovs, (const void*)D->d_tag_table.p)
     switch (st.kernel) {
       case POST_K_UNDISTORT:   // S9b: the undistorted twin of every kept record (kernels_undistort.h)
         hipLaunchKernelGGL(k_undistort_records, grid, dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->d_ucams,
-                           D->d_dets_u, D->h_udets, ostride, P);
+                           D->d_dets_u, D->h_udets, ostride, P, (const void*)D->d_tag_table.p);
         break;
       case POST_K_PLANAR:      // S10: one wave per (frame, bundle) on the kept records (kernels_bundle.h)
         hipLaunchKernelGGL(k_bundle_pose, grid, dim3(64), 0, s, D->d_frames, pose_dets, D->d_counters, D->d_order, D->d_bundle_head,
@@ -2583,7 +2625,7 @@ int amdAprilTagsDebugReconcile(amdAprilTagsHandle handle, uint32_t n, const amdA
       [&](hipStream_t s, const DetParams& P) -> int {
         if (n) HIP_TRY(hipMemcpyAsync(D->d_dets, records_in, (size_t)n * sizeof(DetRec), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_reconcile, dim3(1), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order, D->h_out, P.dcap,
-                           D->h_counters, P);
+                           D->h_counters, P, (const void*)D->d_tag_table.p);
         return AMDAT_SUCCESS;
       },
       [&](uint32_t seq) { return static_cast<volatile FrameCounters*>(D->h_counters)[0].seq == seq; });
@@ -2621,7 +2663,7 @@ int amdAprilTagsDebugUndistort(amdAprilTagsHandle handle, uint32_t n, const amdA
           HIP_TRY(hipMemcpyAsync(D->d_order, ident.data(), (size_t)n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         }
         hipLaunchKernelGGL(k_undistort_records, dim3(1, UD_WAVES_PER_FRAME), dim3(64), 0, s, D->d_frames, D->d_dets, D->d_counters, D->d_order,
-                           D->d_ucams, D->d_dets_u, D->h_udets, P.dcap, P);
+                           D->d_ucams, D->d_dets_u, D->h_udets, P.dcap, P, (const void*)D->d_tag_table.p);
         return AMDAT_SUCCESS;
       },
       [&](uint32_t seq) {

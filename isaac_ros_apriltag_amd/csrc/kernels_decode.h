@@ -9,6 +9,7 @@
 // a brute-force popcount scan over the family table (<= 587 codes x 4 rotations), not a hash table.
 #pragma once
 #include "common.h"
+#include "tag_table.h"
 
 __device__ __forceinline__ void homography_project_dev(const double* H, double x, double y, double* ox, double* oy) {
   const double xx = H[0] * x + H[1] * y + H[2];
@@ -152,7 +153,9 @@ __device__ void pose_from_homography_dev(const double* H, double fx_in, double f
 __global__ __launch_bounds__(64) void k_reconcile(const FrameDesc* __restrict__ frames, const DetRec* __restrict__ dets_all,
                                                   FrameCounters* __restrict__ counters,
                                                   uint16_t* __restrict__ order_all, DetRec* __restrict__ host_out,
-                                                  uint32_t host_stride, FrameCounters* __restrict__ host_counters, DetParams P) {
+                                                  uint32_t host_stride, FrameCounters* __restrict__ host_counters, DetParams P,
+                                                  const void* __restrict__ tag_table) {
+  // tag_table: the handle's tag table (tag_table.h), nullptr where none is set: every record is listed, at P.tag_size.
   // the kept records and the frame's counters go straight to the pinned host buffers the API call reads -- `host_stride` records
   // per frame -- instead of to device buffers that two copy commands would move afterwards
   const int frame = (int)blockIdx.x + P.frame0;
@@ -173,9 +176,14 @@ __global__ __launch_bounds__(64) void k_reconcile(const FrameDesc* __restrict__ 
   if (threadIdx.x == 0) {
     // keep a detection unless an already-kept one with the same family+id overlaps it; records of one
     // (family, id) are contiguous in the order, so only that run is scanned
+    // With a listed-only table, a record the table does not list is dropped as an overlapped one is.  The overlap rule compares
+    // records of one (family, id) only, and those are listed or not together: the kept list is the list without a table less its
+    // unlisted records, in the same order.
+    const bool listed_only = tag_table && static_cast<const TagTableHeader*>(tag_table)->listed_only != 0u;
     uint32_t nk = 0, run_start = 0;
     for (uint32_t i = 0; i < nd; i++) {
       const DetRec* di = &dets[order[i]];
+      if (listed_only && !tt_listed_dev(tag_table, (uint32_t)di->family, (uint32_t)di->id)) continue;
       if (nk > 0) {
         const DetRec* dl = &dets[order[nk - 1]];
         if (dl->family != di->family || dl->id != di->id) run_start = nk;
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(64) void k_reconcile(const FrameDesc* __restrict__ 
   const FrameDesc fd = frames[frame];
   for (uint32_t i = threadIdx.x; i < nk; i += 64) {
     DetRec d = dets[order[i]];
-    pose_from_homography_dev(d.H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, P.tag_size, d.R, d.t);
+    pose_from_homography_dev(d.H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, tt_size_dev(tag_table, (uint32_t)d.family, (uint32_t)d.id, P.tag_size), d.R, d.t);
     if (i < host_stride) host_out[(size_t)frame * host_stride + i] = d;
   }
   // The stamp is the LAST thing the host can see of this launch: every lane's records are out (barrier) and ordered ahead of

@@ -55,12 +55,13 @@ static inline uint32_t pose_refine_waves(uint32_t ostride) {
 // memory: changing it changes no launch argument).  Every lane of a wave that runs stays active through the iteration (a group
 // beyond the last record repeats that record and stores nothing), so that the DPP moves always read live lanes.
 // COV: cov_cfg[0] is sigma^2 (device memory, as the count), cov_out the covariance records, laid out as host_out.
+// tag_table: the handle's tag table (tag_table.h), nullptr where none is set.
 template <bool COV>
 __global__ __launch_bounds__(64) void k_pose_refine(const FrameDesc* __restrict__ frames, const DetRec* __restrict__ dets_all,
                                                     const FrameCounters* __restrict__ counters, const uint16_t* __restrict__ order_all,
                                                     const uint32_t* __restrict__ cfg, PoseRefineRec* __restrict__ host_out,
                                                     uint32_t host_stride, DetParams P, const double* __restrict__ cov_cfg,
-                                                    PoseCovRec* __restrict__ cov_out) {
+                                                    PoseCovRec* __restrict__ cov_out, const void* __restrict__ tag_table) {
   const int frame = (int)blockIdx.x + P.frame0;
   uint32_t nout = counters[frame].nout;
   if (nout > P.dcap) nout = P.dcap;
@@ -80,13 +81,15 @@ __global__ __launch_bounds__(64) void k_pose_refine(const FrameDesc* __restrict_
   const uint32_t i = base + (uint32_t)(lane / PR_LANES_PER_RECORD);
   const bool live = i < nout;
   const DetRec* d = &dets[order[live ? i : nout - 1]];
+  // the record's tag size: the homography pose, the model points of the chains and, through them, of the covariance
+  const double tag_size = PR_TAG_SIZE(P.tag_size, tt_size_dev(tag_table, (uint32_t)d->family, (uint32_t)d->id, P.tag_size));   // (tools_hooks.h: the table's)
   double Rh[9], th[3];
-  pose_from_homography_dev(d->H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, P.tag_size, Rh, th);
+  pose_from_homography_dev(d->H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, tag_size, Rh, th);
 
   const double pix[1][2] = {{d->p[k][0], d->p[k][1]}};
   PrPoints<1> C;
   double Gi[6];
-  pr_setup<1>(pix, k, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, P.tag_size / 2.0, 4.0, sum, &C, Gi);
+  pr_setup<1>(pix, k, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, tag_size / 2.0, 4.0, sum, &C, Gi);
   const double Eh = pr_error<1>(C, Rh, th, sum);
   double Rm[9], Rs[9];
   pr_mirror_start(Rh, th, Rm);

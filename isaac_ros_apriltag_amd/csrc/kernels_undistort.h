@@ -27,11 +27,13 @@ __device__ __forceinline__ double ud_group_read(double x, int sub) { return __sh
 // grid (frames, UD_WAVES_PER_FRAME), one wave per block.  Every lane of a wave that enters a round stays active through it (a group
 // beyond the last record repeats that record and stores nothing), so that the shuffles always read live lanes.  cams: one camera per
 // batch slot, uploaded with the submission's descriptors.  dets_u_all is laid out and indexed as dets_all (order_all serves both);
-// host_out holds host_stride records per frame in the order they are handed out.
+// host_out holds host_stride records per frame in the order they are handed out.  tag_table: as k_reconcile's; the twin's pose takes
+// the size of the record's tag.
 __global__ __launch_bounds__(64) void k_undistort_records(const FrameDesc* __restrict__ frames, const DetRec* __restrict__ dets_all,
                                                           const FrameCounters* __restrict__ counters, const uint16_t* __restrict__ order_all,
                                                           const UndistortCam* __restrict__ cams, DetRec* __restrict__ dets_u_all,
-                                                          UndistortRec* __restrict__ host_out, uint32_t host_stride, DetParams P) {
+                                                          UndistortRec* __restrict__ host_out, uint32_t host_stride, DetParams P,
+                                                          const void* __restrict__ tag_table) {
   const int frame = (int)blockIdx.x + P.frame0;
   uint32_t nk = counters[frame].nout;
   if (nk > P.dcap) nk = P.dcap;
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(64) void k_undistort_records(const FrameDesc* __res
     homography_project_dev(H, 0.0, 0.0, &c[0], &c[1]);
 #pragma unroll
     for (int q = 0; q < 4; q++) { p[q][0] = ud_group_read(pu, 2 * q); p[q][1] = ud_group_read(pv, 2 * q); }
-    pose_from_homography_dev(H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, P.tag_size, R, t);
+    pose_from_homography_dev(H, fd.fx, fd.fy, fd.cx, fd.cy, fd.skew, tt_size_dev(tag_table, (uint32_t)d->family, (uint32_t)d->id, P.tag_size), R, t);
     bool fin = ud_finite(c[0]) && ud_finite(c[1]);
 #pragma unroll
     for (int e = 0; e < 9; e++) fin = fin && ud_finite(H[e]) && ud_finite(R[e]);

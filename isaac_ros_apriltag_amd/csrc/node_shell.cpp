@@ -62,6 +62,7 @@ struct DetectorApi {
   decltype(&amdAprilTagsSetCornerUndistortion) set_corner_undistortion = nullptr;
   decltype(&amdAprilTagsGetUndistortedDetections) get_undistorted_detections = nullptr;
   decltype(&amdAprilTagsSetRawShift) set_raw_shift = nullptr;
+  decltype(&amdAprilTagsSetTagTable) set_tag_table = nullptr;
 };
 
 DetectorApi& api() {
@@ -116,6 +117,7 @@ DetectorApi& api() {
   BIND(set_corner_undistortion, "amdAprilTagsSetCornerUndistortion")
   BIND(get_undistorted_detections, "amdAprilTagsGetUndistortedDetections")
   BIND(set_raw_shift, "amdAprilTagsSetRawShift")
+  BIND(set_tag_table, "amdAprilTagsSetTagTable")
 #undef BIND
   return a;
 }
@@ -283,6 +285,37 @@ void apply_rigid_bundles(amdAprilTagsHandle detector, const NodeOptions& opt) {
   }
   const int error = api().set_bundles_ex(detector, static_cast<uint32_t>(abi.size()), abi.data());
   if (error != 0) throw std::runtime_error("'rigid_bundles' refused (error code " + std::to_string(error) + ")");
+}
+
+// NodeOptions::tags at construction: what can be refused without a handle
+void check_tags(const NodeOptions& opt) {
+  if (opt.tags.size() > AMDAT_MAX_TAG_ENTRIES) throw std::runtime_error("'tags': at most " + std::to_string(AMDAT_MAX_TAG_ENTRIES) + " entries");
+  std::set<uint32_t> ids;
+  for (const TagSpec& t : opt.tags) {
+    if (!t.family.empty() && t.family != opt.tag_family)
+      throw std::runtime_error("'tags': family '" + t.family + "' is not the node's tag_family '" + opt.tag_family + "'");
+    if (t.frame.size() > 47) throw std::runtime_error("'tags': frame '" + t.frame + "' is longer than 47 characters");
+    if (!(t.size >= 0.0) || !std::isfinite(t.size)) throw std::runtime_error("'tags': the size of id " + std::to_string(t.id) + " is negative or not finite");
+    if (t.id >= AMDAT_TAG_ID_ANY) throw std::runtime_error("'tags': id " + std::to_string(t.id) + " is no tag id");
+    if (!ids.insert(t.id).second) throw std::runtime_error("'tags': id " + std::to_string(t.id) + " is listed twice");
+  }
+  if (opt.tags_listed_only && opt.tags.empty()) throw std::runtime_error("'tags_listed_only' needs 'tags'");
+}
+
+// NodeOptions::tags on a freshly created handle (one family: index 0)
+void apply_tag_table(amdAprilTagsHandle detector, const NodeOptions& opt) {
+  if (opt.tags.empty()) return;
+  std::vector<amdAprilTagsTagEntry_t> abi(opt.tags.size());
+  for (size_t i = 0; i < abi.size(); i++) abi[i] = {0u, opt.tags[i].id, static_cast<float>(opt.tags[i].size), 0u};
+  const int error = api().set_tag_table(detector, static_cast<uint32_t>(abi.size()), abi.data(), opt.tags_listed_only ? 1u : 0u);
+  if (error != 0) throw std::runtime_error("'tags' refused (error code " + std::to_string(error) + ")");
+}
+
+// The TF child frame of tag `id`: its NodeOptions::tags frame where it has one, "family:id" otherwise
+std::string tag_child_frame(const NodeOptions& opt, uint32_t id) {
+  for (const TagSpec& t : opt.tags)
+    if (t.id == id && !t.frame.empty()) return t.frame;
+  return opt.tag_family + ":" + std::to_string(id);
 }
 
 // NodeOptions::pose_refinement on a freshly created handle
@@ -553,11 +586,12 @@ Quaternion quaternion_from_colmajor(const float* o) {
 }
 
 // AprilTagDetectionArray + TF transforms of one frame from the detector's records (src/apriltag_node.cpp:499-549)
-void assemble_messages(const amdAprilTagsID_t* tags, uint32_t num_detections, const Header& info_header, const std::string& family,
+void assemble_messages(const amdAprilTagsID_t* tags, uint32_t num_detections, const Header& info_header, const NodeOptions& opt,
                        AprilTagDetectionArray* msg_out, std::vector<TransformStamped>* tfs_out,
                        const std::vector<std::array<double, 36>>* covs = nullptr) {
   AprilTagDetectionArray& msg = *msg_out;
   std::vector<TransformStamped>& tfs = *tfs_out;
+  const std::string& family = opt.tag_family;
   msg.header = info_header;  // camera_info header, not the image header (src/apriltag_node.cpp:501)
   for (uint32_t i = 0; i < num_detections; i++) {
     const amdAprilTagsID_t& d = tags[i];
@@ -574,7 +608,7 @@ void assemble_messages(const amdAprilTagsID_t* tags, uint32_t num_detections, co
     det.center.y = d.center.y;
     TransformStamped tf;
     tf.header = info_header;
-    tf.child_frame_id = family + ":" + std::to_string(d.id);
+    tf.child_frame_id = tag_child_frame(opt, d.id);   // (NodeOptions::tags: the tag's frame name; "family:id" without one)
     tf.transform.translation.x = d.translation[0];
     tf.transform.translation.y = d.translation[1];
     tf.transform.translation.z = d.translation[2];
@@ -724,6 +758,7 @@ struct AprilTagNode::Impl {
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
     apply_rigid_bundles(detector, opt);
+    apply_tag_table(detector, opt);
     apply_pose_refinement(detector, opt);
     apply_pose_covariance(detector, opt);
     width = info.width;
@@ -815,7 +850,7 @@ struct AprilTagNode::Impl {
     }
     AprilTagDetectionArray msg;
     std::vector<TransformStamped> tfs;
-    assemble_messages(tags.data(), num_detections, info.header, opt.tag_family, &msg, &tfs, &covs);
+    assemble_messages(tags.data(), num_detections, info.header, opt, &msg, &tfs, &covs);
     {
       std::vector<std::vector<BundlePose>> poses;
       const Header* hdr = &info.header;
@@ -844,6 +879,7 @@ AprilTagNode::AprilTagNode(const NodeOptions& options) : impl_(new Impl()) {
   // cuAprilTags when exactly CUDA was asked for, VPI otherwise; the HIP detector stands behind both, whatever
   // names the list holds (there is one implementation and no CPU fallback).
   impl_->family_enum = validate_family(options, &impl_->cuapriltags_mode);
+  check_tags(options);
 }
 
 AprilTagNode::~AprilTagNode() {
@@ -927,6 +963,7 @@ struct AprilTagMultiCameraNode::Impl {
     apply_resize(detector, opt);
     apply_bundles(detector, opt);
     apply_rigid_bundles(detector, opt);
+    apply_tag_table(detector, opt);
     apply_pose_refinement(detector, opt);
     apply_pose_covariance(detector, opt);
     apply_rig(detector, opt, S);
@@ -1011,6 +1048,7 @@ AprilTagMultiCameraNode::AprilTagMultiCameraNode(const NodeOptions& options, uin
   impl_->last_bundles.resize(num_streams);
   impl_->last_rigid.resize(num_streams);
   impl_->family_enum = validate_family(options, &impl_->cuapriltags_mode);
+  check_tags(options);
 }
 
 AprilTagMultiCameraNode::~AprilTagMultiCameraNode() {
@@ -1134,7 +1172,7 @@ uint32_t AprilTagMultiCameraNode::Flush() {
       std::fprintf(stderr, "[apriltag_node] refined poses or their covariances not available: round dropped\n");
       return 0;
     }
-    assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt.tag_family, &msgs[i], &tfs[i],
+    assemble_messages(tags.data() + static_cast<size_t>(i) * max_tags, counts[i], I.slots[who[i]].info_header, I.opt, &msgs[i], &tfs[i],
                       &covs);
     headers[i] = &I.slots[who[i]].info_header;
     tf_ptrs[i] = &tfs[i];
@@ -1467,6 +1505,42 @@ NodeShellHarness* node_shell_create_refined(int max_tags, double size, int tile_
     return nullptr;
   }
 }
+// NodeOptions::tags through the flat view: ntags entries, frame "" for none (the field is wider than the 47 characters a frame may
+// have, so that a frame too long reaches the constructor and is refused there)
+struct NodeShellTag {
+  uint32_t id;
+  double size;
+  char frame[64];
+};
+static void flat_tags(NodeOptions* o, int ntags, const NodeShellTag* tags, int listed_only) {
+  for (int i = 0; i < ntags; i++) {
+    amd::isaac_ros::apriltag::TagSpec t;
+    t.id = tags[i].id; t.size = tags[i].size;
+    t.frame = std::string(tags[i].frame, strnlen(tags[i].frame, sizeof(tags[i].frame)));
+    o->tags.push_back(t);
+  }
+  o->tags_listed_only = listed_only != 0;
+}
+// AprilTagNode with NodeOptions::tags / tags_listed_only beside pose_refinement (0: off)
+NodeShellHarness* node_shell_create_tags(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
+                                         int decimate, uint32_t pose_refinement, int ntags, const NodeShellTag* tags,
+                                         int listed_only, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    flat_tags(&o, ntags, tags, listed_only);
+    auto* h = new NodeShellHarness();
+    h->node.reset(new AprilTagNode(o));
+    h->node->set_detections_callback([h](const AprilTagDetectionArray& m) { h->last = m; h->publishes++; });
+    h->node->set_transforms_callback([h](const std::vector<TransformStamped>& t) { h->last_tf = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
 // AprilTagNode with NodeOptions::undistort_corners beside pose_refinement (and pose_covariance_sigma_px; 0: off)
 NodeShellHarness* node_shell_create_undistort_refined(int max_tags, double size, int tile_size, const char* tag_family, const char* backends,
                                                       int decimate, uint32_t pose_refinement, double sigma_px, char* err, size_t err_len) {
@@ -1749,6 +1823,28 @@ MultiShellHarness* node_shell_multi_create_undistort_refined(int num_streams, in
     o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
     o.pose_refinement = pose_refinement;
     o.undistort_corners = true;
+    auto* h = new MultiShellHarness();
+    h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
+    h->node->set_auto_flush(auto_flush != 0);
+    h->last.resize(num_streams); h->last_tf.resize(num_streams); h->publishes.assign(num_streams, 0);
+    h->node->set_detections_callback([h](uint32_t s, const AprilTagDetectionArray& m) { h->last[s] = m; h->publishes[s]++; });
+    h->node->set_transforms_callback([h](uint32_t s, const std::vector<TransformStamped>& t) { h->last_tf[s] = t; });
+    return h;
+  } catch (const std::exception& e) {
+    if (err && err_len) { std::strncpy(err, e.what(), err_len - 1); err[err_len - 1] = 0; }
+    return nullptr;
+  }
+}
+// AprilTagMultiCameraNode with NodeOptions::tags / tags_listed_only beside pose_refinement (0: off)
+MultiShellHarness* node_shell_multi_create_tags(int num_streams, int max_tags, double size, int tile_size, const char* tag_family,
+                                                const char* backends, int decimate, int auto_flush, uint32_t pose_refinement, int ntags,
+                                                const NodeShellTag* tags, int listed_only, char* err, size_t err_len) {
+  try {
+    NodeOptions o;
+    o.max_tags = max_tags; o.size = size; o.tile_size = static_cast<uint16_t>(tile_size);
+    o.tag_family = tag_family; o.backends = backends; o.decimate = static_cast<uint32_t>(decimate);
+    o.pose_refinement = pose_refinement;
+    flat_tags(&o, ntags, tags, listed_only);
     auto* h = new MultiShellHarness();
     h->node.reset(new amd::isaac_ros::apriltag::AprilTagMultiCameraNode(o, static_cast<uint32_t>(num_streams)));
     h->node->set_auto_flush(auto_flush != 0);

@@ -96,8 +96,13 @@
 //                           50 = the green sites of blue rows take the horizontal average for red and the vertical one for blue
 //                           51 = the sample of a 16-bit encoding is (s >> shift) & 255: wrong only where s >= 256 << shift
 //                           52 = the 16-bit Bayer instance ignores the x phase: grbg16 and bggr16 are demosaiced as rggb16 and gbrg16
-//                           (4 .. 52 change values only: no address outside the frame, index bound or launch size; 43 and 44 run their
-//                           removal loop one round less)
+//                           53 = the tag table's binary search (tag_table.h: tt_find) ends one entry early: the last key is never found
+//                           54 = the tag table's lookup consults the family's wildcard before the exact key: wrong only where an
+//                               exact entry sits beside a wildcard of its family
+//                           55 = k_pose_refine keeps the handle's tag_size: wrong only in refined poses and covariances of tags whose
+//                               table size differs from it, never in a detection record
+//                           (4 .. 55 change values only: no address outside the frame, index bound or launch size; 43 and 44 run their
+//                           removal loop one round less; 53 reads one entry less)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
 //                           tests/test_per_frame_sizes_gpu.py::test_cluster_cap_fails_on_the_wrong_build for 6,
@@ -114,7 +119,8 @@
 //                           tests/test_integer_stages_gpu.py::test_integer_stage_tests_fail_on_the_wrong_builds for 31 .. 36,
 //                           tests/test_fit_rules_gpu.py::test_the_fit_rule_tests_fail_on_the_wrong_builds for 37 .. 45,
 //                           tests/test_rig_bundles_gpu.py::test_the_rig_tests_fail_on_the_wrong_builds for 46 .. 48,
-//                           tests/test_raw_formats_gpu.py::test_the_raw_format_tests_fail_on_the_wrong_builds for 49 .. 52)
+//                           tests/test_raw_formats_gpu.py::test_the_raw_format_tests_fail_on_the_wrong_builds for 49 .. 52,
+//                           tests/test_tag_table_gpu.py::test_the_tag_table_tests_fail_on_the_wrong_builds for 53 .. 55)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -510,6 +516,24 @@
 #define RAW_XPHASE(BPS, px) ((BPS) == 2 ? 0u : (px))
 #else
 #define RAW_XPHASE(BPS, px) (px)
+#endif
+
+// ---- the tag table (tag_table.h): where the binary search over n keys ends; whether the wildcard is consulted first; the size
+// ---- k_pose_refine takes for a record (handle: P.tag_size, looked_up: the table's) -------------------------------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 53
+#define TT_SEARCH_END(n) ((n) > 0u ? (n) - 1u : 0u)
+#else
+#define TT_SEARCH_END(n) (n)
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 54
+#define TT_WILDCARD_FIRST true
+#else
+#define TT_WILDCARD_FIRST false
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 55
+#define PR_TAG_SIZE(handle, looked_up) ((void)(looked_up), (handle))
+#else
+#define PR_TAG_SIZE(handle, looked_up) ((void)(handle), (looked_up))
 #endif
 
 // ---- launch sequence (detector.hip) ---------------------------------------------------------------------------------------

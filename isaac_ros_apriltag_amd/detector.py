@@ -55,7 +55,8 @@ def _as_images(frames, width, height, channels=1, per_frame=False, sample_bytes=
 class AprilTagDetector:
     def __init__(self, width, height, families=("tag36h11",), decimate=1, intrinsics=None, tag_size=0.22, max_batch=1,
                  tile_size=4, device=-1, refine_edges=True, quad_sigma=0.0, per_frame_sizes=False, rectification=None, resize=None,
-                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, rig=None, raw_shift=None, **caps):
+                 bundles=None, pose_refinement=0, bundles_ex=None, pose_covariance=0.0, corner_undistortion=None, rig=None, raw_shift=None, tags=None,
+                 listed_only=False, **caps):
         L = capi.lib()
         cfg = capi.Config()
         L.amdAprilTagsDefaultConfig(C.byref(cfg), width, height)
@@ -111,6 +112,8 @@ class AprilTagDetector:
                 self.set_rig(rig)
             if raw_shift is not None:
                 self.set_raw_shift(raw_shift)
+            if tags:
+                self.set_tag_table(tags, listed_only)
         except Exception:
             self.close()
             raise
@@ -123,6 +126,16 @@ class AprilTagDetector:
         """amdAprilTagsSetRawShift: the sample of the 16-bit encodings ("mono16", "bayer_*16") is min(255, s >> shift); 0 .. 8, default 8,
         4 for a sensor with 12 significant bits.  Takes effect with the next submission."""
         capi._check("amdAprilTagsSetRawShift", self._L.amdAprilTagsSetRawShift(self._h, int(shift)))
+
+    def set_tag_table(self, tags, listed_only=False):
+        """amdAprilTagsSetTagTable: tags is a list of (family, id, size) -- family a name of the handle's list or an index into it; id an
+        int, "*" for every id of the family without an entry of its own, or an inclusive (first, last) range; size the tag's edge in
+        metres, 0 for the handle's tag_size.  Every following submission reports each tag's pose, undistorted twin, refined pose and
+        covariance at its own size; with listed_only, tags that the table does not list are not reported at all (members of bundles
+        included: list them).  None or [] turns the table off."""
+        arr = capi.tag_entries(tags, self.families)
+        capi._check("amdAprilTagsSetTagTable",
+                    self._L.amdAprilTagsSetTagTable(self._h, len(arr) if arr is not None else 0, arr, 1 if (listed_only and arr is not None) else 0))
 
     def set_per_frame_sizes(self, enable=True):
         """amdAprilTagsSetPerFrameSizes: every frame of a submission brings its own size, up to the handle's (width, height are then

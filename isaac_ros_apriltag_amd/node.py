@@ -21,6 +21,23 @@ class ShellBundle(C.Structure):
                 ("min_tags", C.c_uint32), ("pad", C.c_uint32), ("min_decision_margin", C.c_double)]
 
 
+class ShellTag(C.Structure):
+    """NodeOptions::tags through the flat view: one tag's id, size (0: the node's) and TF child frame ("": "family:id")."""
+    _fields_ = [("id", C.c_uint32), ("size", C.c_double), ("frame", C.c_char * 64)]
+
+
+def _shell_tags(tags):
+    """tags: [(id, size, frame)] or [{"id", "size", "frame"}] -> the flat view's array."""
+    arr = (ShellTag * max(len(tags), 1))()
+    for e, t in zip(arr, tags):
+        tid, size, frame = (t["id"], t.get("size", 0.0), t.get("frame", "")) if isinstance(t, dict) else t
+        name = (frame or "").encode()
+        if len(name) > 63:
+            raise ValueError("tags: frame %r is longer than 47 characters" % (frame,))
+        e.id, e.size, e.frame = int(tid), float(size), name
+    return arr
+
+
 class ShellRigidBundle(C.Structure):
     """NodeOptions::rigid_bundles through the flat view: members holds nine doubles per member -- id, x, y, z, qw, qx, qy, qz, size."""
     _fields_ = [("name", C.c_char * 32), ("members", C.POINTER(C.c_double)), ("nmembers", C.c_uint32), ("max_hamming", C.c_uint32),
@@ -131,6 +148,12 @@ def lib():
                                                       C.c_int, C.POINTER(ShellBundle), C.c_char_p, C.c_size_t]
         L.node_shell_create_refined.restype = C.c_void_p
         L.node_shell_create_refined.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]
+        L.node_shell_create_tags.restype = C.c_void_p
+        L.node_shell_create_tags.argtypes = [C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.POINTER(ShellTag),
+                                             C.c_int, C.c_char_p, C.c_size_t]
+        L.node_shell_multi_create_tags.restype = C.c_void_p
+        L.node_shell_multi_create_tags.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32,
+                                                   C.c_int, C.POINTER(ShellTag), C.c_int, C.c_char_p, C.c_size_t]
         L.node_shell_multi_create_refined.restype = C.c_void_p
         L.node_shell_multi_create_refined.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32,
                                                       C.c_char_p, C.c_size_t]
@@ -309,8 +332,10 @@ class AprilTagMultiCameraNode:
 
     def __init__(self, num_streams, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
                  auto_flush=True, quad_sigma=0.0, max_width=0, max_height=0, rectify=False, resize=None, bundles=None, pose_refinement=0,
-                 rigid_bundles=None, pose_covariance=0.0, rig_cameras=None, rig_frame_id="rig"):
-        """rig_cameras (NodeOptions::rig_cameras, with rigid_bundles and nothing else): [(R, t)] per stream, the rig frame in the
+                 rigid_bundles=None, pose_covariance=0.0, rig_cameras=None, rig_frame_id="rig", tags=None, tags_listed_only=False):
+        """tags, tags_listed_only (NodeOptions::tags, with pose_refinement and nothing else): [(id, size, frame)] -- every listed tag's pose
+        at its own size (0: the node's) and its transform under `frame` ("": "family:id"); with tags_listed_only the other tags are
+        not reported.  rig_cameras (NodeOptions::rig_cameras, with rigid_bundles and nothing else): [(R, t)] per stream, the rig frame in the
         camera frame -- every round is one instant of the rig: one "rig_bundle:<name>" transform per solved bundle under rig_frame_id
         behind the first served stream's transforms, and rig_bundle_poses() hands out the records.
         max_width, max_height (NodeOptions): both set, streams of every size up to that one are batched together (per-frame image
@@ -332,6 +357,16 @@ class AprilTagMultiCameraNode:
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags, self.num_streams = max_tags, num_streams
+        if tags or tags_listed_only:
+            if bundles or quad_sigma or max_width or max_height or rectify or resize or rigid_bundles or pose_covariance or rig_cameras:
+                raise ValueError("tags is served alone by this view, or with pose_refinement")
+            arr = _shell_tags(list(tags or []))
+            self._h = self._L.node_shell_multi_create_tags(num_streams, max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                           1 if auto_flush else 0, int(pose_refinement), len(tags or []), arr,
+                                                           1 if tags_listed_only else 0, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if rig_cameras:
             if bundles or pose_refinement or quad_sigma or max_width or max_height or rectify or resize or pose_covariance:
                 raise ValueError("rig_cameras is served with rigid_bundles by this view, and with nothing else")
@@ -475,8 +510,10 @@ class AprilTagNode:
 
     def __init__(self, max_tags=64, size=0.22, tile_size=4, tag_family="tag36h11", backends="CUDA", decimate=1,
                  strict_cuapriltags_encodings=False, quad_sigma=0.0, rectify=False, resize=None, bundles=None, pose_refinement=0,
-                 rigid_bundles=None, pose_covariance=0.0, raw_shift=None):
-        """raw_shift (NodeOptions::raw_shift, alone among the extensions but for strict_cuapriltags_encodings): the shift of the 16-bit
+                 rigid_bundles=None, pose_covariance=0.0, raw_shift=None, tags=None, tags_listed_only=False):
+        """tags, tags_listed_only (NodeOptions::tags, with pose_refinement and nothing else): [(id, size, frame)] -- every listed tag's pose
+        at its own size (0: the node's) and its transform under `frame` ("": "family:id"); with tags_listed_only the other tags are
+        not reported.  raw_shift (NodeOptions::raw_shift, alone among the extensions but for strict_cuapriltags_encodings): the shift of the 16-bit
         encodings' samples, 0 .. 8; the raw formats themselves ("bayer_rggb8" .. "bayer_grbg16", "mono16") are taken by every view.
         quad_sigma: AprilRobotics' blur (> 0) / sharpen (< 0) of the working image (NodeOptions::quad_sigma).  rectify
         (NodeOptions): the frames are undistorted inside the submission with the plumb_bob model of the first CameraInfo
@@ -496,6 +533,16 @@ class AprilTagNode:
         err = C.create_string_buffer(1024)
         self._L = lib()
         self.max_tags = max_tags
+        if tags or tags_listed_only:
+            if (bundles or quad_sigma or rectify or resize or rigid_bundles or pose_covariance or strict_cuapriltags_encodings
+                    or raw_shift is not None):
+                raise ValueError("tags is served alone by this view, or with pose_refinement")
+            arr = _shell_tags(list(tags or []))
+            self._h = self._L.node_shell_create_tags(max_tags, size, tile_size, tag_family.encode(), backends.encode(), decimate,
+                                                     int(pose_refinement), len(tags or []), arr, 1 if tags_listed_only else 0, err, 1024)
+            if not self._h:
+                raise RuntimeError(err.value.decode())
+            return
         if raw_shift is not None:
             if bundles or pose_refinement or quad_sigma or rectify or resize or rigid_bundles or pose_covariance:
                 raise ValueError("raw_shift is served alone by this view, or with strict_cuapriltags_encodings")

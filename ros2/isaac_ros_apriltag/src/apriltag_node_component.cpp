@@ -9,6 +9,7 @@
 // described in ros2/README.md.  It takes sensor_msgs/Image (host memory); the NITROS zero-copy type
 // adaptation of the reference is NVIDIA-proprietary and out of scope.
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -123,6 +124,26 @@ public:
         opt.rig_cameras.push_back(c);
       }
       opt.rig_frame_id = declare_parameter<std::string>("rig_frame_id", "rig");
+    }
+    // the tag table (the ROS 2 apriltag_ros' tag.ids / tag.frames / tag.sizes): tag_ids[i] has the edge tag_sizes[i] in metres (0: `size`)
+    // and is published under the TF child frame tag_frames[i] (empty: "family:id"); the three lists have equal lengths.
+    // tag_listed_only: tags that tag_ids does not name are not published at all
+    {
+      const std::vector<int64_t> ids = declare_parameter<std::vector<int64_t>>("tag_ids", std::vector<int64_t>());
+      const std::vector<std::string> frames = declare_parameter<std::vector<std::string>>("tag_frames", std::vector<std::string>());
+      const std::vector<double> sizes = declare_parameter<std::vector<double>>("tag_sizes", std::vector<double>());
+      if (frames.size() != ids.size() || sizes.size() != ids.size()) {
+        throw std::runtime_error("'tag_ids', 'tag_frames' and 'tag_sizes' must have equal lengths");
+      }
+      for (size_t i = 0; i < ids.size(); i++) {
+        if (ids[i] < 0 || ids[i] > 65534) {throw std::runtime_error("'tag_ids': " + std::to_string(ids[i]) + " is no tag id");}
+        shell::TagSpec t;
+        t.id = static_cast<uint32_t>(ids[i]);
+        t.size = sizes[i];
+        t.frame = frames[i];
+        opt.tags.push_back(t);
+      }
+      opt.tags_listed_only = declare_parameter<bool>("tag_listed_only", false);
     }
     // throws std::runtime_error("Tag family not supported by specified backend ...") like the reference
     impl_ = std::make_unique<shell::AprilTagNode>(opt);
