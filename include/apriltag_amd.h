@@ -736,8 +736,9 @@ int amdAprilTagsRegisterFamily(amdAprilTagsFamily slot, const char* name, uint32
 /* The same for an AprilTag-3 style layout -- what the circle / standard / custom families of the reference's table
  * (src/apriltag_node.cpp:47-58: circle21h7, circle49h12, custom48h12, standard41h12, standard52h13) need: nbits data bits
  * (<= 64), bit i at cell (bit_x[i], bit_y[i]) in border coordinates ((0, 0) = top-left cell of the border square of
- * width_at_border cells; cells of outer rings are negative or >= width_at_border), total_width cells across everything
- * (<= 12, same parity as width_at_border), reversed_border != 0 when the border square is white inside a black ring.
+ * width_at_border cells, 3 <= width_at_border <= 10: the decode kernel holds 8 x 10 border samples, and a classic 8 x 8
+ * family, the widest 64-bit word, needs exactly 10; cells of outer rings are negative or >= width_at_border), total_width
+ * cells across everything (<= 12, same parity as width_at_border), reversed_border != 0 when the border square is white inside a black ring.
  * Bit (nbits - 1 - i) of a code is data bit i (AprilTag 3's own convention), 1 = white.  The layout must map onto itself
  * under the quarter turn (x, y) -> (width_at_border - 1 - y, x); AMDAT_INVALID_ARGUMENT otherwise.  This library ships
  * no code tables for those five families (none can be verified offline); a host that has them registers them here under

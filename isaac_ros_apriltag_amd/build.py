@@ -165,7 +165,7 @@ def build_stress(force=False):
 
 
 MUTANTS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40,
-           41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55)   # csrc/tools_hooks.h, AMDAT_MUTATE
+           41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58)   # csrc/tools_hooks.h, AMDAT_MUTATE
 MUTANT_JOBS = 16   # compilers build_mutants runs at a time
 
 
@@ -199,7 +199,8 @@ def build_mutants(force=False):
     slots cut at 63, 49 the raw formats' reflect rule as a clamp at the right and bottom edge, 50 the horizontal and vertical averages
     exchanged at the green sites of blue rows, 51 the 16-bit sample with & 255 in place of the saturation, 52 the 16-bit Bayer instance
     without the x phase, 53 the tag table's binary search ending one entry early, 54 the tag table's wildcard consulted before the exact
-    key, 55 k_pose_refine with the handle's tag_size for every record),
+    key, 55 k_pose_refine with the handle's tag_size for every record, 56 the code scan keeping a lane's later code at equal distance,
+    57 the quarter turn's ballot without lane 63, 58 the border samples from index 64 on stored as invalid),
     shipped like the stress build so that the GPU suite itself shows, under the driver's eyes, that its stage tests FAIL on each of them
     (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds, tests/test_per_frame_sizes_gpu.py for 6,
     tests/test_fit_classes_gpu.py for 7 and 8, tests/test_rectify_submission_gpu.py for 9 and 10,
@@ -207,7 +208,8 @@ def build_mutants(force=False):
     tests/test_pose_refine_gpu.py for 17 and 18, tests/test_rigid_bundles_gpu.py for 19 and 20, tests/test_decode_stage_gpu.py for
     21 .. 24, tests/test_pose_covariance_gpu.py for 25 .. 27, tests/test_corner_undistortion_gpu.py for 28 .. 30,
     tests/test_integer_stages_gpu.py for 31 .. 36, tests/test_fit_rules_gpu.py for 37 .. 45,
-    tests/test_rig_bundles_gpu.py for 46 .. 48, tests/test_raw_formats_gpu.py for 49 .. 52, tests/test_tag_table_gpu.py for 53 .. 55).
+    tests/test_rig_bundles_gpu.py for 46 .. 48, tests/test_raw_formats_gpu.py for 49 .. 52, tests/test_tag_table_gpu.py for 53 .. 55,
+    tests/test_decode_families_gpu.py for 56 .. 58).
     Never loaded by the product path.
     At most MUTANT_JOBS compilers run at a time."""
     from concurrent.futures import ThreadPoolExecutor

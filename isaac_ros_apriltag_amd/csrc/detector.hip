@@ -480,6 +480,9 @@ int amdAprilTagsRegisterFamilyEx(amdAprilTagsFamily slot, const char* name, uint
   if (!family_args_ok(name, nbits, codes, ncodes)) return AMDAT_INVALID_ARGUMENT;
   if (width_at_border < 3 || total_width < width_at_border || total_width > 12 || ((total_width - width_at_border) & 1u))
     return AMDAT_INVALID_ARGUMENT;
+  // k_decode_wave holds the 8 x width_at_border border samples of the gray models in LDS arrays of 80 entries: a border square of at
+  // most 10 cells, which is what a classic 8 x 8 family (64 bits, the widest word) needs
+  if (width_at_border > 10) return AMDAT_INVALID_ARGUMENT;
   FamilyHost f;
   f.d = 0; f.nbits = nbits; f.width_at_border = width_at_border; f.total_width = total_width; f.reversed_border = reversed_border ? 1 : 0;
   const int min_coord = ((int)width_at_border - (int)total_width) / 2;

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
         int flag = is_white ? 2 : 0;
         double v = 0;
         if (!(ix < 0 || iy < 0 || ix >= w || iy >= h)) { flag |= 1; v = (double)im[(size_t)iy * pitch + ix]; }
-        s_gx[sidx] = tagx; s_gy[sidx] = tagy; s_gv[sidx] = v; s_gflag[sidx] = flag;
+        s_gx[sidx] = tagx; s_gy[sidx] = tagy; s_gv[sidx] = v; s_gflag[sidx] = DW_SAMPLE_FLAG(flag, sidx);   // (tools_hooks.h: flag)
       }
       for (int i = lane; i < tw * tw; i += 64) s_values[i] = 0;
       __syncthreads();
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
         int best = 1 << 30, bid = 1 << 30;
         for (uint32_t c = lane; c < fam.ncodes; c += 64) {
           const int hd = __popcll(rcode ^ fam.codes[c]);
-          if (hd < best) { best = hd; bid = (int)c; }
+          if (DW_LANE_TAKES(hd, best)) { best = hd; bid = (int)c; }   // (tools_hooks.h: hd < best, the lane's first)
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(64, DW_WPE) void k_decode_wave(const FrameDesc* __r
         }
         if (best <= P.max_hamming) { id = bid; hamming = best; rotation = r; found = true; }
         else {   // pattern rotated by 90 degrees: bit i takes the value of bit rot_src[i]
-          const bool rb = lane < nbits && ((rcode >> (nbits - 1 - rsrc)) & 1ull);
+          const bool rb = DW_TURN_LANE(lane, nbits) && ((rcode >> (nbits - 1 - rsrc)) & 1ull);
           rcode = __brevll(__ballot(rb)) >> (64 - nbits);
         }
       }

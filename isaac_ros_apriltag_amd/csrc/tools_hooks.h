@@ -101,7 +101,12 @@
 //                               exact entry sits beside a wildcard of its family
 //                           55 = k_pose_refine keeps the handle's tag_size: wrong only in refined poses and covariances of tags whose
 //                               table size differs from it, never in a detection record
-//                           (4 .. 55 change values only: no address outside the frame, index bound or launch size; 43 and 44 run their
+//                           56 = the code scan (k_decode_wave) keeps a lane's LATER code at equal distance (hd <= best over c += 64): wrong
+//                               only where two equally near codes of a family have indices congruent mod 64
+//                           57 = the quarter turn's ballot (k_decode_wave) leaves lane 63 out: wrong only for a 64-bit family read turned
+//                           58 = the border samples of the gray models (k_decode_wave) are stored as invalid from index 64 on, the sample
+//                               loop's second trip: wrong only for a family with width_at_border 9 or 10
+//                           (4 .. 58 change values only: no address outside the frame, index bound or launch size; 43 and 44 run their
 //                           removal loop one round less; 53 reads one entry less)
 //                           the GPU suite ships them all (build.py: build_mutants) and asserts that its stage tests FAIL on each
 //                           (tests/test_gpu_parity.py::test_the_suite_fails_on_wrong_builds for 1 .. 5,
@@ -120,7 +125,8 @@
 //                           tests/test_fit_rules_gpu.py::test_the_fit_rule_tests_fail_on_the_wrong_builds for 37 .. 45,
 //                           tests/test_rig_bundles_gpu.py::test_the_rig_tests_fail_on_the_wrong_builds for 46 .. 48,
 //                           tests/test_raw_formats_gpu.py::test_the_raw_format_tests_fail_on_the_wrong_builds for 49 .. 52,
-//                           tests/test_tag_table_gpu.py::test_the_tag_table_tests_fail_on_the_wrong_builds for 53 .. 55)
+//                           tests/test_tag_table_gpu.py::test_the_tag_table_tests_fail_on_the_wrong_builds for 53 .. 55,
+//                           tests/test_decode_families_gpu.py::test_the_family_tests_fail_on_the_wrong_builds for 56 .. 58)
 // The stop builds key on P.max_nmaxima == 10 (always true) so that the compiler cannot fold the early exit at compile time
 // into dead-code elimination of the phases before it.
 #pragma once
@@ -358,6 +364,23 @@
 #define DW_TIE_TAKES(oi, bid) ((oi) > (bid))
 #else
 #define DW_TIE_TAKES(oi, bid) ((oi) < (bid))
+#endif
+// ---- k_decode_wave: whether distance hd replaces a lane's own best in the code scan (the lane's codes come in ascending index); the
+// ---- lanes whose bits enter the quarter turn's ballot; the valid bit of a border sample stored at index sidx -----------------------------
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 56
+#define DW_LANE_TAKES(hd, best) ((hd) <= (best))
+#else
+#define DW_LANE_TAKES(hd, best) ((hd) < (best))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 57
+#define DW_TURN_LANE(lane, nbits) ((lane) < (nbits) && (lane) < 63)
+#else
+#define DW_TURN_LANE(lane, nbits) ((lane) < (nbits))
+#endif
+#if defined(AMDAT_MUTATE) && AMDAT_MUTATE == 58
+#define DW_SAMPLE_FLAG(flag, sidx) ((sidx) >= 64 ? (flag) & ~1 : (flag))
+#else
+#define DW_SAMPLE_FLAG(flag, sidx) (flag)
 #endif
 
 // ---- k_reconcile: a containment test of quads_overlap_dev, and "margin a goes before margin b" of det_before_dev ------------------------------

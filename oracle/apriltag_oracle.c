@@ -83,6 +83,7 @@ int ato_custom_family(const char* name, uint32_t nbits, const int8_t* bit_x, con
   memset(out, 0, sizeof(*out));
   if (!name || !bit_x || !bit_y || !codes || nbits == 0 || nbits > 64 || ncodes == 0) return -1;
   if (width_at_border < 3 || total_width < width_at_border || total_width > 12 || ((total_width - width_at_border) & 1)) return -1;
+  if (width_at_border > 10) return -1;   /* the library's bound (include/apriltag_amd.h): both sides accept the same families */
   strncpy(out->name, name, sizeof(out->name) - 1);
   out->nbits = nbits; out->d = 0; out->width_at_border = width_at_border; out->total_width = total_width;
   out->reversed_border = reversed_border ? 1 : 0; out->ncodes = ncodes; out->codes = codes;

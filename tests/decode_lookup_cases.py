@@ -68,27 +68,36 @@ def words(name):
     """The family's test words: every 5th code exact; a sample of those with 1 to 4 flipped bits (max_hamming + 1 for every
     max_hamming); the same words carried through 1, 2 and 3 inverse quarter turns, so that the answer's rotation is 1, 2 or 3;
     midpoints between two codes at equal distance; 0 and all-ones; random words, about 4 000 words in all."""
-    def make():
-        f = family(name)
-        n, codes, src = f["nbits"], f["codes"], f["rot_src"]
-        rng = np.random.default_rng(1000 + NAMES.index(name))
-        exact = [codes[i] for i in range(0, len(codes), 5)]
-        step = max(1, len(exact) // 150)
-        flipped = [_flip(c, rng.choice(n, size=k, replace=False)) for c in exact[::step] for k in (1, 2, 3, 4)]
-        turned = [ref.unrotate(w, src, t) for t in (1, 2, 3) for w in (exact[::step] + flipped)[::3]]
-        mid = []
-        for i in range(0, len(codes), max(1, len(codes) // 200)):
-            others = [int(j) for j in rng.integers(0, len(codes), size=64)]
-            even = [(ref.popcount(codes[i] ^ codes[j]), j) for j in others if ref.popcount(codes[i] ^ codes[j]) % 2 == 0 and codes[j] != codes[i]]
-            if even:
-                d, j = min(even)
-                diff = [b for b in range(n) if ((codes[i] ^ codes[j]) >> b) & 1]
-                mid.append(_flip(codes[i], rng.choice(diff, size=d // 2, replace=False)))
-        crafted = exact + flipped + turned + mid + [0, (1 << n) - 1]
-        # random words fill up to about 4 000 (at least 500); a family of up to 12 bits gets every word there is
-        rand = list(range(1 << n)) if n <= 12 else [_random_word(rng, n) for _ in range(max(500, 4000 - len(crafted)))]
-        return tuple(crafted + rand)
-    return _cached(("words", name), make)
+    return _cached(("words+kinds", name), lambda: make_words(family(name), 1000 + NAMES.index(name)))[0]
+
+
+def kinds(name):
+    """Per word of words(name) the list it came from (make_words)."""
+    return _cached(("words+kinds", name), lambda: make_words(family(name), 1000 + NAMES.index(name)))[1]
+
+
+def make_words(f, seed):
+    """(words, kinds) of a family dict as family() returns it: the words as words() describes them and, per word, the list it came
+    from ("exact", "flipped", "turned", "mid", "edge" for 0 and all-ones, "random")."""
+    n, codes, src = f["nbits"], f["codes"], f["rot_src"]
+    rng = np.random.default_rng(seed)
+    exact = [codes[i] for i in range(0, len(codes), 5)]
+    step = max(1, len(exact) // 150)
+    flipped = [_flip(c, rng.choice(n, size=k, replace=False)) for c in exact[::step] for k in (1, 2, 3, 4)]
+    turned = [ref.unrotate(w, src, t) for t in (1, 2, 3) for w in (exact[::step] + flipped)[::3]]
+    mid = []
+    for i in range(0, len(codes), max(1, len(codes) // 200)):
+        others = [int(j) for j in rng.integers(0, len(codes), size=64)]
+        even = [(ref.popcount(codes[i] ^ codes[j]), j) for j in others if ref.popcount(codes[i] ^ codes[j]) % 2 == 0 and codes[j] != codes[i]]
+        if even:
+            d, j = min(even)
+            diff = [b for b in range(n) if ((codes[i] ^ codes[j]) >> b) & 1]
+            mid.append(_flip(codes[i], rng.choice(diff, size=d // 2, replace=False)))
+    crafted = exact + flipped + turned + mid + [0, (1 << n) - 1]
+    # random words fill up to about 4 000 (at least 500); a family of up to 12 bits gets every word there is
+    rand = list(range(1 << n)) if n <= 12 else [_random_word(rng, n) for _ in range(max(500, 4000 - len(crafted)))]
+    kinds = ["exact"] * len(exact) + ["flipped"] * len(flipped) + ["turned"] * len(turned) + ["mid"] * len(mid) + ["edge"] * 2 + ["random"] * len(rand)
+    return tuple(crafted + rand), tuple(kinds)
 
 
 def words4(name):

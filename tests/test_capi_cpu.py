@@ -177,6 +177,34 @@ def test_register_layout_family():
     assert L.amdAprilTagsFamilyFromName(b"bad") == -1
 
 
+def test_register_refuses_a_border_square_above_ten_cells():
+    """k_decode_wave holds 8 x 10 border samples: a layout with width_at_border 11 or 12 is refused by amdAprilTagsRegisterFamilyEx and
+    by the oracle's ato_custom_family alike, whatever else is right about it; the same four-cell layout with width_at_border 10 is
+    accepted by both, with and without an outer ring, and unregistered again."""
+    _need_lib()
+    from oracle import pyoracle as po
+
+    def layout(wb):   # one orbit of the quarter turn (x, y) -> (wb - 1 - y, x)
+        return [1, wb - 2, wb - 2, 1], [1, 1, wb - 2, wb - 2]
+    codes = [0b1010, 0b0110]
+    for wb, tw in ((11, 11), (12, 12)):
+        bx, by = layout(wb)
+        with pytest.raises(capi.AprilTagsError):
+            capi.register_family_ex(6, "wide", bx, by, wb, tw, False, codes)
+        with pytest.raises(ValueError):
+            po.custom_family("wide", bx, by, wb, tw, False, codes)
+        assert capi.lib().amdAprilTagsFamilyFromName(b"wide") == -1
+    for wb, tw in ((10, 12), (10, 10)):
+        bx, by = layout(wb)
+        try:
+            capi.register_family_ex(6, "wide", bx, by, wb, tw, False, codes)
+            assert capi.lib().amdAprilTagsFamilyFromName(b"wide") == 6
+        finally:
+            capi.unregister_family(6)
+        assert po.custom_family("wide", bx, by, wb, tw, False, codes).width_at_border == wb
+    assert capi.lib().amdAprilTagsFamilyFromName(b"wide") == -1
+
+
 def test_c99_example_compiles_and_links(tmp_path):
     """examples/detect_one.c is a plain C99 host of the C ABI (no C++, no HIP headers): it must compile with
     -pedantic -Werror against include/apriltag_amd.h and link against the in-tree library."""
